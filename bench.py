@@ -9,8 +9,12 @@ section 8a's M/T/I/X/Q/D/P rows, chained picture to picture (the deblocked,
 padded reconstruction of step i is the reference of step i+1).  Pictures,
 descriptors and decisions are resident in HBM before the timed region starts.
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, settles, warms up, times the K steps and prints the line;
+--full adds the figures measured after the timed region (roofline, CPU
+baseline, stream decode and encoder searches, the one-GPU comparison of N > 1).
 
 N > 1: every picture is sharded by rows of CUs across the ranks (CTU-row
 shards); the in-loop filter exchanges a 4-row halo with
@@ -103,6 +107,15 @@ def parse():
                          "process groups, RCCL exchanges) even with one rank; launch "
                          "through torch.distributed.run --nproc-per-node 1")
     ap.add_argument("--kernel-times", action="store_true", default=True)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also take the figures beside the headline: "
+                         "per-kernel launch times and roofline, the CPU baseline (--no-cpu "
+                         "skips it), the stream-decode and encoder-search figures (--no-decode "
+                         "skips them) and, with N > 1, the same workload on one GPU; a plain "
+                         "run times the steps and prints the line only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed - the reconstructed picture "
+                         "and the pass's results - to DIR/<name>.npy (float32 / float64)")
     return ap.parse_args()
 
 
@@ -640,6 +653,36 @@ def cpu_baseline(args, clip, bd, border):
 
 RDOQ_PACKED = None if os.environ.get("RDOQ_FUSED") is None else False
 
+DUMP_LIMIT = 60 << 20
+
+
+def dump_outputs(path, fp, rec, border):
+    """What a caller of the frame pass receives after the last timed step: the
+    padded reconstruction (float32 per plane) and FramePass.results() - motion
+    search results, nonzero counts, CU records, SSD parts - one float64 array
+    per field.  Above DUMP_LIMIT bytes in all, every array of more than 1 MB
+    keeps a fixed, seeded sample of its rows."""
+    res, nnz, cus, ssd = fp.results()
+    arrays = {"rec_" + n: p.astype(np.float32)
+              for n, p in zip(("y", "cb", "cr"), rec.download(border))}
+    for prefix, a in (("me_", res), ("cu_", cus)):
+        for f in a.dtype.names:
+            if f != "reserved":
+                arrays[prefix + f] = a[f].astype(np.float64)
+    arrays["nnz"] = nnz.astype(np.float64)
+    arrays["ssd"] = ssd.astype(np.float64)
+    big = [n for n, a in arrays.items() if a.nbytes > 1 << 20]
+    small = sum(a.nbytes for n, a in arrays.items() if n not in big)
+    total = small + sum(arrays[n].nbytes for n in big)
+    if total > DUMP_LIMIT:
+        for n in big:
+            a = arrays[n]
+            keep = len(a) * (DUMP_LIMIT - small) // (total - small)
+            arrays[n] = a[np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))]
+    os.makedirs(path, exist_ok=True)
+    for n, a in arrays.items():
+        np.save(os.path.join(path, n + ".npy"), a)
+
 
 def algorithmic_bytes(d, W, H):
     """Algorithmic bytes per launch of every kernel of the pass (DESIGN.md
@@ -893,7 +936,7 @@ def main_pictures(args, torch, api, pipeline, synth, world, rank, local_rank):
     # multi-GPU figure should be compared with - the N = 1 default of this
     # script is the chain workload, whose references are one picture away
     one_gpu = None
-    if world > 1 and rank == 0:
+    if world > 1 and rank == 0 and args.full:
         s1 = schedule.Schedule(n_pictures, 16, 2, 1, args.slots)
         e1 = picture_parallel.GpuPictureEngine(ctx, s1, 0, W, H, bd, args.qp, origs, None,
                                                rdoq=rdoq)
@@ -906,7 +949,7 @@ def main_pictures(args, torch, api, pipeline, synth, world, rank, local_rank):
         one_gpu = args.steps / (time.perf_counter() - t1)
     roof = cpu = None
     fp = eng.fps[0]
-    if rank == 0:
+    if rank == 0 and args.full:
         # per-kernel launch durations of the pass alone on rank 0 (the other ranks idle)
         recs = [ctx.picture(W, H, bd), ctx.picture(W, H, bd)]
         recs[0].upload(pad_planes(clip.frame(0), border), border)
@@ -967,7 +1010,8 @@ def main_pictures(args, torch, api, pipeline, synth, world, rank, local_rank):
                                                        "HOST STAGING (testing aid)", n_pictures),
                        "schedule_makespan_pictures": int(sched.makespan)},
             "roofline": roof,
-            "cpu_baseline": cpu if cpu is not None or world == 1 else quoted_cpu_baseline()}))
+            "cpu_baseline": (cpu if cpu is not None or world == 1 or not args.full
+                             else quoted_cpu_baseline())}))
     if comm is not None:
         comm.sync()
         comm.destroy()
@@ -998,6 +1042,8 @@ def main():
         mode = "chains" if world == 1 and not args.force_sharded else \
             ("subgop" if args.width * args.height <= 1920 * 1088 and not args.force_sharded
              else "rows")
+    if args.dump_outputs and (mode != "chains" or world > 1 or args.force_sharded):
+        raise SystemExit("--dump-outputs covers the one-rank chain schedule (--schedule chains)")
     if mode == "subgop":
         if args.gpus != world and world > 1:
             raise SystemExit("--gpus must equal WORLD_SIZE")
@@ -1202,6 +1248,13 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
 
+    if args.dump_outputs:
+        # the chain that ran the last timed step, whose buffers hold that step's results
+        last = settle + args.warmup + args.steps - 1
+        c, j = last % n_chains, last // n_chains
+        dfp, drecs = ((pfp if pipelined else fp), recs) if c == 0 else extra[c - 1][2:4]
+        dump_outputs(args.dump_outputs, dfp, drecs[(j + 1) % 2], border)
+
     # PSNR-Y of the last reconstructed picture (sanity, not timed)
     if runner is not None:
         ssd = runner.total_ssd()   # per-shard parts, all-reduced once here
@@ -1212,7 +1265,7 @@ def main():
     # ---- roofline of the dominant kernel: HIP events around it on the
     # context's stream, per launch, same data as the timed region ----
     roof = None
-    if rank == 0:
+    if rank == 0 and args.full:
         d = fp.desc
         # Per-kernel launch durations, averaged over one whole cycle of the
         # frame sequence (the searches are data dependent: 0.08-0.13 ms per
@@ -1351,10 +1404,10 @@ def main():
                                      for k, v in times.items() if v > 0}}
 
     cpu = None
-    if rank == 0 and not multi and not args.no_cpu:
+    if rank == 0 and not multi and not args.no_cpu and args.full:
         cpu = cpu_baseline(args, clip, bd, border)
     decode = None
-    if rank == 0 and not multi and not args.no_decode:
+    if rank == 0 and not multi and not args.no_decode and args.full:
         # its own context: the process holds more streams than the runtime has hardware
         # queues by now (the chains', the main context's), streams share queues in
         # creation order, and the host-bound decoder on the main context's stream ran at
@@ -1417,7 +1470,8 @@ def main():
                                         "RCCL send/recv groups issued by libxvcgpu.so" if native
                                         else "torch.distributed (%s)" % backend))},
             "roofline": roof,
-            "cpu_baseline": cpu if cpu is not None or world == 1 else quoted_cpu_baseline(),
+            "cpu_baseline": (cpu if cpu is not None or world == 1 or not args.full
+                             else quoted_cpu_baseline()),
             "stream_decode": decode,
         }
         print(json.dumps(out))

@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT
 out=$R/gpurun_out/ktrace
 rm -rf $out; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $out -o kt -- python $R/bench.py --no-cpu --no-decode --chains 1 --steps 60 --warmup 10 "$@" > $out/log.txt 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out -o kt -- python $R/bench.py --full --no-cpu --no-decode --chains 1 --steps 60 --warmup 10 "$@" > $out/log.txt 2>&1
 python - <<PY
 import csv, glob
 f = glob.glob("$out/**/*kernel_stats.csv", recursive=True)[0]

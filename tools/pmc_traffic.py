@@ -36,7 +36,7 @@ for k in sorted(set(fetch) | set(write)):
               "correction": "FETCH_SIZE x2 (gfx950 half-count of wide reads), WRITE_SIZE as is"}
 if len(sys.argv) > 5:
     out = {"kernel_source_md5": sys.argv[4], "quant": sys.argv[5],
-           "command": "python bench.py --no-cpu --no-decode --quant %s --steps 56 --warmup 14" % sys.argv[5],
+           "command": "python bench.py --full --no-cpu --no-decode --quant %s --steps 56 --warmup 14" % sys.argv[5],
            "kernels": out}
     json.dump(out, open(sys.argv[3], "w"), indent=1)
     out = out["kernels"]

@@ -14,7 +14,7 @@ R=$GRAFT_REPO_ROOT
 out=$R/gpurun_out/profile_$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-B="python $R/bench.py --quant $quant"
+B="python $R/bench.py --full --quant $quant"
 $B > $out/${tag}_bench.json 2> $out/bench.err
 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o st -- $B --no-cpu --no-decode > $out/stats.log 2>&1
 cp $(find $out/stats -name "*kernel_stats.csv" | head -1) $out/${tag}_bench_kernel_stats.csv

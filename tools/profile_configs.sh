@@ -8,7 +8,7 @@ mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 for cfg in "2160p 3840 2160 27 300 30" "4320p 7680 4320 37 100 10"; do
   set -- $cfg
-  B="python $R/bench.py --width $2 --height $3 --qp $4 --steps $5 --warmup $6 --no-decode"
+  B="python $R/bench.py --full --width $2 --height $3 --qp $4 --steps $5 --warmup $6 --no-decode"
   $B --cpu-frames 2 > $out/${tag}_bench_$1_qp$4.json 2> $out/bench_$1.err
   rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_$1 -o st -- $B --no-cpu > $out/stats_$1.log 2>&1
   cp $(find $out/stats_$1 -name "*kernel_stats.csv" | head -1) $out/${tag}_bench_$1_kernel_stats.csv
