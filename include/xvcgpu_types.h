@@ -517,7 +517,8 @@ typedef struct xvcgpu_mc_block {
  * the launches a host issues per picture - search, CompressAndEvalCbf,
  * deblocking, PadBorder, PSNR parts - selected by `phases`, in this order.
  * All pointers are device memory laid out as for the individual entry points. */
-#define XVC_FP_ENCODE 1     /* xvcgpu_me_search_sized + xvcgpu_recon_from_me    */
+#define XVC_FP_ENCODE 1     /* xvcgpu_me_search_sized, then xvcgpu_recon_from_me(_rdoq)
+                             * or the packed RDOQ pipeline (pred below)     */
 #define XVC_FP_DEBLOCK_V 2  /* xvcgpu_deblock_rows pass 0 on [db_y_begin, db_y_end) */
 #define XVC_FP_DEBLOCK_H 4  /* xvcgpu_deblock_rows pass 1 on [db_y_begin, dbh_y_end) */
 #define XVC_FP_PAD 8        /* xvcgpu_pad_border(rec)                           */
@@ -548,8 +549,10 @@ typedef struct xvcgpu_frame_pass_args {
   /* RDOQ, throughput form (pred != NULL): the residual pipeline split around
    * the packed quantiser - xvcgpu_mc_from_me -> xvcgpu_fwd_transform_batch ->
    * xvcgpu_quant_rdo_batch -> xvcgpu_inv_transform_batch ->
-   * xvcgpu_cu_info_from_me - with these work buffers (3 transform blocks per
-   * own CU: Y, U, V; d_rdoq_params indexed like d_tx) */
+   * xvcgpu_cu_info_from_me, or for CUs up to 16x16 xvcgpu_fwd_from_me_classify_prove ->
+   * xvcgpu_quant_rdo_classified_batch -> xvcgpu_inv_transform_cu_order - with these
+   * work buffers (3 transform blocks per own CU: Y, U, V; d_rdoq_params indexed like
+   * d_tx) */
   struct xvcgpu_picture *pred;
   const xvcgpu_tx_block *d_tx;
   const uint32_t *d_level_off;
@@ -566,9 +569,11 @@ typedef struct xvcgpu_frame_pass_args {
    * general class (xvcgpu_quant_rdo_set_four_lane_only, for this call's batch): pictures
    * of CUs 8x8 .. 16x16 coded with the diagonal scan, say */
   int32_t tx_four_lane_only;
-  /* the caller's word that every job of d_me is a 16x16 or a 16x8 CU (a picture whose width
-   * is a multiple of 16 on the 16-sample CU grid): XVCGPU_ME_ONLY_SQ16 for this call's search */
-  int32_t me_only_sq16;
+  /* the search's shape word, ORed into its flags (xvcgpu.h): 0; XVCGPU_ME_HINT_SQ16 where
+   * (almost) every job of d_me is a 16x16 or a 16x8 CU; XVCGPU_ME_HINT_SQ16 |
+   * XVCGPU_ME_ONLY_SQ16 where every job is one (a picture whose width is a multiple of 16
+   * on the 16-sample CU grid) */
+  int32_t me_shape;
 } xvcgpu_frame_pass_args;
 
 /* One job of xvcgpu_affine_me_batch: InterSearch::MotionEstAffine for one

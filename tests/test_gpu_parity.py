@@ -1401,6 +1401,69 @@ def test_pipelined_frame_pass(gpu, xo, size):
     ctx.use_own_stream()
 
 
+@pytest.mark.parametrize("kw,form", [
+    (dict(), "recon_from_me"), (dict(rdoq=True, rdoq_packed=False), "recon_from_me"),
+    (dict(rdoq=True), "fwd_from_me"), (dict(fused=False), "residual"),
+    (dict(fused=False, rdoq=True), "residual_rdoq"), (dict(cu=32), "residual"),
+    (dict(cu=32, rdoq=True), "fwd_transform")])
+def test_frame_pass_kernel_steps_match_run(gpu, xo, kw, form):
+    """Every form of the frame pass: its kernel_steps() run in order on one chain and
+    run() on another give the same bytes, equal to the oracle's, two chained pictures.
+    A run_phases() call with its own rows and SSD buffer changes nothing for the
+    run() after it."""
+    api, ctx = gpu
+    from xvc_amd import pipeline, synth
+    import oracle_frame
+    pw, ph, bd = 352, 288, 10
+    clip = synth.SyntheticClip(pw, ph, bd)
+    fps = [pipeline.FramePass(ctx, pw, ph, bd, qp=32, **kw) for _ in range(2)]
+    assert fps[0].form == form
+    pics = [[ctx.picture(pw, ph, bd) for _ in range(2)] for _ in fps]     # ref, rec per chain
+    O = ctx.picture(pw, ph, bd)
+    ref_host = pad_planes(clip.frame(0), bd)
+    for p in pics:
+        p[0].upload(ref_host, BL)
+    junk = ctx.alloc(16)
+    before = bytes(fps[1]._args())
+    fps[1].run_phases(O, None, pics[1][1], api.FP_PAD | api.FP_SSD, rows=(0, 16),
+                      ssd_rows=(0, 16), d_ssd=junk.ptr)
+    assert bytes(fps[1]._args()) == before
+    for n in (1, 2):
+        orig_host = pad_planes(clip.frame(n), bd)
+        O.upload(orig_host, BL)
+        for _, fn in fps[0].kernel_steps(O, pics[0][0], pics[0][1], ref_poc=n - 1):
+            fn()
+        fps[1].run(O, pics[1][0], pics[1][1], ref_poc=n - 1)
+        ctx.sync()
+        e_rec, e_res, e_nnz, e_cus, e_ssd = oracle_frame.frame_pass(
+            fps[0].desc, bd, orig_host, ref_host, BL, ref_poc=n - 1, lib=xo)
+        for fp, (_, Rec) in zip(fps, pics):
+            res, nnz, cus, ssd = fp.results()
+            assert np.array_equal(res, e_res) and np.array_equal(nnz, e_nnz), n
+            assert np.array_equal(cus, e_cus), n
+            assert (int(ssd[0]), int(ssd[1])) == e_ssd, n
+            got = Rec.download(BL)
+            for c in range(3):
+                assert np.array_equal(got[c], e_rec[c]), (n, c)
+        ref_host = e_rec
+        for p in pics:
+            p.reverse()          # the next picture references this reconstruction
+    if form == "fwd_from_me":
+        # the argument block of a fresh pass carries the caller's words from the start
+        big = pipeline.FramePass(ctx, 1920, 1080, bd, qp=32, rdoq=True)
+        a = big._args()
+        assert a.tx_four_lane_only == 1
+        assert a.me_shape == api.ME_HINT_SQ16 | api.ME_ONLY_SQ16
+        big.destroy()
+    junk.free()
+    for fp in fps:
+        fp.destroy()
+    for p in pics:
+        for q in p:
+            q.destroy()
+    O.destroy()
+
+
 @pytest.mark.parametrize("cu", [8, 32, 64])
 def test_frame_pass_cu_sizes(gpu, xo, cu):
     """Frame pass with other CU sizes (8: fused wave kernels; 32 / 64: the

@@ -147,7 +147,7 @@ class FramePassArgs(C.Structure):
                 ("pred", C.c_void_p), ("d_tx", C.c_void_p), ("d_level_off", C.c_void_p),
                 ("d_luma_tx_index", C.c_void_p), ("d_coeffs", C.c_void_p),
                 ("d_levels", C.c_void_p), ("n_tx", C.c_int32), ("n_coeffs", C.c_uint32),
-                ("scratch_rec", C.c_void_p), ("tx_four_lane_only", C.c_int32), ("me_only_sq16", C.c_int32)]
+                ("scratch_rec", C.c_void_p), ("tx_four_lane_only", C.c_int32), ("me_shape", C.c_int32)]
 
 
 FP_ENCODE, FP_DEBLOCK_V, FP_DEBLOCK_H, FP_PAD, FP_SSD = 1, 2, 4, 8, 16

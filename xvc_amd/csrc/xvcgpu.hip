@@ -2042,17 +2042,23 @@ xvcgpu_status xvcgpu_intra_select_modes(xvcgpu_ctx *ctx, const uint32_t *d_dist,
 }
 
 /* ---- a picture per call ---- */
+static const int kFramePassAll =
+    XVC_FP_ENCODE | XVC_FP_DEBLOCK_V | XVC_FP_DEBLOCK_H | XVC_FP_PAD | XVC_FP_SSD;
+
+// All phases over a whole picture of a size the fused tail (k_tail.h) covers, with its
+// scratch picture: the pass can end with that one launch instead of five (a->rec non-null)
+static bool whole_picture_pass(const xvcgpu_frame_pass_args *a, int phases) {
+  return a->scratch_rec && (phases & kFramePassAll) == kFramePassAll && a->n_cus > 0 &&
+         a->n_cus == a->n_cus_total && a->db_y_begin == 0 && a->db_y_end >= a->rec->h &&
+         a->dbh_y_end >= a->rec->h && a->ssd_y_begin == 0 && a->ssd_y_end >= a->rec->h &&
+         !(a->rec->w & 7) && !(a->rec->h & 7);
+}
+
 xvcgpu_status xvcgpu_frame_pass(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_args *a,
                                 int phases) {
   if (!ctx || !a || !a->rec) return XVCGPU_INVALID_ARGUMENT;
   xvcgpu_status st = XVCGPU_OK;
-  // the five launches of the tail as one (k_tail.h)
-  const int kAll = XVC_FP_ENCODE | XVC_FP_DEBLOCK_V | XVC_FP_DEBLOCK_H | XVC_FP_PAD | XVC_FP_SSD;
-  const bool fused_tail = a->scratch_rec && (phases & kAll) == kAll && a->n_cus > 0 &&
-                          a->n_cus == a->n_cus_total &&
-                          a->db_y_begin == 0 && a->db_y_end >= a->rec->h &&
-                          a->dbh_y_end >= a->rec->h && a->ssd_y_begin == 0 &&
-                          a->ssd_y_end >= a->rec->h && !(a->rec->w & 7) && !(a->rec->h & 7);
+  const bool fused_tail = whole_picture_pass(a, phases);
   xvcgpu_picture *const rec = fused_tail ? a->scratch_rec : a->rec;
   hipStream_t main_stream = nullptr;   // set while the pass runs on ctx->hi_stream
   struct Back {
@@ -2066,13 +2072,13 @@ xvcgpu_status xvcgpu_frame_pass(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_args *a
     }
   } back = {ctx, &main_stream};
   if ((phases & XVC_FP_ENCODE) && a->n_cus > 0) {
-    // the pass's jobs are the CUs of its grid: where the caller vouches that they are all
-    // 16x16 (16x8 in the bottom row of a 1080-line picture) the search's exact-shape kernel
-    // (a pass of smaller CUs must not take it: its jobs would all be left to the few waves
-    // of the leftover kernel)
+    // the pass's jobs are the CUs of its grid: where the caller's shape word says that they
+    // are (almost) all 16x16 (16x8 in the bottom row of a 1080-line picture) the search's
+    // exact-shape kernel (a pass of smaller CUs must not take it: its jobs would all be left
+    // to the few waves of the leftover kernel)
     st = xvcgpu_me_search_sized(ctx, a->orig, a->ref,
                                 XVCGPU_ME_FULLPEL | XVCGPU_ME_SUBPEL |
-                                    (a->me_only_sq16 ? XVCGPU_ME_HINT_SQ16 | XVCGPU_ME_ONLY_SQ16 : 0),
+                                    (a->me_shape & (XVCGPU_ME_HINT_SQ16 | XVCGPU_ME_ONLY_SQ16)),
                                 a->d_me, a->n_cus, a->d_results, a->max_block_size);
     if (st != XVCGPU_OK) return st;
     if (a->d_rdoq_params && a->pred) {
@@ -2181,21 +2187,17 @@ xvcgpu_status xvcgpu_frame_pass_multi(xvcgpu_ctx *const *ctxs,
                                       int phases) {
   if (!ctxs || !args || n < 1 || !ctxs[0]) return XVCGPU_INVALID_ARGUMENT;
   xvcgpu_ctx *ctx = ctxs[0];
-  const int kAll = XVC_FP_ENCODE | XVC_FP_DEBLOCK_V | XVC_FP_DEBLOCK_H | XVC_FP_PAD | XVC_FP_SSD;
   // the form the launches below cover: whole pictures of CUs up to 16x16 (and at
   // least 8x8: scratch_rec), all phases, the packed RDOQ pipeline or QuantFast;
   // anything else runs picture by picture, each on its own context
-  bool batched = n >= 2 && n <= XVC_MULTI_MAX && (phases & kAll) == kAll;
+  bool batched = n >= 2 && n <= XVC_MULTI_MAX && (phases & kFramePassAll) == kFramePassAll;
   for (int i = 0; i < n && batched; i++) {
     const xvcgpu_frame_pass_args *a = args[i];
     if (!ctxs[i] || !a || !a->orig || !a->ref || !a->rec) return XVCGPU_INVALID_ARGUMENT;
     const bool rdoq_packed = a->d_rdoq_params && a->pred && a->n_tx == 3 * a->n_cus;
     const bool fast = !a->d_rdoq_params;
-    batched = a->scratch_rec && a->n_cus > 0 && a->n_cus == a->n_cus_total &&
-              a->max_block_size <= 16 && (rdoq_packed || fast) &&
-              (rdoq_packed == (args[0]->d_rdoq_params != nullptr)) && a->db_y_begin == 0 &&
-              a->db_y_end >= a->rec->h && a->dbh_y_end >= a->rec->h && a->ssd_y_begin == 0 &&
-              a->ssd_y_end >= a->rec->h && !(a->rec->w & 7) && !(a->rec->h & 7) &&
+    batched = whole_picture_pass(a, phases) && a->max_block_size <= 16 && (rdoq_packed || fast) &&
+              (rdoq_packed == (args[0]->d_rdoq_params != nullptr)) &&
               a->rec->w == args[0]->rec->w && a->rec->h == args[0]->rec->h &&
               a->rec->bd == args[0]->rec->bd && ctxs[i]->device == ctx->device &&
               // what the launches below dereference (the single-picture path

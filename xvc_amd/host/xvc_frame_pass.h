@@ -40,6 +40,7 @@ class FramePass {
     map_stride_ = (width + 3) / 4;
     std::vector<int32_t> map(static_cast<size_t>(map_stride_) * ((height + 3) / 4), -1);
     std::vector<xvcgpu_me_block> me;
+    size_t sq16 = 0;   // jobs of the search's exact-shape kernel: 16x16 and 16x8
     for (int y = 0; y < height; y += cu)
       for (int x = 0; x < width; x += cu) {
         xvcgpu_me_block b = xvcgpu_me_block();
@@ -53,9 +54,14 @@ class FramePass {
         for (int yy = y / 4; yy < (y + b.h) / 4; yy++)
           for (int xx = x / 4; xx < (x + b.w) / 4; xx++)
             map[static_cast<size_t>(yy) * map_stride_ + xx] = static_cast<int32_t>(me.size());
+        sq16 += b.w == 16 && (b.h == 16 || b.h == 8);
         me.push_back(b);
       }
     n_cus_ = static_cast<int>(me.size());
+    // the search's shape word, as pipeline.FramePass sets it: the hint where at least 98 %
+    // of the jobs have those shapes, and the word that no job has another where all do
+    me_shape_ = me.empty() || 50 * sq16 < 49 * me.size() ? 0 : XVCGPU_ME_HINT_SQ16;
+    if (!me.empty() && sq16 == me.size()) me_shape_ |= XVCGPU_ME_ONLY_SQ16;
     d_me_.reset(new DeviceArray<xvcgpu_me_block>(ctx, me));
     d_map_.reset(new DeviceArray<int32_t>(ctx, map));
     d_res_.reset(new DeviceArray<xvcgpu_me_result>(ctx, me.size()));
@@ -93,6 +99,7 @@ class FramePass {
     a.ssd_y_end = 1 << 30;
     a.shift_bitdepth = bd_;
     a.d_ssd = d_ssd_->data();
+    a.me_shape = me_shape_;
     ctx_.Check(xvcgpu_frame_pass(ctx_.get(), &a,
                                  XVC_FP_ENCODE | XVC_FP_DEBLOCK_V | XVC_FP_DEBLOCK_H |
                                      XVC_FP_PAD | XVC_FP_SSD));
@@ -109,7 +116,7 @@ class FramePass {
 
  private:
   const Context &ctx_;
-  int w_, h_, bd_, qp_, qp_c_, n_cus_, map_stride_, max_cu_;
+  int w_, h_, bd_, qp_, qp_c_, n_cus_, map_stride_, max_cu_, me_shape_;
   std::unique_ptr<DeviceArray<xvcgpu_me_block>> d_me_;
   std::unique_ptr<DeviceArray<int32_t>> d_map_;
   std::unique_ptr<DeviceArray<xvcgpu_me_result>> d_res_;

@@ -187,12 +187,9 @@ def run_multi(passes, origs, refs, recs, ref_pocs=None):
     n = len(passes)
     lead = passes[0].ctx
     ctxs = (C.c_void_p * n)(*[p.ctx.h for p in passes])
-    argv = (C.POINTER(api.FramePassArgs) * n)()
-    for i, p in enumerate(passes):
-        a = p._args()
-        a.orig, a.ref, a.rec = origs[i].h_pic, refs[i].h_pic, recs[i].h_pic
-        a.ref_poc = ref_pocs[i] if ref_pocs is not None else 0
-        argv[i] = C.pointer(a)
+    args = [p._call_args(origs[i], refs[i], recs[i], ref_pocs[i] if ref_pocs is not None else 0)
+            for i, p in enumerate(passes)]
+    argv = (C.POINTER(api.FramePassArgs) * n)(*[C.pointer(a) for a in args])
     lead._check(lead.lib.xvcgpu_frame_pass_multi(
         ctxs, argv, n, api.FP_ENCODE | api.FP_DEBLOCK_V | api.FP_DEBLOCK_H | api.FP_PAD |
         api.FP_SSD))
@@ -219,7 +216,6 @@ class FramePass:
         # forward and the inverse half of the residual pipeline: 5 launches instead
         # of the one fused launch, an order of magnitude less time
         self.rdoq_packed = rdoq and (fused if rdoq_packed is None else rdoq_packed)
-        self.tx_four_lane_only = False       # set below, from the transform blocks
         if self.rdoq_packed:
             keep_levels = True
         # keep_levels: also store the quantised coefficients of every TU (what
@@ -229,6 +225,16 @@ class FramePass:
         self.w, self.h, self.bd = width, height, bitdepth
         self.desc = d = FrameDescriptors(width, height, qp, cu, search_range,
                                          row_range, rdoq, bitdepth, xcd_tiles)
+        # the form of the launches between the search and the tail (_launches), named
+        # after the launch that sets it apart
+        if cu <= 16 and self.fused:
+            self.form = "recon_from_me"     # fused: QuantFast or the RDOQ kernel
+        elif cu <= 16 and self.rdoq_packed:
+            self.form = "fwd_from_me"       # packed RDOQ
+        elif self.rdoq_packed:
+            self.form = "fwd_transform"     # packed RDOQ behind mc_from_me
+        else:
+            self.form = "residual_rdoq" if rdoq else "residual"
         self.d_rdoq_ctx = ctx.buffer(d.rdoq_contexts) if rdoq else None
         self.d_rdoq_prm = ctx.buffer(d.rdoq_params) if rdoq else None
         self.d_me = ctx.buffer(d.me)
@@ -238,8 +244,7 @@ class FramePass:
         sq = (d.me["w"] == 16) & ((d.me["h"] == 16) | (d.me["h"] == 8)) if len(d.me) else np.zeros(0, bool)
         self.me_flags = api.ME_FULLPEL | api.ME_SUBPEL | \
             (api.ME_HINT_SQ16 if len(sq) and sq.mean() >= 0.98 else 0)
-        self.me_only_sq16 = bool(len(sq)) and bool(sq.all())
-        if self.me_only_sq16:        # ... all of them: no second kernel for other shapes
+        if len(sq) and sq.all():     # ... all of them: no second kernel for other shapes
             self.me_flags |= api.ME_ONLY_SQ16
         self.d_tx = ctx.buffer(d.tx)
         # no block of the quantiser's general class (diagonal scan, 4x4 sub-blocks, sides up
@@ -261,10 +266,9 @@ class FramePass:
         # whole pictures of CUs >= 8x8 end with ONE launch (xvcgpu_deblock_pad_ssd:
         # unfiltered reconstruction in `scratch` -> deblocked, padded `rec` + SSD)
         # instead of deblock V, H, pad, SSD, SSD fold
-        self.scratch = None
-        if cu >= 8 and width % 8 == 0 and height % 8 == 0 and d.row_range == (0, d.h) \
-                and os.environ.get("XVC_TAIL_FUSED", "1") != "0":
-            self.scratch = ctx.picture(width, height, bitdepth)
+        self.fused_tail = cu >= 8 and width % 8 == 0 and height % 8 == 0 and \
+            d.row_range == (0, d.h) and os.environ.get("XVC_TAIL_FUSED", "1") != "0"
+        self.scratch = ctx.picture(width, height, bitdepth) if self.fused_tail else None
         self.d_levels = self.d_level_off = None
         self.n_levels = 0
         if keep_levels:
@@ -281,8 +285,8 @@ class FramePass:
         return self.d_cus.ptr + api.CU_DTYPE.itemsize * self.desc.cu_base
 
     def _args(self):
-        """The picture-per-call argument block (xvcgpu_frame_pass), built once;
-        only the picture handles, the reference POC and row ranges change."""
+        """The picture-per-call argument block (xvcgpu_frame_pass), built once and
+        never written after: a call fills a copy (_call_args)."""
         if getattr(self, "_fp_args", None) is None:
             d, a = self.desc, api.FramePassArgs()
             a.d_me, a.d_results, a.n_cus = self.d_me.ptr, self.d_res.ptr, d.n_cus
@@ -301,19 +305,24 @@ class FramePass:
                 a.d_level_off, a.d_luma_tx_index = self.d_level_off.ptr, self.d_luma_idx.ptr
                 a.d_coeffs, a.d_levels = self.d_coeffs.ptr, self.d_levels.ptr
                 a.n_coeffs = self.n_levels
+            a.tx_four_lane_only = int(self.tx_four_lane_only)
+            a.me_shape = self.me_flags & (api.ME_HINT_SQ16 | api.ME_ONLY_SQ16)
             self._fp_args = a
         return self._fp_args
+
+    def _call_args(self, orig, ref, rec, ref_poc=0):
+        """A copy of _args() with one call's pictures and reference POC."""
+        a = api.FramePassArgs.from_buffer_copy(self._args())
+        a.orig = orig.h_pic if orig is not None else None
+        a.ref = ref.h_pic if ref is not None else None
+        a.rec, a.ref_poc = rec.h_pic, ref_poc
+        return a
 
     def run_phases(self, orig, ref, rec, phases, ref_poc=0, rows=None, dbh_end=None,
                    ssd_rows=None, d_ssd=None):
         """One call for the selected phases (api.FP_*).  Needs the fused
         CompressAndEvalCbf kernel (CUs up to 16x16) for FP_ENCODE."""
-        a = self._args()
-        a.orig = orig.h_pic if orig is not None else None
-        a.ref = ref.h_pic if ref is not None else None
-        a.rec, a.ref_poc = rec.h_pic, ref_poc
-        a.tx_four_lane_only = 1 if self.tx_four_lane_only else 0
-        a.me_only_sq16 = 1 if self.me_only_sq16 else 0
+        a = self._call_args(orig, ref, rec, ref_poc)
         if rows is not None:
             a.db_y_begin, a.db_y_end = rows
             a.dbh_y_end = dbh_end if dbh_end is not None else rows[1]
@@ -323,151 +332,89 @@ class FramePass:
             a.d_ssd = d_ssd
         self.ctx._check(self.ctx.lib.xvcgpu_frame_pass(self.ctx.h, C.byref(a), phases))
 
+    def _launches(self, orig, ref, rec, ref_poc, fused_tail):
+        """The pass's launches as (name, callable) in issue order, split into the
+        encode part (search -> prediction, transform, quantiser, reconstruction ->
+        CU metadata of the own CUs; empty without CUs) and the tail (deblocking,
+        padding, SSD).  fused_tail: the encode part reconstructs into `scratch` and
+        the tail is the one deblock_pad_ssd launch from there into rec.
+        The quant_rdo launches run without the promise xvcgpu_frame_pass gives the
+        quantiser for its batch (tx_four_lane_only: the general-class launch left
+        out), so that bench.py's per-kernel times stay what they were."""
+        ctx, d, lib = self.ctx, self.desc, self.ctx.lib
+        n, T, bd, form = d.n_cus, len(d.tx), self.bd, self.form
+        out = self.scratch if fused_tail else rec
+        me, res, nnz, cus = self.d_me.ptr, self.d_res.ptr, self.d_nnz.ptr, self.d_cus_own
+        lv = self.d_levels.ptr if self.d_levels else None
+        lo = self.d_level_off.ptr if self.d_level_off else None
+        rq = (self.d_rdoq_ctx.ptr, self.d_rdoq_prm.ptr) if self.rdoq else ()
+        all_cus, stride = self.d_cus.ptr, d.cu_map.shape[1]
+        if fused_tail:
+            tail = [("deblock_pad_ssd", lambda: ctx.deblock_pad_ssd_dev(
+                out, rec, orig, all_cus, d.n_cus_total, self.d_map.ptr, stride, 0, 0, 0, bd,
+                self.d_ssd.ptr))]
+        else:
+            tail = [("deblock", lambda: ctx.deblock_dev(rec, all_cus, d.n_cus_total,
+                                                        self.d_map.ptr, stride, 0, 0, 0, 4)),
+                    ("pad_border", lambda: ctx.pad_border(rec)),
+                    ("picture_ssd", lambda: ctx.picture_ssd_dev(orig, rec, 0, bd,
+                                                                self.d_ssd.ptr))]
+        if n == 0:
+            return [], tail
+        enc = [("me_search", lambda: ctx.me_search_dev(orig, ref, self.me_flags, me, n, res,
+                                                       d.cu_size))]
+        if form == "recon_from_me":
+            # MC + transform/quant/recon + CU metadata in one launch; the prediction
+            # never leaves LDS
+            recon = ctx.recon_from_me_rdoq_dev if self.rdoq else ctx.recon_from_me_dev
+            enc.append(("recon_from_me", lambda: recon(orig, ref, out, me, res, n, d.qp, d.qp_c,
+                                                       ref_poc, nnz, cus, *rq)))
+        elif form == "fwd_from_me":
+            # the prediction goes into the reconstruction's picture, the inverse half then
+            # works in place (and skips the blocks without levels); on the way the kernel
+            # classifies the blocks for the quantiser, proves with the quantiser's contexts
+            # which are all zero (xvcgpu_quant_rdo_set_prove_zero) and writes the CU records
+            co, nc = self.d_coeffs.ptr, C.c_size_t(self.n_levels)
+            enc += [
+                ("fwd_from_me", lambda: ctx._check(lib.xvcgpu_fwd_from_me_classify_prove(
+                    ctx.h, orig.h_pic, ref.h_pic, out.h_pic, me, res, n, d.qp, d.qp_c, ref_poc,
+                    co, lo, nc, lv, nnz, cus, *rq))),
+                ("quant_rdo", lambda: ctx._check(lib.xvcgpu_quant_rdo_classified_batch(
+                    ctx.h, bd, self.d_tx.ptr, T, co, lo, nc, lv, nnz, *rq, cus))),
+                # blocks 3 * cu + comp: U and V of a CU share a wave
+                ("inv_transform", lambda: ctx._check(lib.xvcgpu_inv_transform_cu_order(
+                    ctx.h, out.h_pic, self.d_tx.ptr, n, lv, lo, nnz)))]
+        else:
+            enc.append(("mc_from_me", lambda: ctx.mc_from_me_dev(ref, self.pred, me, res, n)))
+            if form == "fwd_transform":
+                co, nc = self.d_coeffs.ptr, C.c_size_t(self.n_levels)
+                enc += [
+                    ("fwd_transform", lambda: ctx._check(lib.xvcgpu_fwd_transform_batch(
+                        ctx.h, orig.h_pic, self.pred.h_pic, self.d_tx.ptr, T, co, lo))),
+                    ("quant_rdo", lambda: ctx._check(lib.xvcgpu_quant_rdo_batch(
+                        ctx.h, bd, self.d_tx.ptr, T, co, lo, nc, lv, nnz, *rq))),
+                    ("inv_transform", lambda: ctx._check(lib.xvcgpu_inv_transform_batch(
+                        ctx.h, self.pred.h_pic, out.h_pic, self.d_tx.ptr, T, lv, lo, nnz)))]
+            elif form == "residual_rdoq":
+                enc.append(("residual_rdoq", lambda: ctx.residual_rdoq_batch_dev(
+                    orig, self.pred, out, self.d_tx.ptr, T, lv, lo, nnz, *rq)))
+            else:
+                enc.append(("residual", lambda: ctx.residual_batch_dev(
+                    orig, self.pred, out, self.d_tx.ptr, T, lv, lo, nnz)))
+            enc.append(("cu_info", lambda: ctx.cu_info_from_me_dev(
+                me, res, nnz, self.d_luma_idx.ptr, n, d.qp, d.qp_c, ref_poc, cus)))
+        return enc, tail
+
     def encode(self, orig, ref, rec, ref_poc=0):
         """ME -> MC -> residual -> CU metadata for the own CUs (asynchronous)."""
-        ctx, d = self.ctx, self.desc
-        n = d.n_cus
-        if n == 0:
-            return
-        ctx.me_search_dev(orig, ref, self.me_flags, self.d_me.ptr, n, self.d_res.ptr, d.cu_size)
-        if self.fused and d.cu_size <= 16:
-            # MC + transform/quant/recon + CU metadata in one launch; the
-            # prediction never leaves LDS
-            if self.rdoq:
-                ctx.recon_from_me_rdoq_dev(orig, ref, rec, self.d_me.ptr, self.d_res.ptr, n,
-                                           d.qp, d.qp_c, ref_poc, self.d_nnz.ptr,
-                                           self.d_cus_own, self.d_rdoq_ctx.ptr,
-                                           self.d_rdoq_prm.ptr)
-            else:
-                ctx.recon_from_me_dev(orig, ref, rec, self.d_me.ptr, self.d_res.ptr, n,
-                                      d.qp, d.qp_c, ref_poc, self.d_nnz.ptr, self.d_cus_own)
-            return
-        front_fused = self.rdoq_packed and d.cu_size <= 16    # xvcgpu_fwd_from_me
-        if not front_fused:
-            ctx.mc_from_me_dev(ref, self.pred, self.d_me.ptr, self.d_res.ptr, n)
-        if self.rdoq_packed:
-            lib, T = ctx.lib, len(d.tx)
-            # fwd_from_me: the prediction goes into the reconstruction's picture, the
-            # inverse half then works in place (and skips the blocks without levels)
-            pred_pic = rec if front_fused else self.pred
-            if front_fused:     # ... which also classifies the blocks for the quantiser
-                # (with the quantiser's contexts: blocks it can prove all zero on the
-                # spot never reach the walk - xvcgpu_quant_rdo_set_prove_zero)
-                ctx._check(lib.xvcgpu_fwd_from_me_classify_prove(
-                    ctx.h, orig.h_pic, ref.h_pic, rec.h_pic, self.d_me.ptr,
-                    self.d_res.ptr, n, d.qp, d.qp_c, ref_poc, self.d_coeffs.ptr,
-                    self.d_level_off.ptr, C.c_size_t(self.n_levels), self.d_levels.ptr,
-                    self.d_nnz.ptr, self.d_cus_own, self.d_rdoq_ctx.ptr, self.d_rdoq_prm.ptr))
-            else:
-                ctx._check(lib.xvcgpu_fwd_transform_batch(
-                    ctx.h, orig.h_pic, self.pred.h_pic, self.d_tx.ptr, T, self.d_coeffs.ptr,
-                    self.d_level_off.ptr))
-            quant = lib.xvcgpu_quant_rdo_classified_batch if front_fused else \
-                lib.xvcgpu_quant_rdo_batch
-            ctx._check(quant(
-                ctx.h, self.bd, self.d_tx.ptr, T, self.d_coeffs.ptr, self.d_level_off.ptr,
-                C.c_size_t(self.n_levels), self.d_levels.ptr, self.d_nnz.ptr,
-                self.d_rdoq_ctx.ptr, self.d_rdoq_prm.ptr,
-                *([self.d_cus_own] if front_fused else [])))
-            if front_fused:   # blocks 3 * cu + comp, in place: U and V of a CU share a wave
-                ctx._check(lib.xvcgpu_inv_transform_cu_order(
-                    ctx.h, rec.h_pic, self.d_tx.ptr, n, self.d_levels.ptr, self.d_level_off.ptr,
-                    self.d_nnz.ptr))
-            else:
-                ctx._check(lib.xvcgpu_inv_transform_batch(
-                    ctx.h, pred_pic.h_pic, rec.h_pic, self.d_tx.ptr, T, self.d_levels.ptr,
-                    self.d_level_off.ptr, self.d_nnz.ptr))
-        elif self.rdoq:
-            ctx.residual_rdoq_batch_dev(orig, self.pred, rec, self.d_tx.ptr, len(d.tx),
-                                        self.d_levels.ptr if self.d_levels else None,
-                                        self.d_level_off.ptr if self.d_level_off else None,
-                                        self.d_nnz.ptr, self.d_rdoq_ctx.ptr, self.d_rdoq_prm.ptr)
-        else:
-            ctx.residual_batch_dev(orig, self.pred, rec, self.d_tx.ptr, len(d.tx),
-                                   self.d_levels.ptr if self.d_levels else None,
-                                   self.d_level_off.ptr if self.d_level_off else None,
-                                   self.d_nnz.ptr)
-        if not front_fused:      # (front_fused: the records were written on the way)
-            ctx.cu_info_from_me_dev(self.d_me.ptr, self.d_res.ptr, self.d_nnz.ptr,
-                                    self.d_luma_idx.ptr, n, d.qp, d.qp_c, ref_poc,
-                                    self.d_cus_own)
+        for _, fn in self._launches(orig, ref, rec, ref_poc, False)[0]:
+            fn()
 
     def kernel_steps(self, orig, ref, rec, ref_poc=0):
         """The launches of one frame pass as (name, callable) in issue order - for
         per-kernel timing (bench.py); run in order they are a frame pass."""
-        ctx, d, lib = self.ctx, self.desc, self.ctx.lib
-        n, T = d.n_cus, len(d.tx)
-        final = rec
-        if self.scratch is not None:
-            rec = self.scratch
-        steps = [("me_search", lambda: ctx.me_search_dev(
-            orig, ref, self.me_flags, self.d_me.ptr, n, self.d_res.ptr, d.cu_size))]
-        if self.fused and d.cu_size <= 16:
-            if self.rdoq:
-                steps.append(("recon_from_me", lambda: ctx.recon_from_me_rdoq_dev(
-                    orig, ref, rec, self.d_me.ptr, self.d_res.ptr, n, d.qp, d.qp_c, ref_poc,
-                    self.d_nnz.ptr, self.d_cus_own, self.d_rdoq_ctx.ptr, self.d_rdoq_prm.ptr)))
-            else:
-                steps.append(("recon_from_me", lambda: ctx.recon_from_me_dev(
-                    orig, ref, rec, self.d_me.ptr, self.d_res.ptr, n, d.qp, d.qp_c, ref_poc,
-                    self.d_nnz.ptr, self.d_cus_own)))
-        else:
-            front_fused = self.rdoq_packed and d.cu_size <= 16
-            lv = self.d_levels.ptr if self.d_levels else None
-            lo = self.d_level_off.ptr if self.d_level_off else None
-            # fwd_from_me writes the prediction into the reconstruction's picture, the
-            # inverse half works in place (as xvcgpu_frame_pass does)
-            pred_pic = rec if front_fused else self.pred
-            if front_fused:
-                steps.append(("fwd_from_me", lambda: ctx._check(
-                    lib.xvcgpu_fwd_from_me_classify_prove(
-                        ctx.h, orig.h_pic, ref.h_pic, rec.h_pic, self.d_me.ptr,
-                        self.d_res.ptr, n, d.qp, d.qp_c, ref_poc, self.d_coeffs.ptr, lo,
-                        C.c_size_t(self.n_levels), lv, self.d_nnz.ptr, self.d_cus_own,
-                        self.d_rdoq_ctx.ptr, self.d_rdoq_prm.ptr))))
-            else:
-                steps.append(("mc_from_me", lambda: ctx.mc_from_me_dev(
-                    ref, self.pred, self.d_me.ptr, self.d_res.ptr, n)))
-            if self.rdoq_packed:
-                if not front_fused:
-                    steps.append(("fwd_transform", lambda: ctx._check(
-                        lib.xvcgpu_fwd_transform_batch(ctx.h, orig.h_pic, self.pred.h_pic,
-                                                       self.d_tx.ptr, T, self.d_coeffs.ptr, lo))))
-                steps += [
-                    ("quant_rdo", lambda: ctx._check(
-                        (lib.xvcgpu_quant_rdo_classified_batch if front_fused else
-                         lib.xvcgpu_quant_rdo_batch)(
-                            ctx.h, self.bd, self.d_tx.ptr, T, self.d_coeffs.ptr, lo,
-                            C.c_size_t(self.n_levels), lv, self.d_nnz.ptr, self.d_rdoq_ctx.ptr,
-                            self.d_rdoq_prm.ptr, *([self.d_cus_own] if front_fused else [])))),
-                    ("inv_transform", lambda: ctx._check(
-                        lib.xvcgpu_inv_transform_cu_order(ctx.h, rec.h_pic, self.d_tx.ptr, n, lv,
-                                                          lo, self.d_nnz.ptr) if front_fused else
-                        lib.xvcgpu_inv_transform_batch(ctx.h, pred_pic.h_pic, rec.h_pic,
-                                                       self.d_tx.ptr, T, lv, lo,
-                                                       self.d_nnz.ptr)))]
-            elif self.rdoq:
-                steps.append(("residual_rdoq", lambda: ctx.residual_rdoq_batch_dev(
-                    orig, self.pred, rec, self.d_tx.ptr, T, lv, lo, self.d_nnz.ptr,
-                    self.d_rdoq_ctx.ptr, self.d_rdoq_prm.ptr)))
-            else:
-                steps.append(("residual", lambda: ctx.residual_batch_dev(
-                    orig, self.pred, rec, self.d_tx.ptr, T, lv, lo, self.d_nnz.ptr)))
-            if not front_fused:
-                steps.append(("cu_info", lambda: ctx.cu_info_from_me_dev(
-                    self.d_me.ptr, self.d_res.ptr, self.d_nnz.ptr, self.d_luma_idx.ptr, n, d.qp,
-                    d.qp_c, ref_poc, self.d_cus_own)))
-        if self.scratch is not None:
-            steps.append(("deblock_pad_ssd", lambda: ctx.deblock_pad_ssd_dev(
-                rec, final, orig, self.d_cus.ptr, d.n_cus_total, self.d_map.ptr,
-                d.cu_map.shape[1], 0, 0, 0, self.bd, self.d_ssd.ptr)))
-            return steps
-        steps += [
-            ("deblock", lambda: ctx.deblock_dev(rec, self.d_cus.ptr, d.n_cus_total,
-                                                self.d_map.ptr, d.cu_map.shape[1], 0, 0, 0, 4)),
-            ("pad_border", lambda: ctx.pad_border(rec)),
-            ("picture_ssd", lambda: ctx.picture_ssd_dev(orig, rec, 0, self.bd, self.d_ssd.ptr))]
-        return steps
+        enc, tail = self._launches(orig, ref, rec, ref_poc, self.fused_tail)
+        return enc + tail
 
     def deblock_rows(self, rec, pass_, y0, y1):
         d = self.desc
@@ -476,27 +423,19 @@ class FramePass:
 
     def run(self, orig, ref, rec, ref_poc=0, deblock=True, pad=True, ssd=True):
         """Enqueue one whole-picture frame pass (asynchronous)."""
-        ctx, d = self.ctx, self.desc
-        if (self.fused or self.rdoq_packed) and d.cu_size <= 16 and d.row_range == (0, d.h):
+        d = self.desc
+        if self.form in ("recon_from_me", "fwd_from_me") and d.row_range == (0, d.h):
             # the whole sequence behind one C call (xvcgpu_frame_pass)
             self.run_phases(orig, ref, rec, api.FP_ENCODE |
                             (api.FP_DEBLOCK_V | api.FP_DEBLOCK_H if deblock else 0) |
                             (api.FP_PAD if pad else 0) | (api.FP_SSD if ssd else 0), ref_poc)
             return
-        if self.scratch is not None and deblock and pad and ssd:
-            self.encode(orig, ref, self.scratch, ref_poc)
-            ctx.deblock_pad_ssd_dev(self.scratch, rec, orig, self.d_cus.ptr, d.n_cus_total,
-                                    self.d_map.ptr, d.cu_map.shape[1], 0, 0, 0, self.bd,
-                                    self.d_ssd.ptr)
-            return
-        self.encode(orig, ref, rec, ref_poc)
-        if deblock:
-            ctx.deblock_dev(rec, self.d_cus.ptr, d.n_cus_total, self.d_map.ptr,
-                            d.cu_map.shape[1], 0, 0, 0, 4)
-        if pad:
-            ctx.pad_border(rec)
-        if ssd:
-            ctx.picture_ssd_dev(orig, rec, 0, self.bd, self.d_ssd.ptr)
+        enc, tail = self._launches(orig, ref, rec, ref_poc,
+                                   self.fused_tail and deblock and pad and ssd)
+        skip = {"deblock": not deblock, "pad_border": not pad, "picture_ssd": not ssd}
+        for name, fn in enc + tail:
+            if not skip.get(name):
+                fn()
 
     def results(self):
         d = self.desc
@@ -573,17 +512,9 @@ class PipelinedFramePass:
 
     def destroy(self):
         self.sync()
-        self.bot.d_cus = None
-        for fp in (self.top, self.bot):
-            for b in (fp.d_me, fp.d_tx, fp.d_luma_idx, fp.d_map, fp.d_res, fp.d_nnz,
-                      fp.d_cus, fp.d_ssd, fp.d_levels, fp.d_level_off,
-                      fp.d_rdoq_ctx, fp.d_rdoq_prm, fp.d_coeffs):
-                if b is not None:
-                    b.free()
-            fp.pred.destroy()
-            if fp.scratch is not None:
-                fp.scratch.destroy()
-                fp.scratch = None
+        self.bot.d_cus = None       # top's: freed once, with top
+        self.top.destroy()
+        self.bot.destroy()
 
 
 class DecodePass:

@@ -699,10 +699,7 @@ class GpuEngine:
 
     def frame_pass_args(self, orig, ref_idx, rec_idx, ref_poc):
         """The picture's xvcgpu_frame_pass_args (row ranges are the shard engine's)."""
-        a = self.fp._args()
-        a.orig = orig.h_pic
-        a.ref = self.pictures[ref_idx].h_pic
-        a.rec, a.ref_poc = self.pictures[rec_idx].h_pic, ref_poc
+        a = self.fp._call_args(orig, self.pictures[ref_idx], self.pictures[rec_idx], ref_poc)
         a.d_ssd = self.ssd_mem.data_ptr()
         return a
 
