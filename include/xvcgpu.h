@@ -822,6 +822,36 @@ xvcgpu_status xvcgpu_picture_import(xvcgpu_ctx *ctx, xvcgpu_picture *pic,
 xvcgpu_status xvcgpu_picture_export(xvcgpu_ctx *ctx, const xvcgpu_picture *pic,
                                     void *d_dst, int display_width, int display_height,
                                     int out_bitdepth, int dither);
+/* PictureDecoder::Postprocess -> Resampler::ConvertTo (resample.cc:94-148) with
+ * every output format of xvc_decoder_parameters: any size (the 8-tap up /
+ * 12-tap down filters of resample::Resample), 4:0:0 / 4:2:0 / 4:2:2 / 4:4:4
+ * (with the exact-2x bilinear chroma path), interleaved ARGB through the
+ * BT.601 / 709 / 2020 matrices, 8-16 bit.  The display_width x display_height
+ * top-left part of the picture -> d_dst, the reference's bytes: planar planes
+ * back to back, rows tightly packed, 1 byte per sample at <= 8 bit, else 2
+ * (little endian); ARGB is four values per pixel in the order
+ * ConvertColorSpace writes them (R, G, B, alpha = max).  Unset fields of `fmt`
+ * are resolved as Decoder resolves them; d_dst holds xvcgpu_output_bytes of the
+ * resolved format (for ARGB, aligned to 4 bytes per value).
+ *
+ * Edge rule (the one deliberate deviation): positions outside the picture are
+ * clamped to its internal size, i.e. the picture is read as if
+ * YuvPicture::PadBorder had run.  The reference pads only pictures with
+ * tid == 0 or below the highest layer (picture_decoder.cc:198-199); for those
+ * the bytes are the reference's, for the others they are in the interior and
+ * at the edge this is the defined value where the reference reads a stale
+ * border.  The device border is never read and the picture never written.
+ *
+ * XVCGPU_INVALID_ARGUMENT, with nothing written: a display size below 2 or
+ * beyond the picture, an output width or height of 1 or above 32768 (or more
+ * than INT_MAX samples), an unknown chroma format or matrix, a bit depth
+ * outside 8..16, and the bilinear chroma path at out = in depth + 1 (its shift
+ * is undefined in the reference: 4:4:4 at bd + 1, ARGB from an 11-bit
+ * picture).  One launch per picture; with dither on a shift plane, three. */
+size_t xvcgpu_output_bytes(const xvcgpu_output_format *fmt);
+xvcgpu_status xvcgpu_picture_convert_to(xvcgpu_ctx *ctx, const xvcgpu_picture *pic,
+                                        int display_width, int display_height,
+                                        const xvcgpu_output_format *fmt, void *d_dst);
 /* Checksum::CalculateCrc (checksum.cc:46-92): CRC-16 (0x1021, preset 0xffff,
  * low byte of a sample first, 16 trailing zero bits).  mode 0 = kMinOverhead:
  * one value over Y,U,V, d_hash[0..1]; mode 1 = kMaxRobust: one per plane,

@@ -683,4 +683,17 @@ typedef struct xvcgpu_copy_segment {
   uint64_t bytes;
 } xvcgpu_copy_segment;
 
+/* The output fields of xvc_decoder_parameters (xvc_dec_lib/xvcdec.h): what
+ * xvcgpu_picture_convert_to produces.  Unset fields take the picture's values
+ * as Decoder resolves them (decoder.cc:162-176). */
+typedef struct xvcgpu_output_format {
+  int32_t width, height;   /* luma samples; 0 = the display size                  */
+  int32_t chroma_format;   /* 0 = 4:0:0, 1 = 4:2:0, 2 = 4:2:2, 3 = 4:4:4,
+                              4 = ARGB, 255 = the picture's (4:2:0)               */
+  int32_t color_matrix;    /* 0 = undefined (the 709 table), 1 = 601, 2 = 709,
+                              3 = 2020                                            */
+  int32_t bitdepth;        /* 0 = the picture's, else 8..16                       */
+  int32_t dither;          /* the reference's error-feedback down-shift           */
+} xvcgpu_output_format;
+
 #endif /* XVCGPU_TYPES_H_ */

@@ -192,7 +192,7 @@ SYMBOLS = [
     "xvcgpu_comm_group_end", "xvcgpu_comm_send_picture", "xvcgpu_comm_recv_picture",
     "xvcgpu_comm_send_rows", "xvcgpu_comm_recv_rows", "xvcgpu_comm_all_reduce_sum_u64",
     "xvcgpu_comm_send_bytes", "xvcgpu_comm_recv_bytes", "xvcgpu_inv_transform_dist_batch",
-    "xvcgpu_fwd_from_me",
+    "xvcgpu_fwd_from_me", "xvcgpu_output_bytes", "xvcgpu_picture_convert_to",
 ]
 
 _vp = C.c_void_p
@@ -368,11 +368,14 @@ def load_library():
         "xvcgpu_quant_rdo_classified_batch": [_vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_size_t,
                                               _vp, _vp, _vp, _vp, _vp],
         "xvcgpu_comm_recv_bytes": [_vp, _vp, C.c_size_t, C.c_int],
+        "xvcgpu_picture_convert_to": [_vp, _vp, C.c_int, C.c_int, C.POINTER(OutputFormat), _vp],
     }
     lib.xvcgpu_event_destroy.restype = None
     lib.xvcgpu_event_destroy.argtypes = [_vp]
     lib.xvcgpu_comm_destroy.restype = None
     lib.xvcgpu_comm_destroy.argtypes = [_vp]
+    lib.xvcgpu_output_bytes.restype = C.c_size_t
+    lib.xvcgpu_output_bytes.argtypes = [C.POINTER(OutputFormat)]
     for name, args in sigs.items():
         f = getattr(lib, name)
         f.restype = C.c_int
@@ -517,6 +520,37 @@ class Comm:
         if self.h:
             self.ctx.lib.xvcgpu_comm_destroy(self.h)
             self.h = None
+
+
+class OutputFormat(C.Structure):
+    """xvcgpu_output_format (include/xvcgpu_types.h): the output fields of
+    xvc_decoder_parameters.  width / height 0 = the display size, chroma_format
+    0 = 4:0:0, 1 = 4:2:0, 2 = 4:2:2, 3 = 4:4:4, 4 = ARGB, 255 = the picture's;
+    color_matrix 0 = undefined (709 table), 1 = 601, 2 = 709, 3 = 2020;
+    bitdepth 0 = the picture's."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("chroma_format", C.c_int32),
+                ("color_matrix", C.c_int32), ("bitdepth", C.c_int32), ("dither", C.c_int32)]
+
+    def __init__(self, width=0, height=0, chroma_format=255, color_matrix=0, bitdepth=0,
+                 dither=False):
+        super().__init__(int(width), int(height), int(chroma_format), int(color_matrix),
+                         int(bitdepth), int(bool(dither)))
+
+    def resolved(self, display_w, display_h, bitdepth):
+        """The defaults filled in as Decoder does (decoder.cc:162-176)."""
+        return OutputFormat(self.width or display_w, self.height or display_h,
+                            1 if self.chroma_format == 255 else self.chroma_format,
+                            self.color_matrix, self.bitdepth or bitdepth, self.dither)
+
+    def __repr__(self):
+        return "OutputFormat(%s)" % ", ".join("%s=%d" % (n, getattr(self, n))
+                                              for n, _ in self._fields_)
+
+
+def output_bytes(fmt):
+    """xvcgpu_output_bytes of a resolved format (host only; 0 if invalid)."""
+    lib = load_library()
+    return int(lib.xvcgpu_output_bytes(C.byref(fmt)))
 
 
 class Picture:
@@ -1011,6 +1045,23 @@ class Context:
         out = d.to_array(np.uint8, n).tobytes()
         d.free()
         return out
+
+    def picture_convert_to(self, pic, disp_w, disp_h, fmt, d_dst=None):
+        """Resampler::ConvertTo on the device (xvcgpu_picture_convert_to).
+        Returns the output bytes; with d_dst (a device pointer holding
+        output_bytes(fmt.resolved(...))) writes there and returns None."""
+        if d_dst is not None:
+            self._check(self.lib.xvcgpu_picture_convert_to(self.h, pic.h_pic, disp_w, disp_h,
+                                                           C.byref(fmt), d_dst))
+            return None
+        n = output_bytes(fmt.resolved(disp_w, disp_h, pic.bd))
+        d = self.alloc(max(n, 8))
+        try:
+            self._check(self.lib.xvcgpu_picture_convert_to(self.h, pic.h_pic, disp_w, disp_h,
+                                                           C.byref(fmt), d.ptr))
+            return d.to_array(np.uint8, n).tobytes()
+        finally:
+            d.free()
 
     def picture_crc(self, pic, mode=0):
         d = self.alloc(8)

@@ -21,6 +21,7 @@
 #include "k_recon.h"
 #include "k_bipred.h"
 #include "k_stats.h"
+#include "k_output.h"
 #include "k_intra.h"
 #include "k_affine_me.h"
 #include "k_inter_pred.h"
@@ -1814,6 +1815,211 @@ xvcgpu_status xvcgpu_picture_export(xvcgpu_ctx *ctx, const xvcgpu_picture *pic,
   hipLaunchKernelGGL(picture_export_kernel, dim3(a.h[0], 3), dim3(256), 0, ctx->stream,
                      pic->v, a);
   CHECK_LAUNCH(ctx, "picture_export");
+  return XVCGPU_OK;
+}
+
+/* ---- output formats (Resampler::ConvertTo) ---- */
+static const int kOutMaxDim = 32768;
+
+// util::ScaleSizeX / ScaleSizeY of an output format, plane c
+static int out_plane_w(int w, int cf, int c) { return c == 0 || cf >= 3 ? w : w >> 1; }
+static int out_plane_h(int h, int cf, int c) { return c == 0 || cf >= 2 ? h : h >> 1; }
+
+static bool out_format_valid(const xvcgpu_output_format &f) {
+  if (f.width < 2 || f.height < 2 || f.width > kOutMaxDim || f.height > kOutMaxDim) return false;
+  if (f.chroma_format < 0 || f.chroma_format > 4) return false;
+  if (f.color_matrix < 0 || f.color_matrix > 3) return false;
+  if (f.bitdepth < 8 || f.bitdepth > 16) return false;
+  return true;
+}
+
+// util::GetTotalNumSamples; the reference holds it in an int
+static int64_t out_total_samples(const xvcgpu_output_format &f) {
+  const int64_t luma = (int64_t)f.width * f.height;
+  if (f.chroma_format == 4) return 4 * luma;
+  if (f.chroma_format == 0) return luma;
+  return luma + 2 * (int64_t)out_plane_w(f.width, f.chroma_format, 1) *
+                    out_plane_h(f.height, f.chroma_format, 1);
+}
+
+size_t xvcgpu_output_bytes(const xvcgpu_output_format *fmt) {
+  if (!fmt || !out_format_valid(*fmt)) return 0;
+  const int64_t n = out_total_samples(*fmt);
+  if (n > INT32_MAX) return 0;
+  return (size_t)n * (fmt->bitdepth > 8 ? 2 : 1);
+}
+
+// resample.cc GetFilterFromScale
+static int out_filter_from_scale(int scale) {
+  const int k = XVC_OUT_SCALE_ONE;
+  if (scale > 15 * k / 4) return 7;
+  if (scale > 20 * k / 7) return 6;
+  if (scale > 5 * k / 2) return 5;
+  if (scale > 2 * k) return 4;
+  if (scale > 5 * k / 3) return 3;
+  if (scale > 5 * k / 4) return 2;
+  if (scale > 20 * k / 19) return 1;
+  return 0;
+}
+
+// Output rows per tile of a resampled plane: the most (<= XVC_OUT_MAX_TR) whose
+// every tile needs at most XVC_OUT_TMP_ROWS filtered source rows.
+static int out_resample_tile_rows(int dh, int scale_y) {
+  for (int tr = XVC_OUT_MAX_TR; tr > 1; tr >>= 1) {
+    int64_t worst = 0;
+    for (int y0 = 0; y0 < dh; y0 += tr) {
+      const int64_t y1 = std::min(y0 + tr, dh) - 1;
+      worst = std::max(worst, ((y1 * scale_y) >> 15) - (((int64_t)y0 * scale_y) >> 15));
+    }
+    if (worst + 12 <= XVC_OUT_TMP_ROWS) return tr;
+  }
+  return 1;
+}
+
+xvcgpu_status xvcgpu_picture_convert_to(xvcgpu_ctx *ctx, const xvcgpu_picture *pic,
+                                        int display_width, int display_height,
+                                        const xvcgpu_output_format *fmt, void *d_dst) {
+  if (!ctx || !pic || !fmt || !d_dst) return XVCGPU_INVALID_ARGUMENT;
+  if (display_width < 2 || display_height < 2 || display_width > pic->w ||
+      display_height > pic->h)
+    return fail(ctx, XVCGPU_INVALID_ARGUMENT, "convert_to: display size");
+  // Decoder's defaults (decoder.cc:162-176); the source is 4:2:0
+  xvcgpu_output_format f = *fmt;
+  if (f.width == 0) f.width = display_width;
+  if (f.height == 0) f.height = display_height;
+  if (f.chroma_format == 255) f.chroma_format = 1;
+  if (f.bitdepth == 0) f.bitdepth = pic->bd;
+  if (!out_format_valid(f) || out_total_samples(f) > INT32_MAX)
+    return fail(ctx, XVCGPU_INVALID_ARGUMENT, "convert_to: output format");
+  const int cf = f.chroma_format, bd = pic->bd;
+  const bool argb = cf == 4;
+  // CopyToWithResize produces ARGB's components at kColorConversionBitdepth
+  const int dst_bd = argb ? 12 : f.bitdepth;
+  if (argb && ((uintptr_t)d_dst & (f.bitdepth > 8 ? 7 : 3)))
+    return fail(ctx, XVCGPU_INVALID_ARGUMENT, "convert_to: ARGB destination alignment");
+  {
+    const xvcgpu_status st_ = ensure_stats(ctx, 2 * pic->h);
+    if (st_ != XVCGPU_OK) return st_;
+  }
+  OutArgs a;
+  memset(&a, 0, sizeof(a));
+  a.np = cf == 0 ? 1 : 3;
+  a.wide = dst_bd > 8;
+  a.smax = (1 << dst_bd) - 1;
+  a.dst = static_cast<uint8_t *>(d_dst);
+  ExportArgs ex;  // the dithered shift planes, for the export carry kernels
+  memset(&ex, 0, sizeof(ex));
+  bool dither_rows = false;
+  int carry_rows = 0, total_blocks = 0, max_rows = 0;
+  size_t off = 0;
+  for (int c = 0; c < a.np; c++) {
+    OutPlane &q = a.p[c];
+    const int sw = c ? display_width >> 1 : display_width;
+    const int sh = c ? display_height >> 1 : display_height;
+    q.src_c = c;
+    q.dw = out_plane_w(f.width, cf, c);
+    q.dh = out_plane_h(f.height, cf, c);
+    q.iw = pic->v.c[c].w;
+    q.ih = pic->v.c[c].h;
+    q.dst_off = off;
+    off += (size_t)q.dw * q.dh * (a.wide ? 2 : 1);
+    // ConvertTo's plain path (same size, 4:2:0 or 4:0:0) is this branch for every plane
+    if (q.dw == sw && q.dh == sh) {
+      q.kind = kOutShift;
+      if (dst_bd >= bd || (!a.wide && bd <= 8)) {
+        q.mode = 0;
+        q.shift = a.wide ? dst_bd - bd : 0;
+      } else {
+        q.mode = f.dither ? 2 : 1;
+        q.shift = bd - dst_bd;
+      }
+      if (q.mode == 2) {
+        dither_rows = true;
+        q.row_base = carry_rows;
+        ex.w[c] = q.dw;
+        ex.h[c] = q.dh;
+        ex.row_base[c] = carry_rows;
+        ex.shift = q.shift;
+        carry_rows += q.dh;
+        max_rows = std::max(max_rows, q.dh);
+      }
+    } else if (c && q.dw == 2 * sw && q.dh == 2 * sh) {
+      q.kind = kOutBilinear;
+      q.shift = dst_bd - bd;
+      if (q.shift == 1)
+        return fail(ctx, XVCGPU_INVALID_ARGUMENT,
+                    "convert_to: bilinear chroma at out = in bitdepth + 1 (undefined)");
+      q.tile_rows = XVC_OUT_POINT_TR;
+    } else {
+      q.kind = kOutResample;
+      q.scale_x = ((sw << 15) + (q.dw >> 1)) / q.dw;
+      q.scale_y = ((sh << 15) + (q.dh >> 1)) / q.dh;
+      q.filt_x = out_filter_from_scale(q.scale_x);
+      q.filt_y = out_filter_from_scale(q.scale_y);
+      q.shift_hor = std::max(bd - 10, 0);
+      q.shift_ver = 12 - q.shift_hor + bd - dst_bd;
+      q.tile_rows = out_resample_tile_rows(q.dh, q.scale_y);
+    }
+  }
+  if (argb) {
+    // one tile grid for the three components: the smallest tile height
+    int tr = XVC_OUT_MAX_TR;
+    bool filter = false;
+    for (int c = 0; c < 3; c++) {
+      if (a.p[c].kind == kOutShift) a.p[c].tile_rows = XVC_OUT_POINT_TR;
+      filter |= a.p[c].kind == kOutResample;
+      tr = std::min(tr, a.p[c].tile_rows);
+    }
+    for (int c = 0; c < 3; c++) {
+      a.p[c].tile_rows = tr;
+      a.p[c].tiles_x = (a.p[c].dw + XVC_OUT_TW - 1) / XVC_OUT_TW;
+    }
+    a.argb_wide = f.bitdepth > 8;
+    a.argb_max = (1 << f.bitdepth) - 1;
+    a.argb_shift = 10 + 12 - f.bitdepth;
+    static const int kM[4][3][3] = {  // ConvertColorSpace kM: default (= 709), 601, 709, 2020
+        {{1192, 0, 1877}, {1192, -223, -558}, {1192, 2212, 0}},
+        {{1192, 0, 1671}, {1192, -410, -851}, {1192, 2112, 0}},
+        {{1192, 0, 1877}, {1192, -223, -558}, {1192, 2212, 0}},
+        {{1192, 0, 1758}, {1192, -196, -681}, {1192, 2243, 0}}};
+    memcpy(a.m, kM[f.color_matrix], sizeof(a.m));
+    const int blocks = a.p[0].tiles_x * ((a.p[0].dh + tr - 1) / tr);
+    if (filter)
+      hipLaunchKernelGGL(output_argb_kernel<true>, dim3(blocks), dim3(256), 0, ctx->stream,
+                         pic->v, a);
+    else
+      hipLaunchKernelGGL(output_argb_kernel<false>, dim3(blocks), dim3(256), 0, ctx->stream,
+                         pic->v, a);
+    CHECK_LAUNCH(ctx, "output_argb");
+    return XVCGPU_OK;
+  }
+  for (int c = 0; c < a.np; c++) {
+    OutPlane &q = a.p[c];
+    if (q.kind == kOutShift) {
+      q.blocks = q.dh;
+    } else {
+      q.tiles_x = (q.dw + XVC_OUT_TW - 1) / XVC_OUT_TW;
+      q.blocks = q.tiles_x * ((q.dh + q.tile_rows - 1) / q.tile_rows);
+    }
+    total_blocks += q.blocks;
+  }
+  uint32_t *row_words = ctx->d_stats + kStatsHistWords;  // 2 * pic->h rows >= carry_rows
+  a.row_carry = row_words;
+  if (dither_rows) {
+    hipLaunchKernelGGL(export_row_sums_kernel, dim3(max_rows, 3), dim3(256), 0, ctx->stream,
+                       pic->v, ex, row_words);
+    hipLaunchKernelGGL(export_row_scan_kernel, dim3(3), dim3(256), 0, ctx->stream, ex,
+                       row_words);
+  }
+  bool filter = false;
+  for (int c = 0; c < a.np; c++) filter |= a.p[c].kind == kOutResample;
+  if (filter)
+    hipLaunchKernelGGL(output_planar_kernel<true>, dim3(total_blocks), dim3(256), 0,
+                       ctx->stream, pic->v, a);
+  else
+    hipLaunchKernelGGL(output_planar_kernel<false>, dim3(total_blocks), dim3(256), 0,
+                       ctx->stream, pic->v, a);
+  CHECK_LAUNCH(ctx, "output_planar");
   return XVCGPU_OK;
 }
 

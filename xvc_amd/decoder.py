@@ -47,6 +47,10 @@ def load_host_library():
     lib.xvc_host_picture_decoder_destroy.argtypes = [vp]
     lib.xvc_host_picture_decoder_decode.argtypes = [vp, vp, vp, vp, C.POINTER(vp), vp]
     lib.xvc_host_picture_decoder_decode_sequence.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
+    lib.xvc_host_picture_decoder_set_output_format.argtypes = [
+        vp, C.POINTER(api.OutputFormat), C.c_int, C.c_int]
+    lib.xvc_host_picture_decoder_decode_sequence_out.argtypes = [vp, C.c_int, vp, vp, vp, vp,
+                                                                 vp, vp]
     lib.xvc_host_picture_decoder_waves.argtypes = [vp]
     lib.xvc_host_picture_decoder_launches.argtypes = [vp]
     lib.xvc_host_picture_decoder_one_launch_intra.argtypes = [vp, C.c_int]
@@ -100,11 +104,19 @@ class PictureDecoder:
         self.ctx._check(self.lib.xvc_host_picture_decoder_add_lane(self.h, ctx.h))
         self._lanes = getattr(self, "_lanes", []) + [ctx]
 
-    def decode_sequence(self, pictures, ref_index, recs):
+    def set_output_format(self, fmt, display_w, display_h):
+        """The output format (api.OutputFormat) decode_sequence(..., outs=) converts
+        every picture to (PictureDecoder::Postprocess)."""
+        self.ctx._check(self.lib.xvc_host_picture_decoder_set_output_format(
+            self.h, C.byref(fmt), display_w, display_h))
+
+    def decode_sequence(self, pictures, ref_index, recs, outs=None):
         """pictures: [(ps, cus, levels)] in decoding order; ref_index[i][list][k]: the
         position in this sequence of picture i's reference (list, k), -1 = unused; recs:
         [api.Picture] outputs.  The C++ layer plans picture i + 1 on a worker thread
-        while it uploads and launches picture i (xvc_gpu::PictureDecoder::DecodeSequence)."""
+        while it uploads and launches picture i (xvc_gpu::PictureDecoder::DecodeSequence).
+        outs: device pointers, one per picture, that receive the picture in the format
+        of set_output_format."""
         n = len(pictures)
         keep = []
         ps_p, cu_p, lv_p = (C.c_void_p * n)(), (C.c_void_p * n)(), (C.c_void_p * n)()
@@ -114,8 +126,13 @@ class PictureDecoder:
             ps_p[i], cu_p[i], lv_p[i] = ps.ctypes.data, cus.ctypes.data, lv.ctypes.data
         ri = np.ascontiguousarray(ref_index, np.int32).reshape(n, 2, 5)
         rp = (C.c_void_p * n)(*[r.h_pic for r in recs])
-        st = self.lib.xvc_host_picture_decoder_decode_sequence(self.h, n, ps_p, cu_p, lv_p,
-                                                               ri.ctypes.data, rp)
+        if outs is None:
+            st = self.lib.xvc_host_picture_decoder_decode_sequence(self.h, n, ps_p, cu_p, lv_p,
+                                                                   ri.ctypes.data, rp)
+        else:
+            op = (C.c_void_p * n)(*outs)
+            st = self.lib.xvc_host_picture_decoder_decode_sequence_out(
+                self.h, n, ps_p, cu_p, lv_p, ri.ctypes.data, rp, op)
         self.ctx._check(st)
 
     @property

@@ -652,13 +652,31 @@ xvcgpu_status PictureDecoder::IssuePacked(const PicturePlan &p, const xvc_pictur
 // The pictures of a sequence, planning one ahead of issuing: while this thread uploads
 // and launches picture i, a worker validates and plans picture i + 1 (pure host work,
 // 0.1 ms per 1080p B picture - as long as the device takes for the picture).
+void PictureDecoder::SetOutputFormat(const xvcgpu_output_format &fmt, int display_w,
+                                     int display_h) {
+  has_output_ = true;
+  output_ = fmt;
+  output_display_w_ = display_w;
+  output_display_h_ = display_h;
+}
+
 xvcgpu_status PictureDecoder::DecodeSequence(int n, const xvc_picture_syntax *const *ps,
                                              const xvc_cu_syntax *const *cus,
                                              const int16_t *const *levels,
                                              const int32_t *ref_index,
                                              xvcgpu_picture *const *recs) {
+  return DecodeSequence(n, ps, cus, levels, ref_index, recs, nullptr);
+}
+
+xvcgpu_status PictureDecoder::DecodeSequence(int n, const xvc_picture_syntax *const *ps,
+                                             const xvc_cu_syntax *const *cus,
+                                             const int16_t *const *levels,
+                                             const int32_t *ref_index,
+                                             xvcgpu_picture *const *recs,
+                                             void *const *d_out) {
   if (n < 0 || (n && (!ps || !cus || !levels || !ref_index || !recs)))
     return XVCGPU_INVALID_ARGUMENT;
+  if (d_out && !has_output_) return XVCGPU_INVALID_ARGUMENT;
   if (!n) return XVCGPU_OK;
   // With lanes a picture is ordered behind the pictures it REFERENCES only: a buffer
   // handed in twice (a recycled DPB entry) would be written on one lane while another
@@ -825,6 +843,9 @@ xvcgpu_status PictureDecoder::DecodeSequence(int n, const xvc_picture_syntax *co
         st = pd->IssuePacked(plans[i % kRing], *ps[i], q.lay, q.mem, q.copied, refs, recs[i]);
         q.in_flight = true;
       }
+      if (st == XVCGPU_OK && d_out)   // Postprocess
+        st = xvcgpu_picture_convert_to(pd->ctx_, recs[i], output_display_w_, output_display_h_,
+                                       &output_, d_out[i]);
       if (st == XVCGPU_OK && n_lanes > 1) st = xvcgpu_event_record(pd->ctx_, pic_done_[i]);
     }
     t_issue += now() - tb;
@@ -891,6 +912,25 @@ int xvc_host_picture_decoder_decode_sequence(xvc_host_picture_decoder *d, int n,
                                              xvcgpu_picture *const *recs) {
   if (!d) return XVCGPU_INVALID_ARGUMENT;
   return d->dec.DecodeSequence(n, ps, cus, levels, ref_index, recs);
+}
+
+int xvc_host_picture_decoder_set_output_format(xvc_host_picture_decoder *d,
+                                               const xvcgpu_output_format *fmt,
+                                               int display_w, int display_h) {
+  if (!d || !fmt) return XVCGPU_INVALID_ARGUMENT;
+  d->dec.SetOutputFormat(*fmt, display_w, display_h);
+  return XVCGPU_OK;
+}
+
+int xvc_host_picture_decoder_decode_sequence_out(xvc_host_picture_decoder *d, int n,
+                                                 const xvc_picture_syntax *const *ps,
+                                                 const xvc_cu_syntax *const *cus,
+                                                 const int16_t *const *levels,
+                                                 const int32_t *ref_index,
+                                                 xvcgpu_picture *const *recs,
+                                                 void *const *d_out) {
+  if (!d || !d_out) return XVCGPU_INVALID_ARGUMENT;
+  return d->dec.DecodeSequence(n, ps, cus, levels, ref_index, recs, d_out);
 }
 
 void xvc_host_picture_decoder_one_launch_intra(xvc_host_picture_decoder *d, int on) {

@@ -118,6 +118,16 @@ class PictureDecoder {
   xvcgpu_status DecodeSequence(int n, const xvc_picture_syntax *const *ps,
                                const xvc_cu_syntax *const *cus, const int16_t *const *levels,
                                const int32_t *ref_index, xvcgpu_picture *const *recs);
+  // PictureDecoder::Postprocess: with d_out, picture i is also converted to the output
+  // format of SetOutputFormat into d_out[i] (xvcgpu_output_bytes of it) on the lane
+  // that decoded it, right after its in-loop filter and padding.
+  xvcgpu_status DecodeSequence(int n, const xvc_picture_syntax *const *ps,
+                               const xvc_cu_syntax *const *cus, const int16_t *const *levels,
+                               const int32_t *ref_index, xvcgpu_picture *const *recs,
+                               void *const *d_out);
+  // The output fields of xvc_decoder_parameters (xvcgpu_output_format, unset fields
+  // resolved per picture by xvcgpu_picture_convert_to) and the display size.
+  void SetOutputFormat(const xvcgpu_output_format &fmt, int display_w, int display_h);
 
   // Picture-level parallelism (the reference decoder's picture threads,
   // xvc_dec_lib/thread_decoder.cc): a further lane = another context (its own stream)
@@ -180,6 +190,9 @@ class PictureDecoder {
   int next_host_;
   std::vector<std::unique_ptr<PictureDecoder>> lanes_;   // lanes 1 .. (this is lane 0)
   std::vector<xvcgpu_event *> pic_done_;                  // per position of a sequence
+  bool has_output_ = false;                               // SetOutputFormat called
+  xvcgpu_output_format output_ = {};
+  int output_display_w_ = 0, output_display_h_ = 0;
 };
 
 }  // namespace xvc_gpu
@@ -201,6 +214,18 @@ int xvc_host_picture_decoder_decode_sequence(xvc_host_picture_decoder *d, int n,
                                              const int16_t *const *levels,
                                              const int32_t *ref_index,
                                              xvcgpu_picture *const *recs);
+// PictureDecoder::SetOutputFormat / DecodeSequence with d_out (one device buffer per
+// picture, in decoding order)
+int xvc_host_picture_decoder_set_output_format(xvc_host_picture_decoder *d,
+                                               const xvcgpu_output_format *fmt,
+                                               int display_w, int display_h);
+int xvc_host_picture_decoder_decode_sequence_out(xvc_host_picture_decoder *d, int n,
+                                                 const xvc_picture_syntax *const *ps,
+                                                 const xvc_cu_syntax *const *cus,
+                                                 const int16_t *const *levels,
+                                                 const int32_t *ref_index,
+                                                 xvcgpu_picture *const *recs,
+                                                 void *const *d_out);
 // a further picture lane on `ctx` (PictureDecoder::AddLane)
 int xvc_host_picture_decoder_add_lane(xvc_host_picture_decoder *d, xvcgpu_ctx *ctx);
 int xvc_host_picture_decoder_waves(const xvc_host_picture_decoder *d);
