@@ -1143,6 +1143,51 @@ xvcgpu_status xvcgpu_frame_pass_multi(xvcgpu_ctx *const *ctxs,
                                       const xvcgpu_frame_pass_args *const *args, int n,
                                       int phases);
 
+/* ---- the search of a fixed job list through a plan ----------------------- *
+ * A caller that searches the same list again and again - the CUs of a picture's pass, a
+ * real partition with 64x64 beside 8x4 beside 16x16 CUs - sorts it once:
+ * xvcgpu_me_plan_create reads the n descriptors on the device (one launch) and writes,
+ * per bin (XVCGPU_ME_PLAN_*, xvcgpu_types.h), the list of its job indices in list order;
+ * it synchronises once to read the counts back (a set-up call, like
+ * xvcgpu_quant_rdo_reserve) and owns device memory until xvcgpu_me_plan_destroy.
+ * max_block_size as in xvcgpu_me_search_sized.  The plan looks at w, h and the
+ * XVC_ME_USE_LIC bit of the descriptors only: positions, predictors, lambda may change
+ * between searches, the shapes may not (d_blocks must stay alive and in place).
+ * xvcgpu_me_search_planned: the results of xvcgpu_me_search_sized(flags, d_blocks, n,
+ * max_block_size), record for record, with one launch per non-empty bin over that bin's
+ * jobs only - the exact shapes 16x16, 16x8 and 8x8 through instances with the shape
+ * compiled in (both phases).  flags: XVCGPU_ME_FULLPEL / _SUBPEL / _LIC_JOBS (without
+ * the latter the LIC bins are answered unsupported, as there); the shape hints mean
+ * nothing here.  The straggler-first record of the full-pel search is kept by one launch,
+ * the one with the most jobs.  Never synchronises. */
+typedef struct xvcgpu_me_plan xvcgpu_me_plan;
+xvcgpu_status xvcgpu_me_plan_create(xvcgpu_ctx *ctx, const xvcgpu_me_block *d_blocks, int n,
+                                    int max_block_size, xvcgpu_me_plan **out);
+xvcgpu_status xvcgpu_me_plan_counts(const xvcgpu_me_plan *plan,
+                                    int32_t counts[XVCGPU_ME_PLAN_BINS]);
+void xvcgpu_me_plan_destroy(xvcgpu_ctx *ctx, xvcgpu_me_plan *plan);
+xvcgpu_status xvcgpu_me_search_planned(xvcgpu_ctx *ctx, const xvcgpu_picture *orig,
+                                       const xvcgpu_picture *ref, int flags,
+                                       const xvcgpu_me_plan *plan,
+                                       xvcgpu_me_result *d_results);
+
+/* xvcgpu_frame_pass with the search of a->d_me run through `plan` (made from a->d_me,
+ * a->n_cus and the class of a->max_block_size; anything else: XVCGPU_INVALID_ARGUMENT), for
+ * a pass over CUs of any mix of sizes.  The plan knows the shapes: where every CU has both
+ * sides in 8 ... 16 the forms of xvcgpu_frame_pass (their kernels hold a CU whole); where
+ * one is larger than 16x16 or has a side of 4, the any-size middle - QuantFast (no
+ * d_rdoq_params) = xvcgpu_mc_from_me into a->pred -> xvcgpu_residual_batch over a->d_tx /
+ * a->n_tx (d_levels / d_level_off optional) -> xvcgpu_cu_info_from_me through
+ * a->d_luma_tx_index; packed RDOQ (d_rdoq_params and pred) = xvcgpu_mc_from_me ->
+ * xvcgpu_fwd_transform_batch -> xvcgpu_quant_rdo_batch -> inverse transform -> CU records.
+ * Such a pass without those arguments is XVCGPU_INVALID_ARGUMENT, not a wrong picture.
+ * QuantFast with d_levels (and pred, d_tx, d_luma_tx_index) given takes the any-size middle
+ * for any shapes: only the residual pipeline stores levels.  The fused tail (scratch_rec)
+ * covers CUs without a side of 4: with one in the plan scratch_rec is ignored and the pass
+ * ends with the separate deblocking, padding and SSD launches. */
+xvcgpu_status xvcgpu_frame_pass_planned(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_args *a,
+                                        const xvcgpu_me_plan *plan, int phases);
+
 /* ---- tables (host side, no GPU needed) ---------------------------------- *
  * The 8-bit-fraction transform matrices the kernels use (transform_data.cc:
  * 109-796), for table-equality tests. out: size*size int16 row-major. */

@@ -117,6 +117,24 @@ typedef struct xvcgpu_me_result {
   uint32_t subpel_dist;         /* *out_dist of SubpelSearch (SATD)        */
 } xvcgpu_me_result;
 
+/* Bins of a search plan (xvcgpu_me_plan_create, xvcgpu.h): who takes a job.  The exact
+ * shapes that have a kernel instance of their own, the other jobs of the 16 class
+ * (max(w, h) <= 16), the 32 class, the 64 class split into the jobs the sub-pel team
+ * kernel takes (both sides >= 8) and the rest, the XVC_ME_USE_LIC jobs by class, and the
+ * jobs no instance takes (answered with the XVCGPU_ME_UNSUPPORTED record). */
+#define XVCGPU_ME_PLAN_16X16 0
+#define XVCGPU_ME_PLAN_16X8 1
+#define XVCGPU_ME_PLAN_8X8 2
+#define XVCGPU_ME_PLAN_OTHER16 3
+#define XVCGPU_ME_PLAN_C32 4
+#define XVCGPU_ME_PLAN_C64_TEAM 5
+#define XVCGPU_ME_PLAN_C64_WAVE 6
+#define XVCGPU_ME_PLAN_LIC16 7
+#define XVCGPU_ME_PLAN_LIC32 8
+#define XVCGPU_ME_PLAN_LIC64 9
+#define XVCGPU_ME_PLAN_UNSUPPORTED 10
+#define XVCGPU_ME_PLAN_BINS 11
+
 /* One bi-prediction refinement step for one CU (SearchBiIterative inner
  * loop, inter_search.cc:392-433): the searched list's block descriptor, the
  * MV already chosen for the OTHER list and the uni-pred MV of the searched

@@ -152,6 +152,11 @@ class FramePassArgs(C.Structure):
 
 FP_ENCODE, FP_DEBLOCK_V, FP_DEBLOCK_H, FP_PAD, FP_SSD = 1, 2, 4, 8, 16
 
+# bins of a search plan (XVCGPU_ME_PLAN_*, include/xvcgpu_types.h)
+ME_PLAN_BIN_NAMES = ("16x16", "16x8", "8x8", "other16", "c32", "c64_team", "c64_wave",
+                     "lic16", "lic32", "lic64", "unsupported")
+ME_PLAN_BINS = len(ME_PLAN_BIN_NAMES)
+
 # every symbol include/xvcgpu.h declares
 SYMBOLS = [
     "xvcgpu_create", "xvcgpu_destroy", "xvcgpu_last_error", "xvcgpu_version",
@@ -193,6 +198,8 @@ SYMBOLS = [
     "xvcgpu_comm_send_rows", "xvcgpu_comm_recv_rows", "xvcgpu_comm_all_reduce_sum_u64",
     "xvcgpu_comm_send_bytes", "xvcgpu_comm_recv_bytes", "xvcgpu_inv_transform_dist_batch",
     "xvcgpu_fwd_from_me", "xvcgpu_output_bytes", "xvcgpu_picture_convert_to",
+    "xvcgpu_me_plan_create", "xvcgpu_me_plan_counts", "xvcgpu_me_plan_destroy",
+    "xvcgpu_me_search_planned", "xvcgpu_frame_pass_planned",
 ]
 
 _vp = C.c_void_p
@@ -204,8 +211,31 @@ class XvcGpuError(RuntimeError):
     pass
 
 
-def load_library():
-    """Load libxvcgpu.so (fails loudly; never substitutes a CPU path)."""
+class MePlan:
+    """xvcgpu_me_plan: a job list sorted once into the bins that have a search kernel
+    instance of their own.  counts: int32 per bin (ME_PLAN_BIN_NAMES)."""
+
+    def __init__(self, ctx, d_blocks, n, max_block_size=64):
+        self.ctx, self.n, self.max_block_size = ctx, n, max_block_size
+        h = _vp()
+        ctx._check(ctx.lib.xvcgpu_me_plan_create(ctx.h, d_blocks, n, max_block_size,
+                                                 C.byref(h)))
+        self.h = h
+        c = (C.c_int32 * ME_PLAN_BINS)()
+        ctx._check(ctx.lib.xvcgpu_me_plan_counts(h, c))
+        self.counts = np.array(list(c), np.int32)
+
+    def destroy(self):
+        if self.h is not None:
+            self.ctx.lib.xvcgpu_me_plan_destroy(self.ctx.h, self.h)
+            self.h = None
+
+
+def load_library(allow_missing=()):
+    """Load libxvcgpu.so (fails loudly; never substitutes a CPU path).
+    allow_missing: entry points an OLDER build of the library named by XVCGPU_LIB /
+    LIB_PATH may lack (a measuring tool timing a parent commit's library); they are left
+    unbound, so calling one still fails.  Everything else missing is an error."""
     global _lib
     if _lib is not None:
         return _lib
@@ -369,7 +399,14 @@ def load_library():
                                               _vp, _vp, _vp, _vp, _vp],
         "xvcgpu_comm_recv_bytes": [_vp, _vp, C.c_size_t, C.c_int],
         "xvcgpu_picture_convert_to": [_vp, _vp, C.c_int, C.c_int, C.POINTER(OutputFormat), _vp],
+        "xvcgpu_me_plan_create": [_vp, _vp, C.c_int, C.c_int, C.POINTER(_vp)],
+        "xvcgpu_me_plan_counts": [_vp, C.POINTER(C.c_int32)],
+        "xvcgpu_me_search_planned": [_vp, _vp, _vp, C.c_int, _vp, _vp],
+        "xvcgpu_frame_pass_planned": [_vp, C.POINTER(FramePassArgs), _vp, C.c_int],
     }
+    if "xvcgpu_me_plan_destroy" not in allow_missing or hasattr(lib, "xvcgpu_me_plan_destroy"):
+        lib.xvcgpu_me_plan_destroy.restype = None
+        lib.xvcgpu_me_plan_destroy.argtypes = [_vp, _vp]
     lib.xvcgpu_event_destroy.restype = None
     lib.xvcgpu_event_destroy.argtypes = [_vp]
     lib.xvcgpu_comm_destroy.restype = None
@@ -377,6 +414,8 @@ def load_library():
     lib.xvcgpu_output_bytes.restype = C.c_size_t
     lib.xvcgpu_output_bytes.argtypes = [C.POINTER(OutputFormat)]
     for name, args in sigs.items():
+        if name in allow_missing and not hasattr(lib, name):
+            continue
         f = getattr(lib, name)
         f.restype = C.c_int
         f.argtypes = args
@@ -740,6 +779,15 @@ class Context:
         self._check(self.lib.xvcgpu_me_search_sized(self.h, orig.h_pic, ref.h_pic,
                                                     flags, d_blocks, n, d_results,
                                                     max_size))
+
+    def me_plan(self, d_blocks, n, max_block_size=64):
+        """The search plan of the n descriptors at device address d_blocks
+        (xvcgpu_me_plan_create; synchronises once): see MePlan."""
+        return MePlan(self, d_blocks, n, max_block_size)
+
+    def me_search_planned(self, orig, ref, flags, plan, d_results):
+        self._check(self.lib.xvcgpu_me_search_planned(self.h, orig.h_pic, ref.h_pic, flags,
+                                                      plan.h, d_results))
 
     def mc_batch_dev(self, ref, pred, d_blocks, n):
         self._check(self.lib.xvcgpu_mc_batch(self.h, ref.h_pic, pred.h_pic,

@@ -1358,6 +1358,25 @@ me2_search_job(Shared &s, const PicView &orig, const PicView &ref, const xvcgpu_
   if (lane == 0) results[bi] = res;
 }
 
+// Who takes a job (me_search_wave_take, and the search plan of k_me_plan.h): a job no
+// instance of the call takes (a size the search does not have, or larger than the caller's
+// max_block_size, or a LIC job nobody announced) is answered with the
+// XVCGPU_ME_UNSUPPORTED record instead of being left as it was.
+struct Me2JobClass {
+  bool valid, lic;
+  int mx;   // max(w, h): the class is the smallest of 16 / 32 / 64 that holds it
+};
+__device__ __forceinline__ Me2JobClass me2_job_class(const xvcgpu_me_block &b, int max_launched,
+                                                     bool lic_launched) {
+  Me2JobClass c;
+  c.mx = b.w > b.h ? b.w : b.h;
+  const bool pow2 = (b.w & (b.w - 1)) == 0 && (b.h & (b.h - 1)) == 0;
+  c.lic = (b.fullpel_mv & XVC_ME_USE_LIC) != 0;
+  c.valid = pow2 && b.w >= 4 && b.h >= 4 && b.w <= 64 && b.h <= 64 && c.mx <= max_launched &&
+            (!c.lic || lic_launched);
+  return c;
+}
+
 // Job bi of a search call by this wave: the descriptor read and checked, the instance
 // chosen.  SEL 0: every job of the class; 1: the exact-shape jobs only - 16x16 and 16x8, the
 // bottom CU row of a 1080-line picture - (me_search_sq16_kernel); 2: what that kernel
@@ -1373,14 +1392,9 @@ me_search_wave_take(Shared &s, const PicView &orig, const PicView &ref,
   ME2_TRACE_RT(9);
   const xvcgpu_me_block b = blocks[bi];
   {
-    const int mx = b.w > b.h ? b.w : b.h;
-    // a job no instance of this call takes (a size the search does not have, or
-    // larger than the caller's max_block_size) is answered with the
-    // XVCGPU_ME_UNSUPPORTED record instead of being left as it was
-    const bool pow2 = (b.w & (b.w - 1)) == 0 && (b.h & (b.h - 1)) == 0;
-    const bool lic = (b.fullpel_mv & XVC_ME_USE_LIC) != 0;
-    const bool valid = pow2 && b.w >= 4 && b.h >= 4 && b.w <= 64 && b.h <= 64 &&
-                       mx <= max_launched && (!lic || lic_launched);
+    const Me2JobClass jc = me2_job_class(b, max_launched, lic_launched);
+    const int mx = jc.mx;
+    const bool lic = jc.lic, valid = jc.valid;
     if (lic != LIC && valid) return;  // the other set of instances
     if (MS == 16 && !LIC && !valid) {
       if (ME2_LANE == 0) {
@@ -1548,10 +1562,11 @@ template <int MS, int NW>
 __device__ __forceinline__ void
 me_subpel_team_body(const PicView &orig, const PicView &ref, const xvcgpu_me_block *blocks, int n,
                     xvcgpu_me_result *results, const RefTable *refs = nullptr,
-                    const uint8_t *slots = nullptr) {
+                    const uint8_t *slots = nullptr, const int *order = nullptr) {
   __shared__ Me2Shared<MS> s;
-  const int bi = xcd_job_index(blockIdx.x, n);
+  int bi = xcd_job_index(blockIdx.x, n);
   if (bi < 0) return;
+  if (order) bi = order[bi];   // the slots of a plan's bin (k_me_plan.h)
   const xvcgpu_me_block b = blocks[bi];
   {
     const int mx = b.w > b.h ? b.w : b.h;

@@ -13,6 +13,7 @@
 #include "k_tail.h"
 #include "k_me.h"
 #include "k_me2.h"
+#include "k_me_plan.h"
 #include "k_metric.h"
 #include "k_misc.h"
 #include "k_pad.h"
@@ -904,6 +905,167 @@ xvcgpu_status xvcgpu_me_search(xvcgpu_ctx *ctx, const xvcgpu_picture *orig,
                                const xvcgpu_me_block *d_blocks, int n,
                                xvcgpu_me_result *d_results) {
   return xvcgpu_me_search_sized(ctx, orig, ref, flags, d_blocks, n, d_results, 64);
+}
+
+/* ---- the search through a plan (k_me_plan.h) ---- */
+struct xvcgpu_me_plan {
+  const xvcgpu_me_block *d_blocks;
+  int n, max_launched;
+  int *d_order;    // n job indices, bin after bin, list order inside a bin
+  int *d_offsets;  // XVCGPU_ME_PLAN_BINS + 2 (device copy of `first`)
+  // first slot of every bin, n, and the number of jobs with a side below 8
+  int first[XVCGPU_ME_PLAN_BINS + 2];
+  int n_small() const { return first[XVCGPU_ME_PLAN_BINS + 1]; }
+};
+
+xvcgpu_status xvcgpu_me_plan_create(xvcgpu_ctx *ctx, const xvcgpu_me_block *d_blocks, int n,
+                                    int max_block_size, xvcgpu_me_plan **out) {
+  if (!ctx || !out || n < 0 || (n && !d_blocks) || max_block_size < 4 || max_block_size > 64)
+    return XVCGPU_INVALID_ARGUMENT;
+  xvcgpu_me_plan *p = new (std::nothrow) xvcgpu_me_plan();
+  if (!p) return fail(ctx, XVCGPU_OUT_OF_MEMORY, "me_plan");
+  p->d_blocks = d_blocks;
+  p->n = n;
+  p->max_launched = max_block_size > 32 ? 64 : (max_block_size > 16 ? 32 : 16);
+  if (n > 0) {
+    hipError_t e = hipMalloc(&p->d_order, sizeof(int) * (size_t)n);
+    if (e == hipSuccess) e = hipMalloc(&p->d_offsets, sizeof(int) * (XVCGPU_ME_PLAN_BINS + 2));
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(me_plan_kernel_build, dim3(1), dim3(ME_PLAN_THREADS), 0, ctx->stream,
+                         d_blocks, n, p->max_launched, p->d_order, p->d_offsets);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(p->first, p->d_offsets, sizeof(p->first), hipMemcpyDeviceToHost,
+                         ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess || p->first[XVCGPU_ME_PLAN_BINS] != n) {
+      hipFree(p->d_order);
+      hipFree(p->d_offsets);
+      delete p;
+      return fail(ctx, e == hipErrorOutOfMemory ? XVCGPU_OUT_OF_MEMORY : XVCGPU_DEVICE_ERROR,
+                  "me_plan_create", e);
+    }
+  }
+  *out = p;
+  return XVCGPU_OK;
+}
+
+xvcgpu_status xvcgpu_me_plan_counts(const xvcgpu_me_plan *plan,
+                                    int32_t counts[XVCGPU_ME_PLAN_BINS]) {
+  if (!plan || !counts) return XVCGPU_INVALID_ARGUMENT;
+  for (int k = 0; k < XVCGPU_ME_PLAN_BINS; k++) counts[k] = plan->first[k + 1] - plan->first[k];
+  return XVCGPU_OK;
+}
+
+void xvcgpu_me_plan_destroy(xvcgpu_ctx *ctx, xvcgpu_me_plan *plan) {
+  (void)ctx;
+  if (!plan) return;
+  if (plan->d_order) hipFree(plan->d_order);
+  if (plan->d_offsets) hipFree(plan->d_offsets);
+  delete plan;
+}
+
+xvcgpu_status xvcgpu_me_search_planned(xvcgpu_ctx *ctx, const xvcgpu_picture *orig,
+                                       const xvcgpu_picture *ref, int flags,
+                                       const xvcgpu_me_plan *plan,
+                                       xvcgpu_me_result *d_results) {
+  if (!ctx || !orig || !ref || !plan || (plan->n && !d_results) ||
+      !(flags & (XVCGPU_ME_FULLPEL | XVCGPU_ME_SUBPEL)))
+    return XVCGPU_INVALID_ARGUMENT;
+  if (orig->w != ref->w || orig->h != ref->h || orig->bd != ref->bd)
+    return fail(ctx, XVCGPU_INVALID_ARGUMENT, "picture mismatch");
+  if (plan->n == 0) return XVCGPU_OK;
+  Me2Sched sched = {nullptr, nullptr, nullptr};
+  if (flags & XVCGPU_ME_FULLPEL) {  // as xvcgpu_me_search_sized
+    const int e = ctx->me_epoch = (ctx->me_epoch + 1) % 3;
+    sched.use = ctx->d_me_rot + e % 3;
+    sched.record = ctx->d_me_rot + (e + 1) % 3;
+    sched.clear = ctx->d_me_rot + (e + 2) % 3;
+  }
+  const int *first = plan->first;
+  const int ph = flags & 3;
+  // The straggler-first record (k_me2.h) counts positions inside one launch's job list: it
+  // is kept by ONE launch, the full-pel launch with the most jobs, from search to search
+  // of the same plan; the other launches run in list order.
+  const Me2Sched none = {nullptr, nullptr, nullptr};
+  // (the ranges below are those of the PLAN_LAUNCH calls further down: a new bin goes into
+  // both.  No full-pel job outside the LIC bins: sched_bin stays -1, nobody rotates and
+  // nobody resets the third record - stale values are clamped by me2_rotated_wg.)
+  int sched_bin = -1;
+  if (flags & XVCGPU_ME_FULLPEL) {
+    static const int both[][2] = {{XVCGPU_ME_PLAN_16X16, XVCGPU_ME_PLAN_16X8},
+                                  {XVCGPU_ME_PLAN_16X8, XVCGPU_ME_PLAN_8X8},
+                                  {XVCGPU_ME_PLAN_8X8, XVCGPU_ME_PLAN_OTHER16},
+                                  {XVCGPU_ME_PLAN_OTHER16, XVCGPU_ME_PLAN_C32},
+                                  {XVCGPU_ME_PLAN_C32, XVCGPU_ME_PLAN_C64_TEAM},
+                                  {XVCGPU_ME_PLAN_C64_TEAM, XVCGPU_ME_PLAN_LIC16}};
+    static const int single[][2] = {{XVCGPU_ME_PLAN_16X16, XVCGPU_ME_PLAN_C32},
+                                    {XVCGPU_ME_PLAN_C32, XVCGPU_ME_PLAN_C64_TEAM},
+                                    {XVCGPU_ME_PLAN_C64_TEAM, XVCGPU_ME_PLAN_LIC16}};
+    const int (*r)[2] = ph == 3 ? both : single;
+    int most = 0;
+    for (int k = 0; k < (ph == 3 ? 6 : 3); k++)
+      if (first[r[k][1]] - first[r[k][0]] > most) {
+        most = first[r[k][1]] - first[r[k][0]];
+        sched_bin = r[k][0];
+      }
+  }
+  // slots [first[A], first[B]) by instance <MS, PH, LIC, FW, FH>: nothing where empty
+#define PLAN_LAUNCH(A, B, MS, PH, LIC, FW, FH)                                                  \
+  do {                                                                                          \
+    const int cnt_ = first[B] - first[A];                                                       \
+    if (cnt_ > 0)                                                                               \
+      hipLaunchKernelGGL((me_plan_kernel<MS, PH, LIC, FW, FH>), me2_grid(cnt_, ME2_WAVES(MS)),  \
+                         dim3(64 * ME2_WAVES(MS)), 0, ctx->stream, orig->v, ref->v,             \
+                         plan->d_blocks, plan->d_order + first[A], cnt_, d_results,             \
+                         ctx->d_tz_pattern, (A) == sched_bin ? sched : none);                   \
+  } while (0)
+  // the larger classes and the LIC jobs: the two phases as two launches (xvcgpu_me_search_sized)
+#define PLAN_SPLIT(A, B, MS, LIC)                                           \
+  do {                                                                      \
+    if (flags & XVCGPU_ME_FULLPEL) PLAN_LAUNCH(A, B, MS, 1, LIC, 0, 0);     \
+    if (flags & XVCGPU_ME_SUBPEL) PLAN_LAUNCH(A, B, MS, 2, LIC, 0, 0);      \
+  } while (0)
+  if (ph == 3) {
+    PLAN_LAUNCH(XVCGPU_ME_PLAN_16X16, XVCGPU_ME_PLAN_16X8, 16, 3, false, 16, 16);
+    PLAN_LAUNCH(XVCGPU_ME_PLAN_16X8, XVCGPU_ME_PLAN_8X8, 16, 3, false, 16, 8);
+    PLAN_LAUNCH(XVCGPU_ME_PLAN_8X8, XVCGPU_ME_PLAN_OTHER16, 16, 3, false, 8, 8);
+    PLAN_LAUNCH(XVCGPU_ME_PLAN_OTHER16, XVCGPU_ME_PLAN_C32, 16, 3, false, 0, 0);
+  } else {   // a single phase: the whole 16 class through the any-size instance
+    PLAN_SPLIT(XVCGPU_ME_PLAN_16X16, XVCGPU_ME_PLAN_C32, 16, false);
+  }
+  PLAN_SPLIT(XVCGPU_ME_PLAN_C32, XVCGPU_ME_PLAN_C64_TEAM, 32, false);
+  if (flags & XVCGPU_ME_FULLPEL)
+    PLAN_LAUNCH(XVCGPU_ME_PLAN_C64_TEAM, XVCGPU_ME_PLAN_LIC16, 64, 1, false, 0, 0);
+  if (flags & XVCGPU_ME_SUBPEL) {
+    const int team = first[XVCGPU_ME_PLAN_C64_WAVE] - first[XVCGPU_ME_PLAN_C64_TEAM];
+    if (orig->bd > 10) {   // (me2_subpel_fast: no packed path above 10 bit)
+      PLAN_LAUNCH(XVCGPU_ME_PLAN_C64_TEAM, XVCGPU_ME_PLAN_LIC16, 64, 2, false, 0, 0);
+    } else {
+      PLAN_LAUNCH(XVCGPU_ME_PLAN_C64_WAVE, XVCGPU_ME_PLAN_LIC16, 64, 2, false, 0, 0);
+      if (team > 0)
+        hipLaunchKernelGGL((me_plan_team_kernel<64, 4>), dim3((team + 7) / 8 * 8), dim3(256), 0,
+                           ctx->stream, orig->v, ref->v, plan->d_blocks,
+                           plan->d_order + first[XVCGPU_ME_PLAN_C64_TEAM], team, d_results);
+    }
+  }
+  int bad_from = XVCGPU_ME_PLAN_UNSUPPORTED;
+  if (flags & XVCGPU_ME_LIC_JOBS) {
+    PLAN_SPLIT(XVCGPU_ME_PLAN_LIC16, XVCGPU_ME_PLAN_LIC32, 16, true);
+    PLAN_SPLIT(XVCGPU_ME_PLAN_LIC32, XVCGPU_ME_PLAN_LIC64, 32, true);
+    PLAN_SPLIT(XVCGPU_ME_PLAN_LIC64, XVCGPU_ME_PLAN_UNSUPPORTED, 64, true);
+  } else {
+    bad_from = XVCGPU_ME_PLAN_LIC16;   // not announced: nobody takes them
+  }
+#undef PLAN_SPLIT
+#undef PLAN_LAUNCH
+  const int bad = first[XVCGPU_ME_PLAN_BINS] - first[bad_from];
+  if (bad > 0)
+    hipLaunchKernelGGL(me_plan_unsupported_kernel, dim3((bad + 255) / 256), dim3(256), 0,
+                       ctx->stream, plan->d_order + first[bad_from], bad, d_results);
+  CHECK_LAUNCH(ctx, "me_search_planned");
+  return XVCGPU_OK;
 }
 
 xvcgpu_status xvcgpu_mc_batch(xvcgpu_ctx *ctx, const xvcgpu_picture *ref,
@@ -2260,11 +2422,14 @@ static bool whole_picture_pass(const xvcgpu_frame_pass_args *a, int phases) {
          !(a->rec->w & 7) && !(a->rec->h & 7);
 }
 
-xvcgpu_status xvcgpu_frame_pass(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_args *a,
-                                int phases) {
+// plan: null = xvcgpu_frame_pass; else xvcgpu_frame_pass_planned
+static xvcgpu_status frame_pass_impl(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_args *a,
+                                     int phases, const xvcgpu_me_plan *plan) {
   if (!ctx || !a || !a->rec) return XVCGPU_INVALID_ARGUMENT;
   xvcgpu_status st = XVCGPU_OK;
-  const bool fused_tail = whole_picture_pass(a, phases);
+  // (the fused tail covers CUs without a side of 4: a plan that holds one makes the pass
+  // end with the separate launches, whatever scratch_rec says)
+  const bool fused_tail = whole_picture_pass(a, phases) && !(plan && plan->n_small() > 0);
   xvcgpu_picture *const rec = fused_tail ? a->scratch_rec : a->rec;
   hipStream_t main_stream = nullptr;   // set while the pass runs on ctx->hi_stream
   struct Back {
@@ -2282,14 +2447,38 @@ xvcgpu_status xvcgpu_frame_pass(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_args *a
     // are (almost) all 16x16 (16x8 in the bottom row of a 1080-line picture) the search's
     // exact-shape kernel (a pass of smaller CUs must not take it: its jobs would all be left
     // to the few waves of the leftover kernel)
-    st = xvcgpu_me_search_sized(ctx, a->orig, a->ref,
-                                XVCGPU_ME_FULLPEL | XVCGPU_ME_SUBPEL |
-                                    (a->me_shape & (XVCGPU_ME_HINT_SQ16 | XVCGPU_ME_ONLY_SQ16)),
-                                a->d_me, a->n_cus, a->d_results, a->max_block_size);
+    st = plan ? xvcgpu_me_search_planned(ctx, a->orig, a->ref,
+                                         XVCGPU_ME_FULLPEL | XVCGPU_ME_SUBPEL, plan, a->d_results)
+              : xvcgpu_me_search_sized(
+                    ctx, a->orig, a->ref,
+                    XVCGPU_ME_FULLPEL | XVCGPU_ME_SUBPEL |
+                        (a->me_shape & (XVCGPU_ME_HINT_SQ16 | XVCGPU_ME_ONLY_SQ16)),
+                    a->d_me, a->n_cus, a->d_results, a->max_block_size);
     if (st != XVCGPU_OK) return st;
-    if (a->d_rdoq_params && a->pred) {
+    // the kernels that take a CU whole (recon_from_me, fwd_from_me) hold CUs of 8 ... 16
+    // samples a side; the plan knows whether every job is one
+    // ... and QuantFast levels (d_levels without RDOQ) are stored by the residual
+    // pipeline only: recon_from_me keeps none
+    const bool any_size =
+        plan && (a->max_block_size > 16 || plan->n_small() > 0 ||
+                 (!a->d_rdoq_params && a->d_levels && a->pred && a->d_tx && a->d_luma_tx_index));
+    if (any_size && !(a->d_rdoq_params && a->pred)) {
+      // CUs of any size (xvcgpu_frame_pass_planned): prediction picture, the residual
+      // pipeline over the transform blocks, the CU records
+      if (a->d_rdoq_params || !a->pred || !a->d_tx || !a->d_luma_tx_index)
+        return fail(ctx, XVCGPU_INVALID_ARGUMENT,
+                    "frame_pass_planned: CUs above 16x16 or with a side below 8 need pred, "
+                    "d_tx, d_luma_tx_index (QuantFast) or the packed RDOQ arguments");
+      st = xvcgpu_mc_from_me(ctx, a->ref, a->pred, a->d_me, a->d_results, a->n_cus);
+      if (st == XVCGPU_OK)
+        st = xvcgpu_residual_batch(ctx, a->orig, a->pred, rec, a->d_tx, a->n_tx, a->d_levels,
+                                   a->d_level_off, a->d_nnz);
+      if (st == XVCGPU_OK)
+        st = xvcgpu_cu_info_from_me(ctx, a->d_me, a->d_results, a->d_nnz, a->d_luma_tx_index,
+                                    a->n_cus, a->qp_y, a->qp_c, a->ref_poc, a->d_cus_own);
+    } else if (a->d_rdoq_params && a->pred) {
       bool in_place = false, classified = false;
-      if (a->max_block_size <= 16 && a->n_tx == 3 * a->n_cus) {
+      if (!any_size && a->max_block_size <= 16 && a->n_tx == 3 * a->n_cus) {
         // prediction + forward transform in one kernel (transform blocks in CU
         // order, Y U V each: block 3 * cu + comp)
         // (the prediction goes straight into the reconstruction's picture: the
@@ -2385,6 +2574,22 @@ xvcgpu_status xvcgpu_frame_pass(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_args *a
     st = xvcgpu_picture_ssd_rows(ctx, a->orig, a->rec, 0, a->shift_bitdepth, a->ssd_y_begin,
                                  a->ssd_y_end, a->d_ssd);
   return st;
+}
+
+xvcgpu_status xvcgpu_frame_pass(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_args *a,
+                                int phases) {
+  return frame_pass_impl(ctx, a, phases, nullptr);
+}
+
+xvcgpu_status xvcgpu_frame_pass_planned(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_args *a,
+                                        const xvcgpu_me_plan *plan, int phases) {
+  if (!ctx || !a || !plan || plan->n != a->n_cus || plan->d_blocks != a->d_me)
+    return XVCGPU_INVALID_ARGUMENT;
+  // (a plan of a smaller class would answer this pass's larger CUs as unsupported)
+  if (plan->max_launched != (a->max_block_size > 32 ? 64 : (a->max_block_size > 16 ? 32 : 16)))
+    return fail(ctx, XVCGPU_INVALID_ARGUMENT,
+                "frame_pass_planned: the plan was made for another max_block_size class");
+  return frame_pass_impl(ctx, a, phases, plan);
 }
 
 /* ---- several pictures per call: every kernel launched once for all of them ---- */

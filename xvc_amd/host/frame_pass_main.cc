@@ -6,9 +6,12 @@
 //   gcc -O2 -c xvc_amd/host/xvc_synth.c -o synth.o
 //   g++ -std=c++11 -O2 -Iinclude -Ixvc_amd/host xvc_amd/host/frame_pass_main.cc synth.o
 //       -Lxvc_amd -lxvcgpu -o frame_pass && ./frame_pass 1920 1080 10 32 8
+// A sixth argument names a partition file - text, one CU `x y w h` per line, coding
+// order - and the passes run on that partition instead of the 16x16 grid.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <memory>
 #include <vector>
 
 #include "xvc_frame_pass.h"
@@ -29,6 +32,17 @@ int main(int argc, char **argv) {
   const int w = argc > 1 ? std::atoi(argv[1]) : 352, h = argc > 2 ? std::atoi(argv[2]) : 288;
   const int bd = argc > 3 ? std::atoi(argv[3]) : 10, qp = argc > 4 ? std::atoi(argv[4]) : 32;
   const int frames = argc > 5 ? std::atoi(argv[5]) : 3;
+  std::vector<xvc_gpu::CuRect> partition;
+  if (argc > 6) {
+    std::FILE *f = std::fopen(argv[6], "r");
+    if (!f) {
+      std::printf("cannot read partition file %s\n", argv[6]);
+      return 2;
+    }
+    xvc_gpu::CuRect r;
+    while (std::fscanf(f, "%d %d %d %d", &r.x, &r.y, &r.w, &r.h) == 4) partition.push_back(r);
+    std::fclose(f);
+  }
   try {
     xvc_gpu::Context ctx(0);
     std::vector<uint16_t> y(static_cast<size_t>(w) * h), u(y.size() / 4), v(y.size() / 4);
@@ -40,7 +54,10 @@ int main(int argc, char **argv) {
     xo_synth_frame(w, h, bd, 1234, 1, 0, y.data(), w, u.data(), w / 2, v.data(), w / 2);
     ref->Upload(cplanes, strides);
     ref->PadBorder();
-    xvc_gpu::FramePass fp(ctx, w, h, bd, qp);
+    std::unique_ptr<xvc_gpu::FramePass> fpp(
+        argc > 6 ? new xvc_gpu::FramePass(ctx, w, h, bd, qp, partition)
+                 : new xvc_gpu::FramePass(ctx, w, h, bd, qp));
+    xvc_gpu::FramePass &fp = *fpp;
     double gpu_s = 0;
     for (int n = 1; n <= frames; n++) {
       xo_synth_frame(w, h, bd, 1234, 1, n, y.data(), w, u.data(), w / 2, v.data(), w / 2);

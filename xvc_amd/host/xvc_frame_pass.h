@@ -10,6 +10,8 @@
 #include <cmath>
 #include <cstdint>
 #include <memory>
+#include <sstream>
+#include <string>
 #include <vector>
 
 #include "xvc_gpu_ops.h"
@@ -32,11 +34,126 @@ inline uint32_t Lambda16(int qp) {
       std::floor(65536.0 * std::sqrt(0.57 * std::pow(2.0, (qp - 12) / 3.0))));
 }
 
+// One CU of a partition: a luma rectangle.
+struct CuRect {
+  int x, y, w, h;
+};
+
+// pipeline.check_partition: origins on the 4-sample grid, sides of 4, 8, 16, 32 or 64 (or
+// what the right / bottom picture edge leaves of such a side, a multiple of 4), every CU
+// inside the picture, no two overlapping, the picture covered.  Throws Error
+// (XVCGPU_INVALID_ARGUMENT) naming the first offending CU (for a hole: the first
+// uncovered 4x4 cell).
+inline void CheckPartition(int width, int height, const std::vector<CuRect> &parts) {
+  const int cw = (width + 3) / 4, ch = (height + 3) / 4;
+  std::vector<int32_t> seen(static_cast<size_t>(cw) * ch, -1);
+  for (size_t i = 0; i < parts.size(); i++) {
+    const CuRect &p = parts[i];
+    std::ostringstream name;
+    name << "partition: CU " << i << " (x=" << p.x << ", y=" << p.y << ", w=" << p.w
+         << ", h=" << p.h << ")";
+    if (p.w <= 0 || p.h <= 0 || p.x < 0 || p.y < 0 || p.x + p.w > width || p.y + p.h > height)
+      throw Error(XVCGPU_INVALID_ARGUMENT, name.str() + " lies outside the picture");
+    if (p.x % 4 || p.y % 4)
+      throw Error(XVCGPU_INVALID_ARGUMENT, name.str() + ": origin not on the 4-sample grid");
+    const int side[2] = {p.w, p.h}, at[2] = {p.x, p.y}, full[2] = {width, height};
+    for (int k = 0; k < 2; k++) {
+      const int s = side[k];
+      const bool std_side = s == 4 || s == 8 || s == 16 || s == 32 || s == 64;
+      const bool cut = at[k] + s == full[k] && s < 64 && s % 4 == 0;
+      if (!std_side && !cut)
+        throw Error(XVCGPU_INVALID_ARGUMENT,
+                    name.str() + ": side is not 4, 8, 16, 32 or 64 (nor cut by the picture edge)");
+    }
+    for (int yy = p.y / 4; yy < (p.y + p.h + 3) / 4; yy++)
+      for (int xx = p.x / 4; xx < (p.x + p.w + 3) / 4; xx++) {
+        int32_t &c = seen[static_cast<size_t>(yy) * cw + xx];
+        if (c >= 0) {
+          name << " overlaps CU " << c;
+          throw Error(XVCGPU_INVALID_ARGUMENT, name.str());
+        }
+        c = static_cast<int32_t>(i);
+      }
+  }
+  for (size_t k = 0; k < seen.size(); k++)
+    if (seen[k] < 0) {
+      std::ostringstream m;
+      m << "partition: no CU covers the samples at x=" << 4 * (k % cw) << ", y=" << 4 * (k / cw)
+        << " (a gap)";
+      throw Error(XVCGPU_INVALID_ARGUMENT, m.str());
+    }
+}
+
 class FramePass {
  public:
+  // The pass over a caller's CU partition (pipeline.FramePass(partition=...)): the luma
+  // CU tree of a real picture in coding order, CUs of any mix of sizes.  QuantFast; the
+  // search runs through a plan made here (xvcgpu_me_plan_create), the pass through
+  // xvcgpu_frame_pass_planned.  A CU the search has no instance for (a side the picture
+  // edge cut to 12, 24, ...) is refused.
+  FramePass(const Context &ctx, int width, int height, int bitdepth, int qp,
+            const std::vector<CuRect> &partition, int search_range = 96)
+      : ctx_(ctx), w_(width), h_(height), bd_(bitdepth), qp_(qp), qp_c_(ChromaQp(qp)),
+        plan_(nullptr) {
+    CheckPartition(width, height, partition);
+    map_stride_ = (width + 3) / 4;
+    std::vector<int32_t> map(static_cast<size_t>(map_stride_) * ((height + 3) / 4), -1);
+    std::vector<xvcgpu_me_block> me;
+    std::vector<xvcgpu_tx_block> tx;
+    std::vector<int32_t> luma;
+    int side = 16;
+    for (size_t i = 0; i < partition.size(); i++) {
+      const CuRect &p = partition[i];
+      xvcgpu_me_block b = xvcgpu_me_block();
+      b.x = static_cast<int16_t>(p.x);
+      b.y = static_cast<int16_t>(p.y);
+      b.w = static_cast<uint8_t>(p.w);
+      b.h = static_cast<uint8_t>(p.h);
+      b.depth_nonzero = 1;
+      b.lambda16 = Lambda16(qp);
+      b.search_range = search_range;
+      for (int yy = p.y / 4; yy < (p.y + p.h) / 4; yy++)
+        for (int xx = p.x / 4; xx < (p.x + p.w) / 4; xx++)
+          map[static_cast<size_t>(yy) * map_stride_ + xx] = static_cast<int32_t>(i);
+      me.push_back(b);
+      luma.push_back(static_cast<int32_t>(3 * i));
+      for (int c = 0; c < 3; c++) {   // Y U V per CU: block 3 * cu + comp
+        const int sh = c ? 1 : 0;
+        xvcgpu_tx_block t = xvcgpu_tx_block();
+        t.x = static_cast<int16_t>(p.x >> sh);
+        t.y = static_cast<int16_t>(p.y >> sh);
+        t.w = static_cast<uint8_t>(p.w >> sh);
+        t.h = static_cast<uint8_t>(p.h >> sh);
+        t.comp = static_cast<uint8_t>(c);
+        t.qp = static_cast<int8_t>(c ? qp_c_ : qp);
+        tx.push_back(t);
+      }
+      side = p.w > side ? p.w : side;
+      side = p.h > side ? p.h : side;
+    }
+    me_shape_ = 0;
+    max_cu_ = side <= 16 ? 16 : (side <= 32 ? 32 : 64);   // the search's block class
+    Allocate(me, map);
+    d_tx_.reset(new DeviceArray<xvcgpu_tx_block>(ctx, tx));
+    d_luma_.reset(new DeviceArray<int32_t>(ctx, luma));
+    pred_.reset(new Picture(ctx, width, height, bitdepth));
+    ctx_.Check(xvcgpu_me_plan_create(ctx_.get(), d_me_->data(), n_cus_, max_cu_, &plan_));
+    int32_t counts[XVCGPU_ME_PLAN_BINS] = {0};
+    const xvcgpu_status st = xvcgpu_me_plan_counts(plan_, counts);
+    if (st != XVCGPU_OK || counts[XVCGPU_ME_PLAN_UNSUPPORTED] > 0) {
+      xvcgpu_me_plan_destroy(ctx_.get(), plan_);
+      plan_ = nullptr;
+      ctx_.Check(st);
+      throw Error(XVCGPU_INVALID_ARGUMENT,
+                  "partition: the motion search has no instance for some CUs (sides must be "
+                  "4, 8, 16, 32 or 64)");
+    }
+  }
+
   FramePass(const Context &ctx, int width, int height, int bitdepth, int qp,
             int cu = 16, int search_range = 96)
-      : ctx_(ctx), w_(width), h_(height), bd_(bitdepth), qp_(qp), qp_c_(ChromaQp(qp)) {
+      : ctx_(ctx), w_(width), h_(height), bd_(bitdepth), qp_(qp), qp_c_(ChromaQp(qp)),
+        plan_(nullptr) {
     map_stride_ = (width + 3) / 4;
     std::vector<int32_t> map(static_cast<size_t>(map_stride_) * ((height + 3) / 4), -1);
     std::vector<xvcgpu_me_block> me;
@@ -57,20 +174,19 @@ class FramePass {
         sq16 += b.w == 16 && (b.h == 16 || b.h == 8);
         me.push_back(b);
       }
-    n_cus_ = static_cast<int>(me.size());
     // the search's shape word, as pipeline.FramePass sets it: the hint where at least 98 %
     // of the jobs have those shapes, and the word that no job has another where all do
     me_shape_ = me.empty() || 50 * sq16 < 49 * me.size() ? 0 : XVCGPU_ME_HINT_SQ16;
     if (!me.empty() && sq16 == me.size()) me_shape_ |= XVCGPU_ME_ONLY_SQ16;
-    d_me_.reset(new DeviceArray<xvcgpu_me_block>(ctx, me));
-    d_map_.reset(new DeviceArray<int32_t>(ctx, map));
-    d_res_.reset(new DeviceArray<xvcgpu_me_result>(ctx, me.size()));
-    d_nnz_.reset(new DeviceArray<int32_t>(ctx, 3 * me.size()));
-    d_cus_.reset(new DeviceArray<xvcgpu_cu_info>(ctx, me.size()));
-    d_ssd_.reset(new DeviceArray<uint64_t>(ctx, 2));
-    ctx_.Check(xvcgpu_memset(ctx_.get(), d_cus_->data(), 0, me.size() * sizeof(xvcgpu_cu_info)));
+    Allocate(me, map);
     max_cu_ = cu;
   }
+
+  ~FramePass() {
+    if (plan_) xvcgpu_me_plan_destroy(ctx_.get(), plan_);
+  }
+  FramePass(const FramePass &) = delete;
+  FramePass &operator=(const FramePass &) = delete;
 
   // Enqueues one picture (asynchronous): rec becomes the padded reconstruction.
   // The whole sequence - search, CompressAndEvalCbf, deblocking, PadBorder,
@@ -100,9 +216,17 @@ class FramePass {
     a.shift_bitdepth = bd_;
     a.d_ssd = d_ssd_->data();
     a.me_shape = me_shape_;
-    ctx_.Check(xvcgpu_frame_pass(ctx_.get(), &a,
-                                 XVC_FP_ENCODE | XVC_FP_DEBLOCK_V | XVC_FP_DEBLOCK_H |
-                                     XVC_FP_PAD | XVC_FP_SSD));
+    const int phases = XVC_FP_ENCODE | XVC_FP_DEBLOCK_V | XVC_FP_DEBLOCK_H | XVC_FP_PAD |
+                       XVC_FP_SSD;
+    if (plan_) {   // a partition: the any-size middle's arguments, the planned search
+      a.pred = pred_->get();
+      a.d_tx = d_tx_->data();
+      a.n_tx = 3 * n_cus_;
+      a.d_luma_tx_index = d_luma_->data();
+      ctx_.Check(xvcgpu_frame_pass_planned(ctx_.get(), &a, plan_, phases));
+      return;
+    }
+    ctx_.Check(xvcgpu_frame_pass(ctx_.get(), &a, phases));
   }
 
   // SampleMetric::ComputePsnr parts of the last Run (synchronises).
@@ -115,8 +239,23 @@ class FramePass {
   int num_cus() const { return n_cus_; }
 
  private:
+  void Allocate(const std::vector<xvcgpu_me_block> &me, const std::vector<int32_t> &map) {
+    n_cus_ = static_cast<int>(me.size());
+    d_me_.reset(new DeviceArray<xvcgpu_me_block>(ctx_, me));
+    d_map_.reset(new DeviceArray<int32_t>(ctx_, map));
+    d_res_.reset(new DeviceArray<xvcgpu_me_result>(ctx_, me.size()));
+    d_nnz_.reset(new DeviceArray<int32_t>(ctx_, 3 * me.size()));
+    d_cus_.reset(new DeviceArray<xvcgpu_cu_info>(ctx_, me.size()));
+    d_ssd_.reset(new DeviceArray<uint64_t>(ctx_, 2));
+    ctx_.Check(xvcgpu_memset(ctx_.get(), d_cus_->data(), 0, me.size() * sizeof(xvcgpu_cu_info)));
+  }
+
   const Context &ctx_;
   int w_, h_, bd_, qp_, qp_c_, n_cus_, map_stride_, max_cu_, me_shape_;
+  xvcgpu_me_plan *plan_;
+  std::unique_ptr<DeviceArray<xvcgpu_tx_block>> d_tx_;
+  std::unique_ptr<DeviceArray<int32_t>> d_luma_;
+  std::unique_ptr<Picture> pred_;
   std::unique_ptr<DeviceArray<xvcgpu_me_block>> d_me_;
   std::unique_ptr<DeviceArray<int32_t>> d_map_;
   std::unique_ptr<DeviceArray<xvcgpu_me_result>> d_res_;

@@ -111,6 +111,48 @@ def cu_partition(width, height, cu=16, xcd_tiles=False):
     return parts
 
 
+_CU_SIDES = (4, 8, 16, 32, 64)
+
+
+def check_partition(width, height, parts):
+    """A caller's CU partition - (x, y, w, h) luma rectangles in coding order, a sequence
+    or an (n, 4) array - as a list of int tuples, after checking that it is one the frame
+    pass can run: origins on the 4-sample grid, sides of 4, 8, 16, 32 or 64 (or what the
+    right / bottom picture edge leaves of such a side, a multiple of 4), every CU inside
+    the picture, no two overlapping, the picture covered.  ValueError names the first
+    offending CU (for a hole: the first uncovered 4x4 cell)."""
+    arr = np.asarray(parts)
+    if arr.size == 0:
+        arr = arr.reshape(0, 4)
+    if arr.ndim != 2 or arr.shape[1] != 4 or not np.issubdtype(arr.dtype, np.integer):
+        raise ValueError("partition: expected n integer rows (x, y, w, h), got an array of "
+                         "shape %r, dtype %s" % (arr.shape, arr.dtype))
+    cells_w, cells_h = (width + 3) // 4, (height + 3) // 4
+    seen = -np.ones((cells_h, cells_w), np.int64)
+    out = []
+    for i, (x, y, w, h) in enumerate(arr.tolist()):
+        name = "partition: CU %d (x=%d, y=%d, w=%d, h=%d)" % (i, x, y, w, h)
+        if w <= 0 or h <= 0 or x < 0 or y < 0 or x + w > width or y + h > height:
+            raise ValueError("%s lies outside the %dx%d picture" % (name, width, height))
+        if x % 4 or y % 4:
+            raise ValueError("%s: origin not on the 4-sample grid" % name)
+        for side, at, full, what in ((w, x, width, "width"), (h, y, height, "height")):
+            cut = at + side == full and side < 64 and side % 4 == 0
+            if side not in _CU_SIDES and not cut:
+                raise ValueError("%s: %s %d is not 4, 8, 16, 32 or 64 (nor cut by the picture "
+                                 "edge)" % (name, what, side))
+        cell = seen[y // 4:(y + h + 3) // 4, x // 4:(x + w + 3) // 4]
+        if (cell >= 0).any():
+            raise ValueError("%s overlaps CU %d" % (name, int(cell[cell >= 0][0])))
+        cell[...] = i
+        out.append((x, y, w, h))
+    if (seen < 0).any():
+        cy, cx = np.argwhere(seen < 0)[0]
+        raise ValueError("partition: no CU covers the samples at x=%d, y=%d (a gap)"
+                         % (4 * cx, 4 * cy))
+    return out
+
+
 class FrameDescriptors:
     """Host-side (numpy) descriptors of one picture's jobs; shared by the GPU
     frame pass and the CPU oracle frame pass in tests / bench.
@@ -118,16 +160,29 @@ class FrameDescriptors:
     With `row_range=(y0, y1)` only the CUs whose top row lies in [y0, y1) get
     motion-search / residual jobs (one CTU-row shard); the CU map and the CU
     metadata array stay global (indices into the whole picture's raster list)
-    because the in-loop filter looks across the shard boundary."""
+    because the in-loop filter looks across the shard boundary.
+
+    With `partition=` (check_partition: the luma CU tree of a real picture, CUs of any
+    mix of sizes in coding order) instead of the cu x cu grid the arrays are filled the
+    same way, CU by CU in the order given; whole pictures only (no row_range, no
+    xcd_tiles).  cu_size is then the search's block class - the smallest of 16 / 32 / 64
+    that holds the largest side - and cu_rows / cus_per_row are None."""
 
     def __init__(self, width, height, qp=32, cu=16, search_range=96,
-                 row_range=None, rdoq=False, bitdepth=10, xcd_tiles=False):
+                 row_range=None, rdoq=False, bitdepth=10, xcd_tiles=False, partition=None):
         self.w, self.h, self.qp = width, height, qp
         self.rdoq = rdoq
         # (region-major CU order only for a whole picture: a row shard's CUs have to be
         # a contiguous run of the raster list)
         assert not xcd_tiles or row_range is None or tuple(row_range) == (0, height)
-        parts_all = cu_partition(width, height, cu, xcd_tiles)
+        if partition is not None:
+            if xcd_tiles or not (row_range is None or tuple(row_range) == (0, height)):
+                raise ValueError("partition= describes a whole picture: no row_range, "
+                                 "no xcd_tiles")
+            parts_all = check_partition(width, height, partition)
+        else:
+            parts_all = cu_partition(width, height, cu, xcd_tiles)
+        self.partition = parts_all if partition is not None else None
         self.n_cus_total = len(parts_all)
         if row_range is None:
             row_range = (0, height)
@@ -173,6 +228,13 @@ class FrameDescriptors:
                 prm["lambda"][c::3] = lf
                 prm["rd_factor"][c::3] = rf
             self.rdoq_params = prm
+        if partition is not None:
+            side = max([max(p[2], p[3]) for p in parts_all], default=16)
+            self.cu_rows = self.cus_per_row = None
+            self.cu_size = 16 if side <= 16 else (32 if side <= 32 else 64)
+            self.min_side = min([min(p[2], p[3]) for p in parts_all], default=16)
+            self.max_side = side
+            return
         self.cu_rows = (height + cu - 1) // cu
         self.cus_per_row = (width + cu - 1) // cu
         self.cu_size = cu
@@ -183,8 +245,13 @@ def run_multi(passes, origs, refs, recs, ref_pocs=None):
     launched once for all of them (xvcgpu_frame_pass_multi).  passes: FramePass
     objects of one picture size, each on its own Context - the contexts lend their
     scratch, everything is enqueued on passes[0]'s stream (share_stream() puts the
-    other contexts on it)."""
+    other contexts on it).  Passes over a partition (FramePass(partition=...)) are not
+    batched: with one among them every pass is run by its own single call."""
     n = len(passes)
+    if any(p.plan is not None for p in passes):
+        for i, p in enumerate(passes):
+            p.run(origs[i], refs[i], recs[i], ref_pocs[i] if ref_pocs is not None else 0)
+        return
     lead = passes[0].ctx
     ctxs = (C.c_void_p * n)(*[p.ctx.h for p in passes])
     args = [p._call_args(origs[i], refs[i], recs[i], ref_pocs[i] if ref_pocs is not None else 0)
@@ -204,12 +271,20 @@ def share_stream(passes):
 
 class FramePass:
     """Device-resident state for running frame passes of one picture size
-    (or of one CTU-row shard of it)."""
+    (or of one CTU-row shard of it).
+
+    partition=: the pass over a caller's CU partition (FrameDescriptors) instead of the
+    cu x cu grid.  The form follows the shapes - all sides 8 ... 16: the fused forms of
+    the grid; else prediction picture + residual pipeline (`residual`, `residual_rdoq`,
+    or `fwd_transform` for packed RDOQ) -, the fused tail needs CUs without a side of 4,
+    and the search runs through a plan made here (xvcgpu_me_plan_create: the jobs sorted
+    once by kernel instance, one launch per non-empty bin)."""
 
     def __init__(self, ctx, width, height, bitdepth=10, qp=32, cu=16,
                  search_range=96, row_range=None, fused=True, keep_levels=False,
-                 rdoq=False, rdoq_packed=None, xcd_tiles=False):
+                 rdoq=False, rdoq_packed=None, xcd_tiles=False, partition=None):
         self.ctx = ctx
+        self.plan = None
         self.rdoq = rdoq
         # RDOQ keeps only a few lanes of a wave busy per block, so its own kernel
         # packs several blocks into a wave (xvcgpu_quant_rdo_batch) between the
@@ -224,7 +299,11 @@ class FramePass:
             and not self.rdoq_packed
         self.w, self.h, self.bd = width, height, bitdepth
         self.desc = d = FrameDescriptors(width, height, qp, cu, search_range,
-                                         row_range, rdoq, bitdepth, xcd_tiles)
+                                         row_range, rdoq, bitdepth, xcd_tiles, partition)
+        if partition is not None:
+            # the kernels that take a CU whole hold CUs of 8 ... 16 samples a side; `cu`
+            # below: what the grid's rules (cu <= 16, cu >= 8) look at
+            cu = 16 if (d.max_side <= 16 and d.min_side >= 8) else max(32, d.cu_size)
         # the form of the launches between the search and the tail (_launches), named
         # after the launch that sets it apart
         if cu <= 16 and self.fused:
@@ -266,6 +345,19 @@ class FramePass:
         # whole pictures of CUs >= 8x8 end with ONE launch (xvcgpu_deblock_pad_ssd:
         # unfiltered reconstruction in `scratch` -> deblocked, padded `rec` + SSD)
         # instead of deblock V, H, pad, SSD, SSD fold
+        if partition is not None:
+            cu = d.min_side
+            self.plan = ctx.me_plan(self.d_me.ptr, d.n_cus, d.cu_size)
+            bad = int(self.plan.counts[api.ME_PLAN_BIN_NAMES.index("unsupported")])
+            if bad:
+                # (a side the picture edge cut to 12, 24, ...: check_partition lets it
+                # through, the search would answer it with the unsupported record)
+                odd = [p for p in d.partition if (p[2] & (p[2] - 1)) or (p[3] & (p[3] - 1))]
+                self.scratch = self.d_levels = self.d_level_off = self.d_coeffs = None
+                self.destroy()
+                raise ValueError("partition: the motion search has no instance for %d CUs "
+                                 "(sides must be 4, 8, 16, 32 or 64), first (x, y, w, h) = %r"
+                                 % (bad, odd[0] if odd else None))
         self.fused_tail = cu >= 8 and width % 8 == 0 and height % 8 == 0 and \
             d.row_range == (0, d.h) and os.environ.get("XVC_TAIL_FUSED", "1") != "0"
         self.scratch = ctx.picture(width, height, bitdepth) if self.fused_tail else None
@@ -305,6 +397,12 @@ class FramePass:
                 a.d_level_off, a.d_luma_tx_index = self.d_level_off.ptr, self.d_luma_idx.ptr
                 a.d_coeffs, a.d_levels = self.d_coeffs.ptr, self.d_levels.ptr
                 a.n_coeffs = self.n_levels
+            elif self.plan is not None and self.form == "residual":
+                # the any-size QuantFast middle of xvcgpu_frame_pass_planned
+                a.pred, a.d_tx, a.n_tx = self.pred.h_pic, self.d_tx.ptr, len(d.tx)
+                a.d_luma_tx_index = self.d_luma_idx.ptr
+                if self.d_levels is not None:
+                    a.d_level_off, a.d_levels = self.d_level_off.ptr, self.d_levels.ptr
             a.tx_four_lane_only = int(self.tx_four_lane_only)
             a.me_shape = self.me_flags & (api.ME_HINT_SQ16 | api.ME_ONLY_SQ16)
             self._fp_args = a
@@ -330,6 +428,10 @@ class FramePass:
             a.ssd_y_begin, a.ssd_y_end = ssd_rows
         if d_ssd is not None:
             a.d_ssd = d_ssd
+        if self.plan is not None:
+            self.ctx._check(self.ctx.lib.xvcgpu_frame_pass_planned(self.ctx.h, C.byref(a),
+                                                                   self.plan.h, phases))
+            return
         self.ctx._check(self.ctx.lib.xvcgpu_frame_pass(self.ctx.h, C.byref(a), phases))
 
     def _launches(self, orig, ref, rec, ref_poc, fused_tail):
@@ -361,8 +463,12 @@ class FramePass:
                                                                 self.d_ssd.ptr))]
         if n == 0:
             return [], tail
-        enc = [("me_search", lambda: ctx.me_search_dev(orig, ref, self.me_flags, me, n, res,
-                                                       d.cu_size))]
+        if self.plan is not None:
+            enc = [("me_search", lambda: ctx.me_search_planned(
+                orig, ref, api.ME_FULLPEL | api.ME_SUBPEL, self.plan, res))]
+        else:
+            enc = [("me_search", lambda: ctx.me_search_dev(orig, ref, self.me_flags, me, n, res,
+                                                           d.cu_size))]
         if form == "recon_from_me":
             # MC + transform/quant/recon + CU metadata in one launch; the prediction
             # never leaves LDS
@@ -424,7 +530,15 @@ class FramePass:
     def run(self, orig, ref, rec, ref_poc=0, deblock=True, pad=True, ssd=True):
         """Enqueue one whole-picture frame pass (asynchronous)."""
         d = self.desc
-        if self.form in ("recon_from_me", "fwd_from_me") and d.row_range == (0, d.h):
+        one_call = self.form in ("recon_from_me", "fwd_from_me")
+        if self.plan is not None and d.n_cus > 0 and self.form in ("residual", "fwd_transform"):
+            # xvcgpu_frame_pass_planned has the any-size middle behind the one call too, and
+            # takes it where the plan holds a CU above 16x16 or with a side below 8, or where
+            # QuantFast levels are kept; any other pass of these forms (fused=False on CUs
+            # of 8 ... 16) would get the fused kernels there: launch by launch instead
+            one_call = d.cu_size > 16 or d.min_side < 8 or \
+                (self.form == "residual" and self.d_levels is not None)
+        if one_call and d.row_range == (0, d.h):
             # the whole sequence behind one C call (xvcgpu_frame_pass)
             self.run_phases(orig, ref, rec, api.FP_ENCODE |
                             (api.FP_DEBLOCK_V | api.FP_DEBLOCK_H if deblock else 0) |
@@ -451,6 +565,9 @@ class FramePass:
             if b is not None:
                 b.free()
         self.pred.destroy()
+        if self.plan is not None:
+            self.plan.destroy()
+            self.plan = None
         if self.scratch is not None:
             self.scratch.destroy()
             self.scratch = None
