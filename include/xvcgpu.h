@@ -203,7 +203,9 @@ xvcgpu_status xvcgpu_memcpy_d2h_async(xvcgpu_ctx *ctx, void *dst, const void *sr
  * samples, every plane surrounded by a replicated border.  The reference uses
  * 80 luma / 40 chroma samples; here the border is 128 / 64 and strides are
  * rounded to 64 samples so that every row starts 256-byte aligned in HBM.
- * All MV clipping rules (inter_prediction.cc:769-782) keep reads within 80. */
+ * All MV clipping rules (inter_prediction.cc:769-782) keep reads within 80.
+ * bitdepth: the internal bit depth, 8 to 12, the odd depths 9 and 11 included
+ * (anything else: XVCGPU_INVALID_ARGUMENT); every kernel family takes all five. */
 #define XVCGPU_BORDER_LUMA 128
 #define XVCGPU_BORDER_CHROMA 64
 

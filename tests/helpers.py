@@ -92,3 +92,71 @@ def make_pics(rng, bd, pw, ph, border, motion=(3, -2), noise=3):
     orig = np.clip(orig + rng.integers(-noise, noise + 1, size=(H, W)), 0,
                    (1 << bd) - 1).astype(np.uint16)
     return orig, ref
+
+
+# The tile shapes of the packed sub-pel path (k_subpel.h), rectangles first
+EXTREME_SHAPES = [(16, 8), (8, 16), (32, 16), (16, 32), (64, 32), (32, 64), (64, 16), (16, 64),
+                  (8, 8), (16, 16), (32, 32), (64, 64), (32, 8), (8, 32)]
+
+
+def walsh_pictures(rng, bd, pw, ph, border, trial):
+    """The inputs of test_me_search_extreme_residuals (test_gpu_parity.py), draw for draw:
+    the original and the reference are opposite Walsh patterns at full swing (trial 5: a
+    random sign pattern), so every residual is +-(2^bd - 1).  Returns the padded luma
+    planes (orig, ref)."""
+    smax = (1 << bd) - 1
+    yy, xx = np.mgrid[0:ph, 0:pw]
+    kx, ky = int(rng.integers(0, 16)), int(rng.integers(0, 16))
+    walsh = (np.bitwise_count((xx & kx).astype(np.uint8)).astype(np.int64) +
+             np.bitwise_count((yy & ky).astype(np.uint8))) & 1
+    if trial == 5:
+        walsh = rng.integers(0, 2, (ph, pw))
+    orig = np.ascontiguousarray(np.pad((walsh * smax).astype(np.uint16), border, mode="edge"))
+    ref = np.ascontiguousarray(np.pad(((1 - walsh) * smax).astype(np.uint16), border,
+                                      mode="edge"))
+    return orig, ref
+
+
+def extreme_blocks(rng, pw, ph, flags=0):
+    """One search job per shape of EXTREME_SHAPES on the 16-sample grid (the draws of
+    test_me_search_extreme_residuals); `flags` goes to fullpel_mv (XVC_ME_USE_LIC = 2)."""
+    blocks = np.zeros(len(EXTREME_SHAPES), ol.ME_DTYPE)
+    for b, (w, h) in zip(blocks, EXTREME_SHAPES):
+        b["w"], b["h"] = w, h
+        b["x"] = int(rng.integers(0, (pw - w) // 16 + 1)) * 16
+        b["y"] = int(rng.integers(0, (ph - h) // 16 + 1)) * 16
+        b["lambda16"], b["search_range"] = 498000, 96
+        b["fullpel_mv"] = flags
+    return blocks
+
+
+def me_struct(b):
+    s = ol.MeBlock()
+    for name in ol.ME_DTYPE.names:
+        setattr(s, name, int(b[name]))
+    return s
+
+
+def bi_struct(j):
+    s = ol.BiBlock()
+    for name in ol.ME_DTYPE.names:
+        setattr(s.blk, name, int(j["blk"][name]))
+    for name in ("other_mv_x", "other_mv_y", "boot_mv_x", "boot_mv_y"):
+        setattr(s, name, int(j[name]))
+    return s
+
+
+def extreme_bi_jobs(rng, blocks):
+    """One bi-prediction refinement job per block: the other list's vector full-pel for
+    every second job (then the 2 * orig - pred target sits at its ends, -(2^bd - 1) and
+    2 * (2^bd - 1), when that picture is the opposite pattern), sub-pel for the rest."""
+    jobs = np.zeros(len(blocks), ol.BI_DTYPE)
+    jobs["blk"] = blocks
+    jobs["blk"]["search_range"] = 4
+    for k, j in enumerate(jobs):
+        if k % 2:
+            j["other_mv_x"], j["other_mv_y"] = int(rng.integers(-40, 40)), int(rng.integers(-40, 40))
+        else:
+            j["other_mv_x"], j["other_mv_y"] = 16 * int(rng.integers(-2, 3)), 16 * int(rng.integers(-2, 3))
+        j["boot_mv_x"], j["boot_mv_y"] = int(rng.integers(-48, 48)), int(rng.integers(-48, 48))
+    return jobs

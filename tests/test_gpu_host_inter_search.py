@@ -57,7 +57,7 @@ def test_bit_prices_and_final_mvp_vs_reference():
 
 
 @pytest.mark.skipif(not ol.have_ref(), reason="oracle/_ref not built")
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12])
 def test_eval_start_mvp_and_ref_loop_vs_reference(gpu, bd):
     api, ctx = gpu
     L, xr, xo = host_lib(), ol.Lib("xr"), ol.Lib("xo")
@@ -133,7 +133,7 @@ def test_eval_start_mvp_and_ref_loop_vs_reference(gpu, bd):
 
 
 @pytest.mark.skipif(not ol.have_ref(), reason="oracle/_ref not built")
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12])
 def test_search_merge_candidates_vs_reference(gpu, bd):
     """SearchMergeCandidates (inter_search.cc:165-197): per-candidate SATD on the
     device (uni and bi-directional candidates), the double-precision fold, the

@@ -105,7 +105,7 @@ def test_intra_pred_all_modes_all_sizes(gpu, xo):
     P.destroy()
 
 
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12])
 def test_intra_satd_batch(gpu, xo, bd):
     api, ctx = gpu
     rng = np.random.default_rng(1040 + bd)

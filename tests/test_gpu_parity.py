@@ -176,12 +176,16 @@ def to_me_struct(b):
     return s
 
 
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12])
 def test_me_search(gpu, xo, bd):
+    _me_search(gpu, xo, bd, [(3, -2), (0, 0), (-17, 9), (40, 26)])
+
+
+def _me_search(gpu, xo, bd, motions):
     api, ctx = gpu
     rng = np.random.default_rng(3000 + bd)
     pw, ph = 320, 192
-    for motion in [(3, -2), (0, 0), (-17, 9), (40, 26)]:
+    for motion in motions:
         orig, ref = make_pics(rng, bd, pw, ph, BL, motion)
         O, R = ctx.picture(pw, ph, bd), ctx.picture(pw, ph, bd)
         O.upload([orig, None, None], BL)
@@ -242,7 +246,7 @@ def test_me_search(gpu, xo, bd):
         R.destroy()
 
 
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12])
 def test_me_search_extreme_residuals(gpu, xo, bd):
     """Sub-pel SATD at the edge of the packed 16-bit budget (k_subpel.h): the
     original and the reference are opposite Walsh patterns at full swing, so
@@ -345,7 +349,7 @@ def test_unsupported_jobs_are_reported(gpu):
     R.destroy()
 
 
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12])
 def test_bipred_search(gpu, xo, bd):
     """M2/T2/T7: one SearchBiIterative step per job vs the oracle."""
     api, ctx = gpu
@@ -559,7 +563,7 @@ def test_residual_pipeline(gpu, xo, bd):
     _residual_pipeline(gpu, xo, bd, False)
 
 
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12])
 def test_residual_pipeline_restricted_mode(gpu, xo, bd):
     """The 6-bit DCT-2 of restricted mode (XVC_TX_DCT2_LOW per direction; the
     oracle's form is pinned to the reference with the restriction flag set in
@@ -670,7 +674,7 @@ def test_transform_skip(gpu, xo, bd):
         pic.destroy()
 
 
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12])
 def test_residual_batch_grid(gpu, xo, bd):
     """A whole picture tiled by non-overlapping blocks in one launch."""
     api, ctx = gpu
@@ -710,7 +714,7 @@ def test_residual_batch_grid(gpu, xo, bd):
         pic.destroy()
 
 
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12])
 @pytest.mark.parametrize("bipred", [0, 1])
 @pytest.mark.parametrize("sub", [4, 8])
 def test_deblock(gpu, xo, bd, bipred, sub):
@@ -790,7 +794,7 @@ def test_deblock_chains(gpu, xo):
         Rc.destroy()
 
 
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12])
 @pytest.mark.parametrize("bipred", [0, 1])
 def test_deblock_pad_ssd(gpu, xo, bd, bipred):
     """The fused tail (k_tail.h): one launch = DeblockPicture (4-sample subblocks,
@@ -803,6 +807,8 @@ def test_deblock_pad_ssd(gpu, xo, bd, bipred):
     sizes = [(64, 64), (136, 72), (320, 200), (352, 288), (8, 8), (72, 200), (640, 384)]
     if bd == 10 and bipred:
         sizes.append((1920, 1080))      # BASELINE config 1's picture: 510 tiles, 7 remainder rows
+    if bd > 10:
+        sizes.remove((640, 384))        # the depths above 10 stay at 352x288 and below
     for k, (pw, ph) in enumerate(sizes):
         trial = k % 3
         parts = random_partition(rng, pw, ph, 8)
@@ -870,7 +876,7 @@ def test_pad_border(gpu, xo):
         P.destroy()
 
 
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12])
 def test_picture_ssd(gpu, xo, bd):
     api, ctx = gpu
     rng = np.random.default_rng(7000)
@@ -1138,7 +1144,12 @@ def test_frame_pass_multi(gpu, rdoq, n):
                                         (12, 32, (352, 288)), (12, 17, (136, 72))])
 def test_frame_pass_bitdepths(gpu, xo, bd, qp, size):
     """The frame pass at internal bit depths 8 and 12 (the packed sub-pel
-    sweep takes bd <= 10; 12 runs the row-major path) and other QPs."""
+    sweep takes bd <= 10; 12 runs the row-major path) and other QPs; the odd
+    depths 9 and 11 run it in test_gpu_bitdepth_paths.py."""
+    _frame_pass_bitdepth(gpu, xo, bd, qp, size)
+
+
+def _frame_pass_bitdepth(gpu, xo, bd, qp, size):
     api, ctx = gpu
     from xvc_amd import pipeline, synth
     import oracle_frame
@@ -1207,7 +1218,7 @@ def test_decode_pass_equals_encoder_reconstruction(gpu, xo, size):
         p.destroy()
 
 
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12])
 def test_bipicture_reconstruction(gpu, xo, bd):
     """N1 for a B picture: CUs predicted from list 0, list 1 or both (random
     partition into 8..64 CUs), residual coded with the device quantiser, then

@@ -134,12 +134,16 @@ def _search_lists(w, h):
     }
 
 
-@pytest.mark.parametrize("phases", ["both", "fullpel", "subpel"])
-def test_planned_search_equals_sized(gpu, phases):
+# (the 10-bit cases keep the ids they had before there was a depth to choose)
+@pytest.mark.parametrize("phases,bd", [
+    pytest.param(ph, bd, id=ph if bd == 10 else "%s-bd%d" % (ph, bd))
+    for bd in (10, 12) for ph in ("both", "fullpel", "subpel")])
+def test_planned_search_equals_sized(gpu, phases, bd):
+    """bd 12: the 64 class's sub-pel leaves the four-wave team kernel for the wave
+    instance (the packed SATD sweep holds bd <= 10)."""
     api, ctx = gpu
     from xvc_amd import synth
     w, h = picture_size("c1x", 3)
-    bd = 10
     clip = synth.SyntheticClip(w, h, bd)
     O, R = ctx.picture(w, h, bd), ctx.picture(w, h, bd)
     O.upload(pad_planes(clip.frame(1)), BL)
@@ -233,7 +237,7 @@ def _run_partition_pass(api, ctx, xo, name, pic, bd, qp, rdoq, check_steps=False
 
 
 @pytest.mark.parametrize("rdoq", [False, True])
-@pytest.mark.parametrize("bd,qp", [(10, 32), (8, 27)])
+@pytest.mark.parametrize("bd,qp", [(10, 32), (8, 27), (12, 32)])
 @pytest.mark.parametrize("name,pic", [("tiny", 1), ("tiny", 3), ("c0", 1), ("c0q22", 1)])
 def test_partition_pass_matches_oracle(gpu, xo, name, pic, bd, qp, rdoq):
     api, ctx = gpu
@@ -302,8 +306,10 @@ def small_partition(w, h):
     return parts
 
 
-@pytest.mark.parametrize("rdoq", [False, True])
-def test_one_call_on_small_cus(gpu, xo, rdoq):
+@pytest.mark.parametrize("rdoq,bd", [
+    pytest.param(r, bd, id=str(r) if bd == 10 else "%s-bd%d" % (r, bd))
+    for bd in (10, 12) for r in (False, True)])
+def test_one_call_on_small_cus(gpu, xo, rdoq, bd):
     """xvcgpu_frame_pass_planned itself (run_phases: no Python choice in between) on a
     partition whose largest side is 16 and that holds 4-wide CUs: the plan knows, the call
     takes the any-size middle; against the oracle.  And a plan of another class is refused."""
@@ -311,7 +317,7 @@ def test_one_call_on_small_cus(gpu, xo, rdoq):
     import oracle_frame
     from xvc_amd import pipeline, synth
     api, ctx = gpu
-    w, h, bd, qp = 208, 112, 10, 30
+    w, h, qp = 208, 112, 30
     parts = small_partition(w, h)
     clip = synth.SyntheticClip(w, h, bd)
     ref_host, orig_host = pad_planes(clip.frame(0)), pad_planes(clip.frame(1))

@@ -69,26 +69,35 @@ def test_gpu_rdoq_golden(gpu, prove_zero):
     assert done > 400
 
 
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12])
 def test_gpu_residual_rdoq_pipeline(gpu, bd):
     """xvcgpu_residual_rdoq_batch == the oracle's TransformAndReconstruct with
     QuantRdo: levels, counts and reconstruction; all block shapes 2..64 (both
     kernels: one wave per block up to 16x16, the workgroup path above / 2-wide),
     luma and chroma, a mix of RDOQ and QuantFast blocks in one batch."""
     api, ctx = gpu
-    xo = ol.Lib("xo")
-    rng = np.random.default_rng(930 + bd)
-    pw, ph = 256, 192
+    residual_rdoq_pipeline(api, ctx, bd, np.random.default_rng(930 + bd))
+
+
+def rdoq_pipeline_inputs(api, rng, bd, pw, ph, full_swing=False, qps=None):
+    """orig, pred (padded planes), the transform blocks tiling them, their RDOQ
+    parameters and the context snapshots.  full_swing: opposite random sign patterns at
+    0 / 2^bd - 1, every residual +-(2^bd - 1); qps: the QPs to draw from (20..39)."""
     pad = lambda planes: [np.ascontiguousarray(np.pad(p, G_BL >> (1 if c else 0), mode="edge"))
                           for c, p in enumerate(planes)]
-    base = [rnd_samples(rng, bd, ph >> (1 if c else 0), pw >> (1 if c else 0), 1) for c in range(3)]
-    noise = [rng.integers(-24, 25, p.shape) << (bd - 8) for p in base]
-    orig = pad([np.clip(p.astype(np.int64) + n, 0, (1 << bd) - 1).astype(np.uint16)
-                for p, n in zip(base, noise)])
-    pred = pad(base)
-    O, P, R = (ctx.picture(pw, ph, bd) for _ in range(3))
-    O.upload(orig, G_BL)
-    P.upload(pred, G_BL)
+    if full_swing:
+        sign = [rng.integers(0, 2, (ph >> (1 if c else 0), pw >> (1 if c else 0)))
+                for c in range(3)]
+        smax = (1 << bd) - 1
+        orig = pad([(s_ * smax).astype(np.uint16) for s_ in sign])
+        pred = pad([((1 - s_) * smax).astype(np.uint16) for s_ in sign])
+    else:
+        base = [rnd_samples(rng, bd, ph >> (1 if c else 0), pw >> (1 if c else 0), 1)
+                for c in range(3)]
+        noise = [rng.integers(-24, 25, p.shape) << (bd - 8) for p in base]
+        orig = pad([np.clip(p.astype(np.int64) + n, 0, (1 << bd) - 1).astype(np.uint16)
+                    for p, n in zip(base, noise)])
+        pred = pad(base)
     # a tiling of the luma plane into blocks of mixed shapes, and of the chroma planes
     sizes = [2, 4, 8, 16, 32, 64]
     blocks, params = [], []
@@ -107,7 +116,7 @@ def test_gpu_residual_rdoq_pipeline(gpu, bd):
                 sc = 1 if comp else 0
                 scan = int(rng.integers(0, 3)) if intra and (w << sc) < 16 and (h << sc) < 16 else 0
                 rdoq = rng.integers(0, 5) != 0
-                qp = int(rng.integers(20, 40))
+                qp = int(rng.integers(20, 40)) if qps is None else int(rng.choice(qps))
                 flags = (api.TXF_RDOQ if rdoq else 0) | (scan << api.TXF_SCAN_SHIFT) | \
                     (api.TXF_NO_SIGN_HIDING if rng.integers(0, 6) == 0 else 0)
                 txh = txv = 0
@@ -127,15 +136,19 @@ def test_gpu_residual_rdoq_pipeline(gpu, bd):
             y += h
     blocks = np.array(blocks, api.TX_DTYPE)
     params = np.array(params, api.RDOQ_PARAMS_DTYPE)
-    levels, off, nnz = ctx.residual_rdoq_batch(O, P, R, blocks, ctxs, params)
-    got = R.download(0)
-    # oracle
+    return orig, pred, blocks, params, ctxs
+
+
+def rdoq_pipeline_oracle(bd, pw, ph, orig, pred, blocks, params, ctxs):
+    """The oracle's TransformAndReconstruct per block: reconstruction planes and per block
+    (nnz, levels)."""
+    xo = ol.Lib("xo")
     f = xo.dll.xo_residual_pipeline_rdoq
     f.restype = C.c_int
     vp = C.c_void_p
-    exp = [np.zeros_like(p) for p in got]
+    exp = [np.zeros((ph >> (1 if c else 0), pw >> (1 if c else 0)), np.uint16) for c in range(3)]
     coeff = np.zeros(64 * 64, np.int16)
-    n_coded = 0
+    out = []
     for i, b in enumerate(blocks):
         c = int(b["comp"])
         bb = G_BL >> (1 if c else 0)
@@ -148,9 +161,24 @@ def test_gpu_residual_rdoq_pipeline(gpu, bd):
                   vp(exp[c].ctypes.data), C.c_ssize_t(exp[c].strides[0] // 2),
                   vp(coeff.ctypes.data))
         w, h = int(b["w"]), int(b["h"])
+        out.append((e_nnz, coeff[:w * h].copy()))
+    return exp, out
+
+
+def residual_rdoq_pipeline(api, ctx, bd, rng, pw=256, ph=192, full_swing=False, qps=None):
+    orig, pred, blocks, params, ctxs = rdoq_pipeline_inputs(api, rng, bd, pw, ph, full_swing, qps)
+    O, P, R = (ctx.picture(pw, ph, bd) for _ in range(3))
+    O.upload(orig, G_BL)
+    P.upload(pred, G_BL)
+    levels, off, nnz = ctx.residual_rdoq_batch(O, P, R, blocks, ctxs, params)
+    got = R.download(0)
+    exp, records = rdoq_pipeline_oracle(bd, pw, ph, orig, pred, blocks, params, ctxs)
+    n_coded = 0
+    for i, (b, (e_nnz, coeff)) in enumerate(zip(blocks, records)):
+        w, h = int(b["w"]), int(b["h"])
         assert nnz[i] == e_nnz, (i, tuple(b), int(nnz[i]), e_nnz)
         if e_nnz:       # cbf = 0: level buffer unspecified in the reference, zeros here
-            assert np.array_equal(levels[off[i]:off[i] + w * h], coeff[:w * h]), (i, tuple(b))
+            assert np.array_equal(levels[off[i]:off[i] + w * h], coeff), (i, tuple(b))
         else:
             assert not levels[off[i]:off[i] + w * h].any(), (i, tuple(b))
         n_coded += e_nnz > 0

@@ -17,16 +17,15 @@ CLASS_SIZES = {16: [(16, 16), (8, 8), (16, 8), (8, 16), (16, 4), (4, 8)],
                64: [(64, 64), (64, 32), (32, 64), (64, 16)]}
 
 
-@pytest.fixture(scope="module")
-def gpu():
+def _pictures(bd):
     from xvc_amd import api
     ctx = api.Context(0)
-    clip = synth.SyntheticClip(W, H, BD)
+    clip = synth.SyntheticClip(W, H, bd)
     pad = lambda planes: [np.ascontiguousarray(np.pad(p, BL >> (c > 0), mode="edge"))
                           for c, p in enumerate(planes)]
     pics = []
     for k in range(4):
-        p = ctx.picture(W, H, BD)
+        p = ctx.picture(W, H, bd)
         p.host_luma = pad(clip.frame(k))[0]       # (for the oracle)
         p.upload(pad(clip.frame(k)), BL)
         pics.append(p)
@@ -34,6 +33,18 @@ def gpu():
     for p in pics:
         p.destroy()
     ctx.close()
+
+
+@pytest.fixture(scope="module")
+def gpu():
+    yield from _pictures(BD)
+
+
+@pytest.fixture(scope="module")
+def gpu12():
+    """The same clip at 12 bit: above 10 the sub-pel search of every form leaves the
+    packed SATD sweep (and, in the 64 class, the team kernel)."""
+    yield from _pictures(12)
 
 
 def _me_blocks(api, rng, cls, n):
@@ -60,6 +71,15 @@ def _slots(rng, n, width=1):
 
 @pytest.mark.parametrize("cls", [16, 32, 64])
 def test_me_search_refs(gpu, cls):
+    _me_search_refs(gpu, cls, BD)
+
+
+@pytest.mark.parametrize("cls", [16, 32, 64])
+def test_me_search_refs_12bit(gpu12, cls):
+    _me_search_refs(gpu12, cls, 12)
+
+
+def _me_search_refs(gpu, cls, bd):
     api, ctx, orig, refs = gpu
     rng = np.random.default_rng(100 + cls)
     n = 40
@@ -81,17 +101,26 @@ def test_me_search_refs(gpu, cls):
     for i in np.flatnonzero(slots != 255):
         st = to_me_struct(blocks[i])
         rp = refs[int(slots[i])].host_luma
-        (fx, fy), cost = xo.tz_search(BD, st, W, H, orig.host_luma, rp, BL)
+        (fx, fy), cost = xo.tz_search(bd, st, W, H, orig.host_luma, rp, BL)
         assert (int(got[i]["fullpel_x"]), int(got[i]["fullpel_y"]), int(got[i]["fullpel_cost"])) == (fx, fy, cost), \
             (cls, i, tuple(blocks[i]), tuple(got[i]))
         if not (blocks[i]["fullpel_mv"] & 1):
-            (sx, sy), sd = xo.subpel_search(BD, st, W, H, orig.host_luma, rp, BL, (fx, fy))
+            (sx, sy), sd = xo.subpel_search(bd, st, W, H, orig.host_luma, rp, BL, (fx, fy))
             assert (int(got[i]["mv_x"]), int(got[i]["mv_y"]), int(got[i]["subpel_dist"])) == (sx, sy, sd), \
                 (cls, i, tuple(blocks[i]), tuple(got[i]))
 
 
 @pytest.mark.parametrize("cls", [16, 32, 64])
 def test_bipred_search_refs(gpu, cls):
+    _bipred_search_refs(gpu, cls)
+
+
+@pytest.mark.parametrize("cls", [16, 32, 64])
+def test_bipred_search_refs_12bit(gpu12, cls):
+    _bipred_search_refs(gpu12, cls)
+
+
+def _bipred_search_refs(gpu, cls):
     api, ctx, orig, refs = gpu
     rng = np.random.default_rng(200 + cls)
     n = 36
@@ -116,6 +145,14 @@ def test_bipred_search_refs(gpu, cls):
 
 
 def test_mc_metric_batch_refs(gpu):
+    _mc_metric_batch_refs(gpu)
+
+
+def test_mc_metric_batch_refs_12bit(gpu12):
+    _mc_metric_batch_refs(gpu12)
+
+
+def _mc_metric_batch_refs(gpu):
     api, ctx, orig, refs = gpu
     rng = np.random.default_rng(300)
     n = 64
@@ -139,6 +176,15 @@ def test_mc_metric_batch_refs(gpu):
 
 @pytest.mark.parametrize("cu_height", [16, 32, 64])
 def test_affine_me_batch_refs(gpu, cu_height):
+    _affine_me_batch_refs(gpu, cu_height)
+
+
+@pytest.mark.parametrize("cu_height", [16, 32, 64])
+def test_affine_me_batch_refs_12bit(gpu12, cu_height):
+    _affine_me_batch_refs(gpu12, cu_height)
+
+
+def _affine_me_batch_refs(gpu, cu_height):
     api, ctx, orig, refs = gpu
     rng = np.random.default_rng(400 + cu_height)
     n = 18

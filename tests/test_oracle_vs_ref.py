@@ -51,7 +51,7 @@ def test_metrics_sample_sample(libs, bd, simd):
     assert n > 500
 
 
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12, 9, 11])
 def test_metrics_residual_sample(libs, bd):
     xo, xr = libs
     rng = np.random.default_rng(7 + bd)
@@ -70,7 +70,7 @@ def test_metrics_residual_sample(libs, bd):
             assert xr.ssd_rr(bd, a2, b2) == xo.ssd_rr(bd, a2, b2)
 
 
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12, 9, 11])
 def test_picture_ssd(libs, bd):
     xo, xr = libs
     rng = np.random.default_rng(3)
@@ -129,7 +129,7 @@ def test_clip_and_window(libs):
         assert xr._mvd_bits(mx, my, x * 3, -y, 0) == xo._mvd_bits(mx, my, x * 3, -y, 0)
 
 
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12, 9, 11])
 def test_mc_block(libs, bd):
     xo, xr = libs
     rng = np.random.default_rng(9)
@@ -256,7 +256,7 @@ def test_transforms(libs, bd):
         assert np.array_equal(xr.inv_transform_skip(bd, r), xo.inv_transform_skip(bd, r))
 
 
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12, 9, 11])
 def test_quant_dequant(libs, bd):
     xo, xr = libs
     rng = np.random.default_rng(31)
@@ -272,7 +272,7 @@ def test_quant_dequant(libs, bd):
                 assert np.array_equal(xr.dequant(bd, qp, lv), xo.dequant(bd, qp, lv)), (w, h, qp)
 
 
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12, 9, 11])
 @pytest.mark.parametrize("bipred", [0, 1])
 def test_deblock(libs, bd, bipred):
     xo, xr = libs
@@ -331,7 +331,7 @@ def test_pad_border(libs):
             assert np.array_equal(pr[c], po[c])
 
 
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12, 9, 11])
 def test_tz_and_subpel_search(libs, bd):
     xo, xr = libs
     rng = np.random.default_rng(61 + bd)
@@ -366,7 +366,47 @@ def test_tz_and_subpel_search(libs, bd):
     assert n_grid > 30
 
 
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 11, 12])
+@pytest.mark.parametrize("simd", [0, 1])
+def test_search_on_full_swing_residuals(libs, bd, simd):
+    """The inputs of the GPU tests' extreme-residual searches (opposite Walsh patterns
+    at +-(2^bd - 1), all 14 shapes; test_gpu_parity.py, test_gpu_bitdepth_paths.py):
+    the checker those tests compare with is itself pinned on them.  (The harness's
+    xr_tz_search has no switch for the AC-only metrics of XVC_ME_USE_LIC: plain jobs.)"""
+    from helpers import (EXTREME_SHAPES, bi_struct, extreme_bi_jobs, extreme_blocks, me_struct,
+                         walsh_pictures)
+    xo, xr = libs
+    xr._set_simd(simd)
+    rng = np.random.default_rng(3100 + bd)      # (the seed and the draws of the GPU test)
+    bi_rng = np.random.default_rng(3200 + bd)
+    pw, ph, border = 256, 192, 128
+    n = 0
+    for trial in range(6):
+        orig, ref = walsh_pictures(rng, bd, pw, ph, border, trial)
+        for b in extreme_blocks(rng, pw, ph):
+            blk = me_struct(b)
+            rmv, _ = xr.tz_search(bd, blk, pw, ph, orig, ref, border)
+            omv, _ = xo.tz_search(bd, blk, pw, ph, orig, ref, border)
+            assert rmv == omv, (trial, tuple(b), rmv, omv)
+            r = xr.subpel_search(bd, blk, pw, ph, orig, ref, border, omv)
+            o = xo.subpel_search(bd, blk, pw, ph, orig, ref, border, omv)
+            assert r == o, (trial, tuple(b), r, o)
+            n += 1
+        # the bi-prediction refinement on the same pictures: the other list's prediction
+        # out of the opposite pattern, so the 2 * orig - pred target spans
+        # -(2^bd - 1) .. 2 * (2^bd - 1); searched in either pattern
+        search = ref if trial % 2 == 0 else orig
+        for j in extreme_bi_jobs(bi_rng, extreme_blocks(bi_rng, pw, ph)):
+            st = bi_struct(j)
+            r = xr.bipred_search(bd, st, pw, ph, orig, ref, search, border)
+            o = xo.bipred_search(bd, st, pw, ph, orig, ref, search, border)
+            assert r == o, (trial, j, r, o)
+            n += 1
+    xr._set_simd(1)
+    assert n == 2 * 6 * len(EXTREME_SHAPES)
+
+
+@pytest.mark.parametrize("bd", [8, 10, 12, 9, 11])
 def test_full_search(libs, bd):
     xo, xr = libs
     rng = np.random.default_rng(71)
@@ -387,7 +427,7 @@ def test_full_search(libs, bd):
         assert a == b
 
 
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12, 9, 11])
 def test_mc_bipred_block(libs, bd):
     xo, xr = libs
     rng = np.random.default_rng(83 + bd)
@@ -413,7 +453,7 @@ def test_mc_bipred_block(libs, bd):
             assert np.array_equal(a, o), (x, y, w, h, mv0, mv1, comp)
 
 
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12, 9, 11])
 def test_bipred_search(libs, bd):
     xo, xr = libs
     rng = np.random.default_rng(91 + bd)
@@ -443,7 +483,7 @@ def test_bipred_search(libs, bd):
     assert n == 32
 
 
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12, 9, 11])
 def test_mc_metric(libs, bd):
     """GetSubpelDist with every metric (T4's per-candidate step)."""
     xo, xr = libs
@@ -482,7 +522,7 @@ def affine_mvs(rng, w, i):
     return [base, mv1, mv2]
 
 
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12, 9, 11])
 def test_mc_affine_block(libs, bd):
     xo, xr = libs
     rng = np.random.default_rng(111 + bd)
@@ -687,7 +727,7 @@ def test_aqp_variance(libs, bd):
     assert len(hit) >= 8   # the sweep exercised most of the -3..7 range
 
 
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12, 9, 11])
 def test_lic_histogram_distance(libs, bd):
     import oracle_stats as st
     xo, xr = libs
@@ -759,7 +799,7 @@ def test_intra_prediction_all_modes_all_sizes(libs):
                                       oi.pred_block(xr, "xr", bd, j, rec, pw, ph)), (w, h, mode)
 
 
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12, 9, 11])
 def test_intra_satd_modes(libs, bd):
     import oracle_intra as oi
     xo, xr = libs
@@ -819,7 +859,7 @@ def test_intra_lm_chroma(libs, bd):
     assert n == 240
 
 
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12, 9, 11])
 def test_mc_lic_block(libs, bd):
     """InterPrediction::MotionCompensationMv with local illumination
     compensation (LocalIlluminationComp / DeriveLicParams)."""
@@ -889,7 +929,7 @@ def test_affine_gradient_search(libs, bd):
     assert nonzero > 25
 
 
-@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("bd", [8, 10, 12, 9, 11])
 def test_affine_me(libs, bd):
     """InterSearch::MotionEstAffine on zooming / rotating content: uni-pred and
     the bi-pred refinement search (target 2 * orig - other prediction)."""

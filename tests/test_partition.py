@@ -110,10 +110,18 @@ def compare_oracle_and_reference(name, pic, bd, qp, rdoq):
 needs_ref = pytest.mark.skipif(not ol.have_ref(), reason="reference harness not built")
 
 
+def partition_cases():
+    """Every fixture of SMALL at (10, 32) and (8, 27), and - the row-major sub-pel path of
+    bd > 10 - (12, 32) on two of them; RDOQ off and on.  The ids are those of the stacked
+    parameter lists this replaces."""
+    cases = [(n, p, bd, qp, rdoq) for rdoq in (False, True) for bd, qp in [(10, 32), (8, 27)]
+             for n, p in SMALL]
+    cases += [(n, p, 12, 32, rdoq) for rdoq in (False, True) for n, p in [("tiny", 1), ("c0", 1)]]
+    return [pytest.param(*c, id="%s-%d-%d-%d-%s" % c) for c in cases]
+
+
 @needs_ref
-@pytest.mark.parametrize("rdoq", [False, True])
-@pytest.mark.parametrize("bd,qp", [(10, 32), (8, 27)])
-@pytest.mark.parametrize("name,pic", SMALL)
+@pytest.mark.parametrize("name,pic,bd,qp,rdoq", partition_cases())
 def test_oracle_equals_reference_on_partitions(name, pic, bd, qp, rdoq):
     assert compare_oracle_and_reference(name, pic, bd, qp, rdoq) > 0
 
