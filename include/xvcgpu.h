@@ -620,6 +620,18 @@ xvcgpu_status xvcgpu_quant_rdo_reserve(xvcgpu_ctx *ctx, int n, size_t n_coeffs);
 #define XVCGPU_PROVE_ZERO_AUTO_QP 30
 xvcgpu_status xvcgpu_quant_rdo_set_prove_zero(xvcgpu_ctx *ctx, int mode);
 
+/* How the quantiser builds its class lists from the per-block classes (k_rdoq.h).
+ * Two launches of 1024-thread workgroups: rdoq_count_kernel counts the classes of each
+ * chunk of 4096 blocks, rdoq_scatter_kernel sums the chunks in front of its own and
+ * writes the indices.  One launch of 256-thread workgroups: rdoq_lists_kernel, where
+ * every workgroup of 1024 blocks counts the classes in front of it itself - a read
+ * that grows with the square of the batch.  The lists are the same either way.
+ * mode: 0 two launches, 1 one launch, -1 (default) one launch for batches of up to
+ * XVCGPU_RDOQ_ONE_LAUNCH_LISTS_MAX_BLOCKS blocks: twice a 1920x1080 picture's
+ * 3 x 8160 = 24 480, half a 3840x2160 picture's 3 x 32 400 = 97 200. */
+#define XVCGPU_RDOQ_ONE_LAUNCH_LISTS_MAX_BLOCKS (2 * 3 * 8160)
+xvcgpu_status xvcgpu_quant_rdo_set_list_form(xvcgpu_ctx *ctx, int mode);
+
 /* Diagnostics: the number of blocks of the last xvcgpu_quant_rdo_batch that
  * needed the walk, by class (out[0]: diagonal scan, up to four 4x4 sub-blocks;
  * out[1]: diagonal scan, up to sixteen, sides up to 32 - both walked with four
@@ -628,6 +640,11 @@ xvcgpu_status xvcgpu_quant_rdo_set_prove_zero(xvcgpu_ctx *ctx, int mode);
  * quantise to zero are settled by the classification pass and not counted.
  * Synchronises the stream. */
 xvcgpu_status xvcgpu_quant_rdo_class_counts(xvcgpu_ctx *ctx, int32_t out[3]);
+/* Tests: the class lists the context's last quantiser call built - counts[c] block
+ * indices of class c, ascending, at lists + c * cap (lists: 3 * cap entries; a count
+ * above cap is XVCGPU_INVALID_ARGUMENT).  Synchronises the stream. */
+xvcgpu_status xvcgpu_debug_rdoq_lists(xvcgpu_ctx *ctx, int32_t counts[3], int32_t *lists,
+                                      int cap);
 /* The walk is two launches: the four-lane classes (out[0], out[1] above) and the
  * general class (out[2]), whose waves hold 255 vector registers - even with an empty
  * list that launch waits for room beside other streams' kernels (190 us in flight

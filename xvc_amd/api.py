@@ -185,6 +185,7 @@ SYMBOLS = [
     "xvcgpu_get_transform_matrix", "xvcgpu_inter_pred_batch", "xvcgpu_deblock_tree",
     "xvcgpu_residual_rdoq_batch", "xvcgpu_quant_rdo_batch", "xvcgpu_recon_from_me_rdoq",
     "xvcgpu_quant_rdo_reserve", "xvcgpu_quant_rdo_class_counts", "xvcgpu_quant_rdo_set_prove_zero",
+    "xvcgpu_quant_rdo_set_list_form", "xvcgpu_debug_rdoq_lists",
     "xvcgpu_tx_eval_batch", "xvcgpu_root_cbf_batch", "xvcgpu_bipred_search_lic",
     "xvcgpu_inter_pred_batch_to", "xvcgpu_copy_blocks", "xvcgpu_intra_recon_waves",
     "xvcgpu_host_alloc", "xvcgpu_host_free", "xvcgpu_memcpy_h2d_async",
@@ -343,6 +344,8 @@ def load_library(allow_missing=()):
         "xvcgpu_quant_rdo_reserve": [_vp, C.c_int, C.c_size_t],
         "xvcgpu_quant_rdo_class_counts": [_vp, _vp],
         "xvcgpu_quant_rdo_set_prove_zero": [_vp, C.c_int],
+        "xvcgpu_quant_rdo_set_list_form": [_vp, C.c_int],
+        "xvcgpu_debug_rdoq_lists": [_vp, _vp, _vp, C.c_int],
         "xvcgpu_quant_rdo_set_four_lane_only": [_vp, C.c_int],
         "xvcgpu_tx_eval_batch": [_vp, _vp, C.c_int, _vp, _vp],
         "xvcgpu_inter_pred_batch_to": [_vp, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int],
@@ -736,6 +739,21 @@ class Context:
         """The all-zero proof ahead of the RDO quantiser's walk: 0 never, 1 always,
         -1 by batch size (xvcgpu_quant_rdo_set_prove_zero; same results either way)."""
         self._check(self.lib.xvcgpu_quant_rdo_set_prove_zero(self.h, int(mode)))
+
+    def set_rdoq_list_form(self, mode):
+        """How the RDO quantiser builds its class lists: 0 count + scatter (two launches),
+        1 rdoq_lists_kernel (one launch), -1 by batch size (xvcgpu_quant_rdo_set_list_form;
+        the same lists either way)."""
+        self._check(self.lib.xvcgpu_quant_rdo_set_list_form(self.h, int(mode)))
+
+    def debug_rdoq_lists(self, cap):
+        """The class lists of the last quantiser call: three int32 arrays of block indices
+        (xvcgpu_debug_rdoq_lists; cap: the call's block count)."""
+        counts = np.zeros(3, np.int32)
+        lists = np.zeros((3, max(1, int(cap))), np.int32)
+        self._check(self.lib.xvcgpu_debug_rdoq_lists(
+            self.h, counts.ctypes.data, lists.ctypes.data, lists.shape[1]))
+        return [lists[c, :counts[c]].copy() for c in range(3)]
 
     def use_own_stream(self):
         self._check(self.lib.xvcgpu_use_own_stream(self.h))

@@ -1817,6 +1817,97 @@ rdoq_scatter_kernel(int n, RdoqLists l) {
     for (int k = 0; k < 3; k++) l.count[k] = bs[k] + part[k][16 + 15];
 }
 
+// The same lists in ONE launch, for batches small enough that a redundant read of
+// the classes costs less than a second launch and the hand-over through l.part: a
+// workgroup of 256 threads owns RDOQ_LISTS_CHUNK blocks (four per thread, the
+// per-thread shape of rdoq_chunk_counts) and counts the classes of all the chunks
+// in front of it itself - 1024 bytes per chunk, sixteen at a time, resident in L2
+// (1080p: 24 workgroups, the last one reads 23 KB).  That read grows with the
+// square of n: the caller keeps the two launches above for large batches.  Four
+// waves place beside other streams' kernels where sixteen have to wait for a CU
+// with four free slots on every SIMD.  grid: ceil(n / RDOQ_LISTS_CHUNK); block: 256.
+#define RDOQ_LISTS_CHUNK 1024
+
+// the bytes of v that equal c (0..127), exactly: no carry crosses a byte
+__device__ __forceinline__ int rq_bytes_equal(uint32_t v, uint32_t c) {
+  const uint32_t x = v ^ (c * 0x01010101u);
+  return __popc(~(((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x | 0x7f7f7f7fu));
+}
+
+__global__ void __launch_bounds__(256)
+rdoq_lists_kernel(int n, RdoqLists l) {
+  __shared__ int wsum[3][4];    // the prefix read's wave sums
+  __shared__ int wtot[3][4];    // the chunk's own wave totals
+  const int t = threadIdx.x, b = blockIdx.x, wv = t >> 6;
+  const uint32_t *cw = reinterpret_cast<const uint32_t *>(l.cls);
+  // the chunks in front of this one: 64 * b 16-byte words of classes, all of them
+  // inside n.  l.cls is 16-byte aligned (ensure_rdoq_scratch keeps the lists'
+  // capacity a multiple of four), so the reads cover the prefix and nothing else
+  int v[3] = {0, 0, 0};
+  {
+    const uint4 *q = reinterpret_cast<const uint4 *>(cw);
+    const int quads = (RDOQ_LISTS_CHUNK / 16) * b;
+    for (int j = t; j < quads; j += 256) {
+      const uint4 u = q[j];
+      const uint32_t a[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        v[0] += rq_bytes_equal(a[k], 0);
+        v[1] += rq_bytes_equal(a[k], 1);
+        v[2] += rq_bytes_equal(a[k], 2);
+      }
+    }
+  }
+  // this chunk: four blocks per thread
+  const int i = b * RDOQ_LISTS_CHUNK + 4 * t;
+  uint32_t mine = 0;
+  int cnt[3] = {0, 0, 0};
+  if (i < n) {
+    mine = cw[i >> 2];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const int c = (int)(signed char)(mine >> (8 * k));
+      const bool in = i + k < n;
+      cnt[0] += in && c == 0;
+      cnt[1] += in && c == 1;
+      cnt[2] += in && c == 2;
+    }
+  }
+  int inc[3];
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    const int w = wave_reduce_add_i32(v[k]);
+    int s = cnt[k];
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int o = __shfl_up(s, d, 64);
+      if ((t & 63) >= d) s += o;
+    }
+    inc[k] = s;
+    if ((t & 63) == 0) wsum[k][wv] = w;
+    if ((t & 63) == 63) wtot[k][wv] = s;
+  }
+  __syncthreads();
+  int base[3], pos[3];
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    base[k] = wsum[k][0] + wsum[k][1] + wsum[k][2] + wsum[k][3];
+    int before = 0;
+#pragma unroll
+    for (int w = 0; w < 3; w++) before += w < wv ? wtot[k][w] : 0;
+    pos[k] = base[k] + before + inc[k] - cnt[k];
+  }
+  if (i < n) {
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const int c = (int)(signed char)(mine >> (8 * k));
+      if (i + k < n && c >= 0) l.list[c][pos[c]++] = i + k;
+    }
+  }
+  if (b == (int)gridDim.x - 1 && t == 255)
+    for (int k = 0; k < 3; k++) l.count[k] = pos[k];   // base + the chunk's total
+}
+
 // LDS of one wave: G lanes per block (64 / G blocks per wave), blocks of at most NSB
 // region sub-blocks.  One table of context costs per wave: the groups of a wave
 // nearly always name the same snapshot; when they do not, the wave serves one

@@ -247,6 +247,8 @@ xvcgpu_status xvcgpu_create(int device, xvcgpu_ctx **out) {
     ctx->rdoq_classified_proved = false;
     const char *e = getenv("XVCGPU_PROVE_ZERO");   // 0 / 1; default: by batch size
     ctx->rdoq_prove_zero = (e && (e[0] == '0' || e[0] == '1') && !e[1]) ? e[0] - '0' : -1;
+    ctx->rdoq_list_form = -1;
+    ctx->rdoq_last_n = 0;
   }
   for (int i = 0; i < 64; i++) ctx->ev_pool[i] = nullptr;
   ctx->d_me_rot = nullptr;
@@ -900,6 +902,26 @@ xvcgpu_status xvcgpu_debug_rdoq_trace(unsigned long long *out, int n_rows) {
 }
 #endif
 
+// tests: the class lists the context's last quantiser call built (list c at lists + c * cap)
+xvcgpu_status xvcgpu_debug_rdoq_lists(xvcgpu_ctx *ctx, int32_t counts[3], int32_t *lists,
+                                      int cap) {
+  if (!ctx || !counts || !lists || cap < 0) return XVCGPU_INVALID_ARGUMENT;
+  counts[0] = counts[1] = counts[2] = 0;
+  if (!ctx->d_rdoq_lists || !ctx->rdoq_last_n) return XVCGPU_OK;
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  HIP_TRY(ctx, hipMemcpy(counts, ctx->d_rdoq_lists, 3 * sizeof(int32_t), hipMemcpyDeviceToHost));
+  for (int c = 0; c < 3; c++) {
+    if (counts[c] < 0 || counts[c] > ctx->rdoq_last_n)
+      return fail(ctx, XVCGPU_DEVICE_ERROR, "rdoq list count out of range");
+    if (counts[c] > cap) return fail(ctx, XVCGPU_INVALID_ARGUMENT, "rdoq lists: cap too small");
+    if (counts[c])
+      HIP_TRY(ctx, hipMemcpy(lists + (size_t)c * cap,
+                             ctx->d_rdoq_lists + 4 + (size_t)c * ctx->rdoq_lists_cap,
+                             counts[c] * sizeof(int32_t), hipMemcpyDeviceToHost));
+  }
+  return XVCGPU_OK;
+}
+
 xvcgpu_status xvcgpu_me_search(xvcgpu_ctx *ctx, const xvcgpu_picture *orig,
                                const xvcgpu_picture *ref, int flags,
                                const xvcgpu_me_block *d_blocks, int n,
@@ -1414,7 +1436,9 @@ static xvcgpu_status ensure_rdoq_scratch(xvcgpu_ctx *ctx, int n, size_t n_coeffs
       ctx->d_rdoq_lists = nullptr;
       ctx->rdoq_lists_cap = 0;
     }
-    const int cap = n + n / 4;
+    // a multiple of four: the classes then start 16 bytes aligned behind count[4] and
+    // the three lists, which rdoq_lists_kernel's 16-byte reads rely on
+    const int cap = (n + n / 4 + 3) & ~3;
     // count[4], three lists and the classes (cap bytes = cap / 4 ints), then the
     // compaction's per-chunk counts
     if (hipMalloc(&ctx->d_rdoq_lists,
@@ -1442,6 +1466,12 @@ xvcgpu_status xvcgpu_quant_rdo_set_prove_zero(xvcgpu_ctx *ctx, int mode) {
   return XVCGPU_OK;
 }
 
+xvcgpu_status xvcgpu_quant_rdo_set_list_form(xvcgpu_ctx *ctx, int mode) {
+  if (!ctx || mode < -1 || mode > 1) return XVCGPU_INVALID_ARGUMENT;
+  ctx->rdoq_list_form = mode;
+  return XVCGPU_OK;
+}
+
 xvcgpu_status xvcgpu_quant_rdo_set_four_lane_only(xvcgpu_ctx *ctx, int on) {
   if (!ctx) return XVCGPU_INVALID_ARGUMENT;
   ctx->rdoq_four_lane_only = on ? 1 : 0;
@@ -1454,7 +1484,7 @@ xvcgpu_status xvcgpu_quant_rdo_reserve(xvcgpu_ctx *ctx, int n, size_t n_coeffs) 
 }
 
 static RdoqLists rdoq_lists_of(xvcgpu_ctx *ctx) {
-  const int cap = ctx->rdoq_lists_cap;
+  const int cap = ctx->rdoq_lists_cap;   // a multiple of four: cls is 16-byte aligned
   RdoqLists l;
   l.count = ctx->d_rdoq_lists;
   for (int c = 0; c < 3; c++) l.list[c] = ctx->d_rdoq_lists + 4 + (size_t)c * cap;
@@ -1497,11 +1527,18 @@ static xvcgpu_status quant_rdo_launch(xvcgpu_ctx *ctx, int bitdepth,
                        dim3(256), 0, ctx->stream,
                        bitdepth, d_blocks, n, d_coeffs, d_offsets, d_levels, d_nnz, d_contexts,
                        d_params, l);
-  {
+  // the class lists: one launch of small workgroups for small batches, count + scatter
+  // above the threshold (k_rdoq.h, xvcgpu_quant_rdo_set_list_form)
+  if (ctx->rdoq_list_form > 0 ||
+      (ctx->rdoq_list_form < 0 && n <= XVCGPU_RDOQ_ONE_LAUNCH_LISTS_MAX_BLOCKS)) {
+    hipLaunchKernelGGL(rdoq_lists_kernel, dim3((n + RDOQ_LISTS_CHUNK - 1) / RDOQ_LISTS_CHUNK),
+                       dim3(256), 0, ctx->stream, n, l);
+  } else {
     const int chunks = (n + RDOQ_CHUNK - 1) / RDOQ_CHUNK;
     hipLaunchKernelGGL(rdoq_count_kernel, dim3(chunks), dim3(1024), 0, ctx->stream, n, l);
     hipLaunchKernelGGL(rdoq_scatter_kernel, dim3(chunks), dim3(1024), 0, ctx->stream, n, l);
   }
+  ctx->rdoq_last_n = n;
   // the class sizes are only known on the device: a bounded number of workgroups
   // per class that walk their list (k_rdoq.h)
   static const int grid16 = [] {

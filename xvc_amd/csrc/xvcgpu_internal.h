@@ -83,6 +83,8 @@ struct xvcgpu_ctx {
   int seg_ring_half;
   hipEvent_t seg_ring_ev[2];
   bool seg_ring_used[2];
+  int rdoq_list_form;              // xvcgpu_quant_rdo_set_list_form: 0 count + scatter / 1 one launch / -1 by batch size
+  int rdoq_last_n;                 // blocks of the last quantiser call (xvcgpu_debug_rdoq_lists)
   int rdoq_four_lane_only;         // xvcgpu_quant_rdo_set_four_lane_only: the general class's launch is skipped
   int *h_rdoq_misuse;              // page-locked: set by the walk when such a batch held a general-class block
   // scratch of xvcgpu_quant_rdo_batch (k_rdoq.h): the three class lists + their

@@ -442,7 +442,10 @@ class FramePass:
         the tail is the one deblock_pad_ssd launch from there into rec.
         The quant_rdo launches run without the promise xvcgpu_frame_pass gives the
         quantiser for its batch (tx_four_lane_only: the general-class launch left
-        out), so that bench.py's per-kernel times stay what they were."""
+        out), so that bench.py's per-kernel times stay what they were.
+        "quant_rdo" is the class lists and the walk: rdoq_lists_kernel (one launch; batches
+        above XVCGPU_RDOQ_ONE_LAUNCH_LISTS_MAX_BLOCKS: rdoq_count_kernel + rdoq_scatter_kernel,
+        xvcgpu_quant_rdo_set_list_form) -> quant_rdo_packed4_kernel [-> quant_rdo_packed_kernel]."""
         ctx, d, lib = self.ctx, self.desc, self.ctx.lib
         n, T, bd, form = d.n_cus, len(d.tx), self.bd, self.form
         out = self.scratch if fused_tail else rec
