@@ -29,6 +29,24 @@ __device__ __forceinline__ T group_sum(T v) {
   return v;
 }
 
+// for (i = first; i < n; i += STEP) body(i) over the lanes of a wave, first < STEP.  N > 0:
+// n is the constant N - the trips are unrolled and carry no compare, mask update or branch
+// (a bound test only in a last, partial trip); N == 0: the loop as written, n at run time.
+template <int N, int STEP, typename F>
+__device__ __forceinline__ void lane_loop(int first, int n, F body) {
+  if constexpr (N > 0) {
+    constexpr int TRIPS = (N + STEP - 1) / STEP;
+#pragma unroll
+    for (int k = 0; k < TRIPS; k++) {
+      const int i = first + k * STEP;
+      if (N % STEP != 0 && k == TRIPS - 1 && i >= N) break;
+      body(i);
+    }
+  } else {
+    for (int i = first; i < n; i += STEP) body(i);
+  }
+}
+
 // Arguments of one kernel for up to XVC_MULTI_MAX pictures, passed by value: a
 // "multi" kernel is the single-picture kernel's body run with the arguments of
 // picture blockIdx.y (xvcgpu_frame_pass_multi: kernels of the same kind run well

@@ -199,11 +199,12 @@ __device__ __forceinline__ int tx2_job(Tx2Shared &sh, const xvcgpu_tx_block &b, 
   const bool bias = ((lgw + lgh) & 1) != 0;
   const int tshift = 15 - bd - ((lgw + lgh) >> 1);
   const int n_el = w * h;
+  constexpr int NE = FW * FH;   // > 0: n_el at compile time, lane_loop unrolls the trips
 
   int nnz;
   if (MODE != TX_MODE_INV) {
     // residual, 4 samples per lane along a row
-    for (int i = lane * 4; i < n_el; i += 4 * G) {
+    lane_loop<NE, 4 * G>(lane * 4, n_el, [&](int i) {
       const int y = i >> lw, x = i & (w - 1);
       // blocks are <= 256 samples: one iteration, so a caller may have
       // fetched this lane's four original samples ahead of time
@@ -219,7 +220,7 @@ __device__ __forceinline__ int tx2_job(Tx2Shared &sh, const xvcgpu_tx_block &b, 
       *reinterpret_cast<uint2 *>(s.r + i) =
           make_uint2((uint32_t)(d0 & 0xffff) | ((uint32_t)d1 << 16),
                      (uint32_t)(d2 & 0xffff) | ((uint32_t)d3 << 16));
-    }
+    });
     wave_sync();
     ME2_TRACE(2);
     const int shift1 = lgw + bd - 9 + (b.tx_hor == XVC_TX_DCT2_LOW ? 0 : 2);
@@ -248,7 +249,7 @@ __device__ __forceinline__ int tx2_job(Tx2Shared &sh, const xvcgpu_tx_block &b, 
           }
           wave_sync();
         }
-        for (int i = lane; i < n_el; i += G) {
+        lane_loop<NE, G>(lane, n_el, [&](int i) {
           const int a = (short)d_abs((int)s.c[i]);
           const bool nz = (short)(int)((((long long)a * fq_scale) + fq_offset) >> fq_shift) != 0;
           any |= nz;
@@ -258,7 +259,7 @@ __device__ __forceinline__ int tx2_job(Tx2Shared &sh, const xvcgpu_tx_block &b, 
               pv->xy[grp][slot] = (unsigned short)(((i & (h - 1)) << 8) | (i >> lgh));
             if (a < 0) pv->fail[grp] = 1;   // a magnitude of 32768: no proof
           }
-        }
+        });
         const unsigned long long group =
             G == 64 ? ~0ull : (((1ull << G) - 1) << (ME2_LANE & ~(G - 1)));
         bool live = (__ballot(any) & group) != 0;
@@ -269,16 +270,16 @@ __device__ __forceinline__ int tx2_job(Tx2Shared &sh, const xvcgpu_tx_block &b, 
         if (lane == 0) fc->cls[bi] = live ? (signed char)rq_class_of(b) : (signed char)-1;
         if (!live) {   // its levels are zeros; the coefficients are not needed again
           int16_t *z = fc->levels + level_off[bi];
-          for (int i = lane; i < n_el; i += G) z[i] = 0;
+          lane_loop<NE, G>(lane, n_el, [&](int i) { z[i] = 0; });
           if (lane == 0 && fc->nnz) fc->nnz[bi] = 0;
           return 0;
         }
       }
       if (lv)
-        for (int i = lane; i < n_el; i += G) {
+        lane_loop<NE, G>(lane, n_el, [&](int i) {
           const int x = i >> lgh, k2 = i & (h - 1);  // C[x][k2] (h a power of two)
           lv[k2 * w + x] = s.c[i];
-        }
+        });
       return 0;
     }
     // QuantFast (rdo_quant.cc:156-201): levels -> s.r, rounding remainders
@@ -359,10 +360,10 @@ __device__ __forceinline__ int tx2_job(Tx2Shared &sh, const xvcgpu_tx_block &b, 
   } else {
     nnz = nnz_out[bi];
     if (nnz)
-      for (int i = lane; i < n_el; i += G) {
+      lane_loop<NE, G>(lane, n_el, [&](int i) {
         const int x = i >> lgh, k2 = i & (h - 1);
         s.r[i] = lv[k2 * w + x];
-      }
+      });
   }
   wave_sync();
 
@@ -390,13 +391,13 @@ __device__ __forceinline__ int tx2_job(Tx2Shared &sh, const xvcgpu_tx_block &b, 
   {
     const int shift = 6 - tshift + (bias ? 8 : 0);
     const int scale = (kInvQuantScales[qpb % 6] << (qpb / 6)) * (bias ? 181 : 1);
-    for (int i = lane; i < n_el; i += G) {
+    lane_loop<NE, G>(lane, n_el, [&](int i) {
       const int prod = (int)s.r[i] * scale;
       int cf;
       if (shift > 0) cf = (prod + (1 << (shift - 1))) >> shift;
       else cf = (int)((unsigned)prod << -shift);
       s.c[i] = (int16_t)d_clip3(cf, -32768, 32767);
-    }
+    });
   }
   wave_sync();
   ME2_TRACE(6);
@@ -407,7 +408,7 @@ __device__ __forceinline__ int tx2_job(Tx2Shared &sh, const xvcgpu_tx_block &b, 
   if (dc_only && dct2_both) {  // InvDct2Dc, transform.cc:279-291
     const int sh = 14 - bd, add = 1 << (sh - 1);
     const int cf = (int16_t)(((((int)s.c[0] + 1) >> 1) + add) >> sh);
-    for (int i = lane * 4; i < n_el; i += 4 * G) {
+    lane_loop<NE, 4 * G>(lane * 4, n_el, [&](int i) {
       const int y = i >> lw, x = i & (w - 1);
       const U16x4 p = *reinterpret_cast<const U16x4 *>(
           pred_p + (ptrdiff_t)y * pred_stride + x);
@@ -418,7 +419,7 @@ __device__ __forceinline__ int tx2_job(Tx2Shared &sh, const xvcgpu_tx_block &b, 
                ((uint32_t)d_clip3((int)(p.v[1] >> 16) + cf, 0, smax) << 16);
       *reinterpret_cast<U16x4 *>(pr.p + (ptrdiff_t)(b.y + y) * pr.stride + b.x + x) = o;
       if (dist_out) dist4(y, x, p, cf, cf, cf, cf);
-    }
+    });
     if (dist_out) dist_finish();
     return nnz;
   }
@@ -433,7 +434,7 @@ __device__ __forceinline__ int tx2_job(Tx2Shared &sh, const xvcgpu_tx_block &b, 
     ME2_TRACE(7);
   }
   // SampleBuffer::AddClip
-  for (int i = lane * 4; i < n_el; i += 4 * G) {
+  lane_loop<NE, 4 * G>(lane * 4, n_el, [&](int i) {
     const int y = i >> lw, x = i & (w - 1);
     const U16x4 p = *reinterpret_cast<const U16x4 *>(
         pred_p + (ptrdiff_t)y * pred_stride + x);
@@ -447,7 +448,7 @@ __device__ __forceinline__ int tx2_job(Tx2Shared &sh, const xvcgpu_tx_block &b, 
     if (dist_out)
       dist4(y, x, p, (int)(int16_t)(rs.x & 0xffff), (int)rs.x >> 16, (int)(int16_t)(rs.y & 0xffff),
             (int)rs.y >> 16);
-  }
+  });
   if (dist_out) dist_finish();
   return nnz;
 }
@@ -487,8 +488,6 @@ __global__ void __launch_bounds__(64 * TX2_WAVES)
 inv_cu_pairs_kernel(PicView rec, const xvcgpu_tx_block *blocks, int n_cus, int16_t *levels,
                     const uint32_t *level_off, int32_t *nnz_out, const int16_t *tx_tables,
                     const int16_t *tx_tables_t, TxTableLayout lay) {
-  __shared__ Tx2Shared s_all[TX2_WAVES];
-  Tx2Shared &s = s_all[threadIdx.x >> 6];
   const int n = 2 * n_cus;
   const int n_wg = (n + TX2_WAVES - 1) / TX2_WAVES;
   const int wg = xcd_job_index(blockIdx.x, n_wg);
@@ -496,26 +495,43 @@ inv_cu_pairs_kernel(PicView rec, const xvcgpu_tx_block *blocks, int n_cus, int16
   const int job = __builtin_amdgcn_readfirstlane(wg * TX2_WAVES + (int)(threadIdx.x >> 6));
   if (job >= n) return;
   const int ci = job >> 1;
+  // the counts before anything else: in place, a block without a level is already what it
+  // will be, and most waves end here
+  if (!(job & 1)) {
+    if (nnz_out[3 * ci] == 0) return;
+  } else {
+    if (nnz_out[3 * ci + 1] == 0 && nnz_out[3 * ci + 2] == 0) return;
+  }
+  __shared__ Tx2Shared s_all[TX2_WAVES];
+  Tx2Shared &s = s_all[threadIdx.x >> 6];
   if (!(job & 1)) {
     const int bi = 3 * ci;
-    if (nnz_out[bi] == 0) return;   // in place: the block is already what it will be
     const xvcgpu_tx_block b = blocks[bi];
     if (!tx_small_job(b)) return;   // (not a block of this layout: left as it is)
     const PlaneView pc = rec.c[0];
-    tx2_job<TX_MODE_INV, 64, false>(s, b, bi, rec.bd, pc, pc.p + (ptrdiff_t)b.y * pc.stride + b.x,
-                                    pc.stride, pc, levels, level_off, nnz_out, tx_tables,
-                                    tx_tables_t, lay);
+    const uint16_t *at = pc.p + (ptrdiff_t)b.y * pc.stride + b.x;
+    if (__builtin_expect(b.w == 16 && b.h == 16, 1))   // (a 16x16 CU's luma block: nearly every job)
+      tx2_job<TX_MODE_INV, 64, false, 16, 16>(s, b, bi, rec.bd, pc, at, pc.stride, pc, levels,
+                                              level_off, nnz_out, tx_tables, tx_tables_t, lay);
+    else
+      tx2_job<TX_MODE_INV, 64, false>(s, b, bi, rec.bd, pc, at, pc.stride, pc, levels, level_off,
+                                      nnz_out, tx_tables, tx_tables_t, lay);
     return;
   }
-  if (nnz_out[3 * ci + 1] == 0 && nnz_out[3 * ci + 2] == 0) return;
   // this lane's half: lanes 0-31 the U block, 32-63 the V block
   const int g = ME2_LANE >> 5, bi = 3 * ci + 1 + g;
   const xvcgpu_tx_block b = blocks[bi];
   if (!tx_small_job(b) || b.w * b.h > 64) return;   // a half-wave holds a block of <= 64 samples
   const PlaneView pc = g ? rec.c[2] : rec.c[1];
-  tx2_job<TX_MODE_INV, 32, false>(s, b, bi, rec.bd, pc, pc.p + (ptrdiff_t)b.y * pc.stride + b.x,
-                                  pc.stride, pc, levels, level_off, nnz_out, tx_tables,
-                                  tx_tables_t, lay, nullptr, g * 128);
+  const uint16_t *at = pc.p + (ptrdiff_t)b.y * pc.stride + b.x;
+  // (U and V of a CU have one size: the test is wave-uniform)
+  if (__builtin_expect(b.w == 8 && b.h == 8, 1))
+    tx2_job<TX_MODE_INV, 32, false, 8, 8>(s, b, bi, rec.bd, pc, at, pc.stride, pc, levels,
+                                          level_off, nnz_out, tx_tables, tx_tables_t, lay,
+                                          nullptr, g * 128);
+  else
+    tx2_job<TX_MODE_INV, 32, false>(s, b, bi, rec.bd, pc, at, pc.stride, pc, levels, level_off,
+                                    nnz_out, tx_tables, tx_tables_t, lay, nullptr, g * 128);
 }
 
 template <int MODE, bool RDOQ = false>
