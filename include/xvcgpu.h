@@ -1143,7 +1143,38 @@ xvcgpu_status xvcgpu_copy_segments(xvcgpu_ctx *ctx, const xvcgpu_copy_segment *d
  * CompressAndEvalCbf for the uni-pred CUs of a->d_me), DEBLOCK_V, DEBLOCK_H
  * (DeblockingFilter::DeblockPicture, by rows so that a row shard can exchange
  * its halo in between), PAD (YuvPicture::PadBorder), SSD (ComparePicture parts).
- * Asynchronous on the context's stream like its parts. */
+ * Asynchronous on the context's stream like its parts.
+ *
+ * ENCODE with n_cus > 0 runs the search (xvcgpu_me_search_sized with me_shape, or the
+ * plan's) and then the launches of a->form, which the caller names:
+ *
+ *   form (XVC_FP_FORM_)  launches behind the search              fields read beside the common ones
+ *   RECON_FROM_ME        xvcgpu_recon_from_me, or _rdoq where     d_nnz, d_cus_own (optional);
+ *                        d_rdoq_params is set                    d_rdoq_params + d_rdoq_contexts
+ *   FWD_FROM_ME          xvcgpu_fwd_from_me_classify_prove ->     d_rdoq_params, d_rdoq_contexts, d_tx,
+ *                        xvcgpu_quant_rdo_classified_batch ->     n_tx == 3 * n_cus, d_coeffs, n_coeffs,
+ *                        xvcgpu_inv_transform_cu_order           d_levels, d_level_off, d_nnz, d_cus_own,
+ *                                                                tx_four_lane_only
+ *   FWD_TRANSFORM        xvcgpu_mc_from_me ->                     pred, d_luma_tx_index and those of
+ *                        xvcgpu_fwd_transform_batch ->            FWD_FROM_ME (any n_tx)
+ *                        xvcgpu_quant_rdo_batch ->
+ *                        xvcgpu_inv_transform_batch ->
+ *                        xvcgpu_cu_info_from_me
+ *   RESIDUAL             xvcgpu_mc_from_me ->                     pred, d_tx, n_tx, d_luma_tx_index,
+ *                        xvcgpu_residual_batch ->                 d_nnz, d_cus_own; d_levels +
+ *                        xvcgpu_cu_info_from_me                  d_level_off optional; no d_rdoq_params
+ *   RESIDUAL_RDOQ        the same around                         those of RESIDUAL, d_rdoq_params,
+ *                        xvcgpu_residual_rdoq_batch              d_rdoq_contexts
+ *
+ * Common: orig, ref, rec, d_me, d_results, n_cus, max_block_size, qp_y, qp_c, ref_poc.
+ * RECON_FROM_ME and FWD_FROM_ME take a CU whole: max_block_size <= 16 and, with a plan, no
+ * CU side below 8.  Form 0, a form the block cannot run or a missing field is
+ * XVCGPU_INVALID_ARGUMENT with a message naming it (xvcgpu_last_error), decided before the
+ * first launch: a refused call has enqueued nothing.  A set but unused field changes nothing.
+ * With scratch_rec, all phases and all rows (and no CU side of 4 in the plan) the form
+ * reconstructs into scratch_rec and the pass ends with xvcgpu_deblock_pad_ssd; FWD_FROM_ME
+ * then runs its inverse transform and that tail on the context's high-priority stream where
+ * it has one. */
 xvcgpu_status xvcgpu_frame_pass(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_args *a,
                                 int phases);
 
@@ -1155,9 +1186,10 @@ xvcgpu_status xvcgpu_frame_pass(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_args *a
  * Same results as n calls of xvcgpu_frame_pass(ctxs[i], args[i], phases).
  * Everything is enqueued on ctxs[0]'s stream; ctxs[i] lends picture i its
  * scratch (its own stream must be idle or the same stream).  Batched for
- * 2 <= n <= 4 whole pictures of one size whose CUs are 8x8 ... 16x16
- * (scratch_rec given), all phases, QuantFast or the packed RDOQ pipeline;
- * anything else falls back to the n single calls, each on its own context. */
+ * 2 <= n <= 4 whole pictures of one size and device that end with the fused tail
+ * (scratch_rec given, all phases), all of form FWD_FROM_ME or all of form
+ * RECON_FROM_ME with QuantFast; anything else falls back to the n single calls, each
+ * on its own context. */
 xvcgpu_status xvcgpu_frame_pass_multi(xvcgpu_ctx *const *ctxs,
                                       const xvcgpu_frame_pass_args *const *args, int n,
                                       int phases);
@@ -1192,18 +1224,13 @@ xvcgpu_status xvcgpu_me_search_planned(xvcgpu_ctx *ctx, const xvcgpu_picture *or
 
 /* xvcgpu_frame_pass with the search of a->d_me run through `plan` (made from a->d_me,
  * a->n_cus and the class of a->max_block_size; anything else: XVCGPU_INVALID_ARGUMENT), for
- * a pass over CUs of any mix of sizes.  The plan knows the shapes: where every CU has both
- * sides in 8 ... 16 the forms of xvcgpu_frame_pass (their kernels hold a CU whole); where
- * one is larger than 16x16 or has a side of 4, the any-size middle - QuantFast (no
- * d_rdoq_params) = xvcgpu_mc_from_me into a->pred -> xvcgpu_residual_batch over a->d_tx /
- * a->n_tx (d_levels / d_level_off optional) -> xvcgpu_cu_info_from_me through
- * a->d_luma_tx_index; packed RDOQ (d_rdoq_params and pred) = xvcgpu_mc_from_me ->
- * xvcgpu_fwd_transform_batch -> xvcgpu_quant_rdo_batch -> inverse transform -> CU records.
- * Such a pass without those arguments is XVCGPU_INVALID_ARGUMENT, not a wrong picture.
- * QuantFast with d_levels (and pred, d_tx, d_luma_tx_index) given takes the any-size middle
- * for any shapes: only the residual pipeline stores levels.  The fused tail (scratch_rec)
- * covers CUs without a side of 4: with one in the plan scratch_rec is ignored and the pass
- * ends with the separate deblocking, padding and SSD launches. */
+ * a pass over CUs of any mix of sizes.  The forms are those of xvcgpu_frame_pass; the plan
+ * knows the shapes, so RECON_FROM_ME or FWD_FROM_ME over a plan that holds a CU side of 4 is
+ * refused (XVCGPU_INVALID_ARGUMENT, not a wrong picture): such a partition, or one with a CU
+ * above 16x16, runs FWD_TRANSFORM, RESIDUAL or RESIDUAL_RDOQ.  Only those store QuantFast
+ * levels (d_levels), whatever the shapes.  The fused tail (scratch_rec) covers CUs without a
+ * side of 4: with one in the plan scratch_rec is ignored and the pass ends with the separate
+ * deblocking, padding and SSD launches. */
 xvcgpu_status xvcgpu_frame_pass_planned(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_args *a,
                                         const xvcgpu_me_plan *plan, int phases);
 

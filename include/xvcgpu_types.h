@@ -541,6 +541,12 @@ typedef struct xvcgpu_mc_block {
 #define XVC_FP_DEBLOCK_H 4  /* xvcgpu_deblock_rows pass 1 on [db_y_begin, dbh_y_end) */
 #define XVC_FP_PAD 8        /* xvcgpu_pad_border(rec)                           */
 #define XVC_FP_SSD 16       /* xvcgpu_picture_ssd_rows(orig, rec, luma)         */
+/* xvcgpu_frame_pass_args.form, named as pipeline.FramePass.form names them; 0 is none */
+#define XVC_FP_FORM_RECON_FROM_ME 1
+#define XVC_FP_FORM_FWD_FROM_ME 2
+#define XVC_FP_FORM_FWD_TRANSFORM 3
+#define XVC_FP_FORM_RESIDUAL 4
+#define XVC_FP_FORM_RESIDUAL_RDOQ 5
 typedef struct xvcgpu_frame_pass_args {
   const struct xvcgpu_picture *orig, *ref;
   struct xvcgpu_picture *rec;
@@ -592,6 +598,10 @@ typedef struct xvcgpu_frame_pass_args {
    * XVCGPU_ME_ONLY_SQ16 where every job is one (a picture whose width is a multiple of 16
    * on the 16-sample CU grid) */
   int32_t me_shape;
+  /* XVC_FP_FORM_*: the launches of XVC_FP_ENCODE between the search and the tail (the
+   * table at xvcgpu_frame_pass in xvcgpu.h).  The caller says it, the call checks that the
+   * block can run it - before the first launch - and never guesses it from the pointers. */
+  int32_t form;
 } xvcgpu_frame_pass_args;
 
 /* One job of xvcgpu_affine_me_batch: InterSearch::MotionEstAffine for one

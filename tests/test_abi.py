@@ -45,7 +45,7 @@ def test_struct_layouts_match_header(api):
     assert api.AFFINE_ME_DTYPE == oracle_affine_me.BLOCK_DTYPE
     assert api.AFFINE_ME_RESULT_DTYPE == oracle_affine_me.RESULT_DTYPE
     src = ("#include <stdio.h>\n#include <stddef.h>\n#include \"xvcgpu.h\"\nint main(){"
-           "printf(\"%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n\", sizeof(xvcgpu_cu_info),"
+           "printf(\"%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n\", sizeof(xvcgpu_cu_info),"
            "sizeof(xvcgpu_me_block), sizeof(xvcgpu_me_result), sizeof(xvcgpu_tx_block),"
            "sizeof(xvcgpu_mc_block), sizeof(xvcgpu_metric_cand),"
            "offsetof(xvcgpu_cu_info, mv), offsetof(xvcgpu_me_block, lambda16),"
@@ -55,7 +55,8 @@ def test_struct_layouts_match_header(api):
            "offsetof(xvcgpu_mc_lic_block, left_x), sizeof(xvcgpu_affine_me_block),"
            "offsetof(xvcgpu_affine_me_block, other_mv), sizeof(xvcgpu_affine_me_result),"
            "sizeof(xvcgpu_copy_segment), sizeof(xvcgpu_frame_pass_args),"
-           "offsetof(xvcgpu_frame_pass_args, me_shape));return 0;}")
+           "offsetof(xvcgpu_frame_pass_args, me_shape),"
+           "offsetof(xvcgpu_frame_pass_args, form));return 0;}")
     import subprocess
     import tempfile
     with tempfile.TemporaryDirectory() as d:
@@ -66,8 +67,15 @@ def test_struct_layouts_match_header(api):
     assert [int(v) for v in out] == [84, 32, 24, 12, 16, 12, 20, 24, 48, 24, 40, 12, 10, 24, 20,
                                        api.AFFINE_ME_DTYPE.itemsize, 60, api.AFFINE_ME_RESULT_DTYPE.itemsize,
                                        api.SEG_DTYPE.itemsize, C.sizeof(api.FramePassArgs),
-                                       api.FramePassArgs.me_shape.offset]
-    assert C.sizeof(api.FramePassArgs) == 232 and api.FramePassArgs.me_shape.offset == 228
+                                       api.FramePassArgs.me_shape.offset,
+                                       api.FramePassArgs.form.offset]
+    assert C.sizeof(api.FramePassArgs) == 240 and api.FramePassArgs.me_shape.offset == 228
+    assert api.FramePassArgs.form.offset == 232
+    # the form constants of the header are the indices of api.FP_FORM_NAMES
+    hdr = open(os.path.join(ROOT, "include", "xvcgpu_types.h")).read()
+    forms = dict(re.findall(r"#define XVC_FP_FORM_([A-Z_]+) (\d+)", hdr))
+    assert {k.lower(): int(v) for k, v in forms.items()} == \
+        {n: i for i, n in enumerate(api.FP_FORM_NAMES) if n}
     assert api.AFFINE_ME_DTYPE.itemsize == 84 and api.AFFINE_ME_RESULT_DTYPE.itemsize == 32
 
 

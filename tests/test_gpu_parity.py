@@ -1140,6 +1140,50 @@ def test_frame_pass_multi(gpu, rdoq, n):
         c.close()
 
 
+def test_frame_pass_multi_picture_by_picture(gpu):
+    """Two pictures of 64x64 of which the second is of form `residual` (fused=False): not
+    what the batched launches cover, so the call runs each picture's own pass - the
+    second's prediction picture is written, which no batched launch does - and both give
+    the bytes of a single run()."""
+    api, ctx = gpu
+    from xvc_amd import pipeline, synth
+    pw, ph, qp, bd = 64, 64, 32, 10
+    clip = synth.SyntheticClip(pw, ph, bd)
+    ctxs = [api.Context(0) for _ in range(2)]
+    kws = [dict(), dict(fused=False)]
+    passes = [pipeline.FramePass(c, pw, ph, bd, qp=qp, **kw) for c, kw in zip(ctxs, kws)]
+    assert [p.form for p in passes] == ["recon_from_me", "residual"]
+    assert all(p.fused_tail for p in passes)
+    pipeline.share_stream(passes)
+    pics = [[c.picture(pw, ph, bd) for _ in range(3)] for c in ctxs]      # orig, ref, rec
+    sO, sR, sRec = (ctx.picture(pw, ph, bd) for _ in range(3))
+    for i in range(2):
+        pics[i][0].upload(pad_planes(clip.frame(i + 1), bd), BL)
+        pics[i][1].upload(pad_planes(clip.frame(i), bd), BL)
+    poison = pad_planes([np.full_like(p, 3) for p in clip.frame(0)], bd)
+    passes[1].pred.upload(poison, BL)
+    pipeline.run_multi(passes, [p[0] for p in pics], [p[1] for p in pics], [p[2] for p in pics],
+                       [0, 1])
+    ctxs[0].sync()
+    assert not np.array_equal(passes[1].pred.download(BL)[0], poison[0])
+    for i in range(2):
+        single = pipeline.FramePass(ctx, pw, ph, bd, qp=qp, **kws[i])
+        sO.upload(pics[i][0].download(BL), BL)
+        sR.upload(pics[i][1].download(BL), BL)
+        single.run(sO, sR, sRec, ref_poc=i)
+        ctx.sync()
+        got, exp = pics[i][2].download(BL), sRec.download(BL)
+        for c in range(3):
+            assert np.array_equal(got[c], exp[c]), (i, c)
+        for a, b in zip(passes[i].results(), single.results()):
+            assert np.array_equal(a, b), i
+        single.destroy()
+    for p in passes:
+        p.destroy()
+    for c in ctxs:
+        c.close()
+
+
 @pytest.mark.parametrize("bd,qp,size", [(8, 22, (352, 288)), (8, 37, (200, 120)),
                                         (12, 32, (352, 288)), (12, 17, (136, 72))])
 def test_frame_pass_bitdepths(gpu, xo, bd, qp, size):
@@ -1429,6 +1473,7 @@ def test_frame_pass_kernel_steps_match_run(gpu, xo, kw, form):
     clip = synth.SyntheticClip(pw, ph, bd)
     fps = [pipeline.FramePass(ctx, pw, ph, bd, qp=32, **kw) for _ in range(2)]
     assert fps[0].form == form
+    assert fps[1]._args().form == api.FP_FORM_NAMES.index(form)    # run(): the one C call
     pics = [[ctx.picture(pw, ph, bd) for _ in range(2)] for _ in fps]     # ref, rec per chain
     O = ctx.picture(pw, ph, bd)
     ref_host = pad_planes(clip.frame(0), bd)
@@ -1473,6 +1518,88 @@ def test_frame_pass_kernel_steps_match_run(gpu, xo, kw, form):
         for q in p:
             q.destroy()
     O.destroy()
+
+
+# what each form needs (include/xvcgpu.h): the fields a refused block lacks, one at a time
+_FORM_NEEDS = {
+    "recon_from_me": (dict(), []),
+    "fwd_from_me": (dict(rdoq=True), ["d_rdoq_params", "d_rdoq_contexts", "d_tx", "d_coeffs",
+                                      "d_levels", "d_level_off", "d_nnz"]),
+    "fwd_transform": (dict(cu=32, rdoq=True), [
+        "pred", "d_rdoq_params", "d_rdoq_contexts", "d_tx", "d_coeffs", "d_levels",
+        "d_level_off", "d_nnz", "d_luma_tx_index"]),
+    "residual": (dict(fused=False), ["pred", "d_tx", "d_luma_tx_index"]),
+    "residual_rdoq": (dict(fused=False, rdoq=True), ["pred", "d_tx", "d_luma_tx_index",
+                                                     "d_rdoq_params", "d_rdoq_contexts"]),
+}
+
+
+def test_refused_frame_pass_launches_nothing(gpu):
+    """Every block its form cannot run is XVCGPU_INVALID_ARGUMENT before the first launch:
+    search results, counts, CU records and the reconstruction keep their poison."""
+    import ctypes as C
+    api, ctx = gpu
+    from xvc_amd import pipeline
+    pw, ph, bd = 64, 64, 10
+    O, R, Rec = (ctx.picture(pw, ph, bd) for _ in range(3))
+    rng = np.random.default_rng(3)
+    planes = lambda: pad_planes([rng.integers(0, 1 << bd, (ph >> (c > 0), pw >> (c > 0)))
+                                 .astype(np.uint16) for c in range(3)], bd)
+    O.upload(planes(), BL)
+    R.upload(planes(), BL)
+    rec_poison = planes()
+    Rec.upload(rec_poison, BL)
+    all_phases = 31
+
+    def refused(fp, tag, planned=False, **fields):
+        bufs = (fp.d_res, fp.d_nnz, fp.d_cus)
+        sizes = (api.MERES_DTYPE.itemsize * fp.desc.n_cus, 4 * len(fp.desc.tx),
+                 api.CU_DTYPE.itemsize * fp.desc.n_cus_total)
+        for b, n in zip(bufs, sizes):
+            ctx.h2d(b.ptr, np.full(n, 0xa5, np.uint8))
+        a = fp._call_args(O, R, Rec)
+        for k, v in fields.items():
+            setattr(a, k, v)
+        if planned:
+            st = ctx.lib.xvcgpu_frame_pass_planned(ctx.h, C.byref(a), fp.plan.h, all_phases)
+        else:
+            st = ctx.lib.xvcgpu_frame_pass(ctx.h, C.byref(a), all_phases)
+        assert st == 10, (tag, fields, st)          # XVCGPU_INVALID_ARGUMENT
+        ctx.sync()
+        for b, n in zip(bufs, sizes):
+            assert (b.to_array(np.uint8, n) == 0xa5).all(), (tag, fields)
+        got = Rec.download(BL)
+        for c in range(3):
+            assert np.array_equal(got[c], rec_poison[c]), (tag, fields, c)
+
+    for form, (kw, needs) in _FORM_NEEDS.items():
+        fp = pipeline.FramePass(ctx, pw, ph, bd, qp=32, **kw)
+        assert fp.form == form and fp.fused_tail
+        assert fp.desc.n_cus == (4 if kw.get("cu") == 32 else 16)
+        for field in needs:
+            refused(fp, form, **{field: None})
+        refused(fp, form, form=0)
+        refused(fp, form, form=len(api.FP_FORM_NAMES))
+        if form == "fwd_from_me":
+            refused(fp, form, max_block_size=32)
+            refused(fp, form, n_tx=len(fp.desc.tx) - 1)
+        if form == "residual":      # QuantFast: RDOQ parameters do not belong to it
+            q = pipeline.FramePass(ctx, pw, ph, bd, qp=32, fused=False, rdoq=True)
+            refused(fp, form, d_rdoq_params=q.d_rdoq_prm.ptr, d_rdoq_contexts=q.d_rdoq_ctx.ptr)
+            q.destroy()
+        if form == "recon_from_me":
+            refused(fp, form, max_block_size=32)
+        fp.destroy()
+    # a plan that holds 4x4 CUs under a form whose kernels take a CU whole
+    parts = [p for p in pipeline.cu_partition(pw, ph, 16) if p[:2] != (0, 0)]
+    parts = [(0, 0, 4, 4), (4, 0, 4, 4), (0, 4, 4, 4), (4, 4, 4, 4), (8, 0, 8, 8), (0, 8, 8, 8),
+             (8, 8, 8, 8)] + parts
+    fp = pipeline.FramePass(ctx, pw, ph, bd, qp=32, partition=parts)
+    assert fp.form == "residual" and fp.desc.cu_size == 16
+    refused(fp, "plan", planned=True, form=api.FP_FORM_NAMES.index("recon_from_me"))
+    fp.destroy()
+    for p in (O, R, Rec):
+        p.destroy()
 
 
 @pytest.mark.parametrize("cu", [8, 32, 64])

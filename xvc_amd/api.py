@@ -147,10 +147,14 @@ class FramePassArgs(C.Structure):
                 ("pred", C.c_void_p), ("d_tx", C.c_void_p), ("d_level_off", C.c_void_p),
                 ("d_luma_tx_index", C.c_void_p), ("d_coeffs", C.c_void_p),
                 ("d_levels", C.c_void_p), ("n_tx", C.c_int32), ("n_coeffs", C.c_uint32),
-                ("scratch_rec", C.c_void_p), ("tx_four_lane_only", C.c_int32), ("me_shape", C.c_int32)]
+                ("scratch_rec", C.c_void_p), ("tx_four_lane_only", C.c_int32), ("me_shape", C.c_int32),
+                ("form", C.c_int32)]
 
 
 FP_ENCODE, FP_DEBLOCK_V, FP_DEBLOCK_H, FP_PAD, FP_SSD = 1, 2, 4, 8, 16
+# FramePassArgs.form: XVC_FP_FORM_* is the index (0: none; include/xvcgpu_types.h)
+FP_FORM_NAMES = (None, "recon_from_me", "fwd_from_me", "fwd_transform", "residual",
+                 "residual_rdoq")
 
 # bins of a search plan (XVCGPU_ME_PLAN_*, include/xvcgpu_types.h)
 ME_PLAN_BIN_NAMES = ("16x16", "16x8", "8x8", "other16", "c32", "c64_team", "c64_wave",

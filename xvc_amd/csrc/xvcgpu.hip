@@ -197,6 +197,16 @@ void launch_residual_rdoq(xvcgpu_ctx *ctx, const PicView &o, const PicView &p,
                        xvcgpu_tx_layout(), d_ctx, d_prm);
 }
 
+// xvcgpu_frame_pass_multi: one kernel's argument block for n pictures,
+// fill(picture, its context, its slot)
+template <typename T, typename F>
+MultiArgs<T> multi_args(xvcgpu_ctx *const *ctxs, const xvcgpu_frame_pass_args *const *args, int n,
+                        F fill) {
+  MultiArgs<T> m;
+  for (int i = 0; i < n; i++) fill(args[i], ctxs[i], m.a[i]);
+  return m;
+}
+
 }  // namespace
 
 extern "C" {
@@ -783,6 +793,18 @@ static dim3 me2_grid(int n, int waves) {
   return dim3((n_wg + 7) / 8 * 8);
 }
 
+// the search's block class: the smallest of 16 / 32 / 64 that holds max_block_size
+static int me_class_of(int max_block_size) {
+  return max_block_size > 32 ? 64 : (max_block_size > 16 ? 32 : 16);
+}
+
+// A context's next full-pel search rotates its three straggler-first records (k_me2.h).
+// The epoch only matters modulo 3 and is kept there: no overflow, slot indices always 0..2
+static Me2Sched me_sched_next(xvcgpu_ctx *ctx) {
+  const int e = ctx->me_epoch = (ctx->me_epoch + 1) % 3;
+  return Me2Sched{ctx->d_me_rot + e, ctx->d_me_rot + (e + 1) % 3, ctx->d_me_rot + (e + 2) % 3};
+}
+
 xvcgpu_status xvcgpu_me_search_sized(xvcgpu_ctx *ctx, const xvcgpu_picture *orig,
                                      const xvcgpu_picture *ref, int flags,
                                      const xvcgpu_me_block *d_blocks, int n,
@@ -803,14 +825,7 @@ xvcgpu_status xvcgpu_me_search_sized(xvcgpu_ctx *ctx, const xvcgpu_picture *orig
   // latency-bound full-pel search overlap waves in the VALU-bound sub-pel
   // search on the same SIMD).
   Me2Sched sched = {nullptr, nullptr, nullptr};
-  if (flags & XVCGPU_ME_FULLPEL) {  // rotate the three records (k_me2.h)
-    // the epoch only ever matters modulo 3: keep it there (no overflow after
-    // 2^31 searches, slot indices always 0..2)
-    const int e = ctx->me_epoch = (ctx->me_epoch + 1) % 3;
-    sched.use = ctx->d_me_rot + e % 3;
-    sched.record = ctx->d_me_rot + (e + 1) % 3;
-    sched.clear = ctx->d_me_rot + (e + 2) % 3;
-  }
+  if (flags & XVCGPU_ME_FULLPEL) sched = me_sched_next(ctx);
   const bool lic_jobs = (flags & XVCGPU_ME_LIC_JOBS) != 0;
   // (the caller's word only counts where it can be kept: both phases, the 16 class alone)
   const bool only_sq16 = (flags & XVCGPU_ME_ONLY_SQ16) && (flags & 3) == 3 && max_block_size <= 16;
@@ -818,7 +833,7 @@ xvcgpu_status xvcgpu_me_search_sized(xvcgpu_ctx *ctx, const xvcgpu_picture *orig
   hipLaunchKernelGGL((me_search_wave_kernel<MS, PH, LIC>), me2_grid(n, ME2_WAVES(MS)),  \
                      dim3(64 * ME2_WAVES(MS)), 0, ctx->stream, orig->v, ref->v,         \
                      d_blocks, n, d_results, ctx->d_tz_pattern, sched,                  \
-                     max_block_size > 32 ? 64 : (max_block_size > 16 ? 32 : 16), lic_jobs)
+                     me_class_of(max_block_size), lic_jobs)
 #define ME_LAUNCH(MS, PH) ME_LAUNCH_T(MS, PH, false)
   // jobs of CUs that try local illumination compensation (XVC_ME_USE_LIC): their
   // own instances, the two phases as two launches
@@ -829,7 +844,7 @@ xvcgpu_status xvcgpu_me_search_sized(xvcgpu_ctx *ctx, const xvcgpu_picture *orig
   } while (0)
 #define ME_LAUNCH_SQ16()                                                                \
   do {                                                                                  \
-    const int ml = max_block_size > 32 ? 64 : (max_block_size > 16 ? 32 : 16);          \
+    const int ml = me_class_of(max_block_size);                                         \
     hipLaunchKernelGGL(me_search_sq16_kernel, me2_grid(n, ME2_WAVES(16)),                \
                        dim3(64 * ME2_WAVES(16)), 0, ctx->stream, orig->v, ref->v,       \
                        d_blocks, n, d_results, ctx->d_tz_pattern, sched, ml, lic_jobs,  \
@@ -948,7 +963,7 @@ xvcgpu_status xvcgpu_me_plan_create(xvcgpu_ctx *ctx, const xvcgpu_me_block *d_bl
   if (!p) return fail(ctx, XVCGPU_OUT_OF_MEMORY, "me_plan");
   p->d_blocks = d_blocks;
   p->n = n;
-  p->max_launched = max_block_size > 32 ? 64 : (max_block_size > 16 ? 32 : 16);
+  p->max_launched = me_class_of(max_block_size);
   if (n > 0) {
     hipError_t e = hipMalloc(&p->d_order, sizeof(int) * (size_t)n);
     if (e == hipSuccess) e = hipMalloc(&p->d_offsets, sizeof(int) * (XVCGPU_ME_PLAN_BINS + 2));
@@ -999,12 +1014,7 @@ xvcgpu_status xvcgpu_me_search_planned(xvcgpu_ctx *ctx, const xvcgpu_picture *or
     return fail(ctx, XVCGPU_INVALID_ARGUMENT, "picture mismatch");
   if (plan->n == 0) return XVCGPU_OK;
   Me2Sched sched = {nullptr, nullptr, nullptr};
-  if (flags & XVCGPU_ME_FULLPEL) {  // as xvcgpu_me_search_sized
-    const int e = ctx->me_epoch = (ctx->me_epoch + 1) % 3;
-    sched.use = ctx->d_me_rot + e % 3;
-    sched.record = ctx->d_me_rot + (e + 1) % 3;
-    sched.clear = ctx->d_me_rot + (e + 2) % 3;
-  }
+  if (flags & XVCGPU_ME_FULLPEL) sched = me_sched_next(ctx);
   const int *first = plan->first;
   const int ph = flags & 3;
   // The straggler-first record (k_me2.h) counts positions inside one launch's job list: it
@@ -1219,7 +1229,7 @@ static xvcgpu_status bipred_search_launch(xvcgpu_ctx *ctx, const xvcgpu_picture 
     return fail(ctx, XVCGPU_INVALID_ARGUMENT, "picture mismatch");
   if (n == 0) return XVCGPU_OK;
   const dim3 grid((n + 7) / 8 * 8);
-  const int bi_max = max_block_size > 32 ? 64 : (max_block_size > 16 ? 32 : 16);
+  const int bi_max = me_class_of(max_block_size);
 #define BI_LAUNCH(MS)                                                                        \
   do {                                                                                       \
     if (rec)                                                                                 \
@@ -2450,36 +2460,157 @@ xvcgpu_status xvcgpu_intra_select_modes(xvcgpu_ctx *ctx, const uint32_t *d_dist,
 static const int kFramePassAll =
     XVC_FP_ENCODE | XVC_FP_DEBLOCK_V | XVC_FP_DEBLOCK_H | XVC_FP_PAD | XVC_FP_SSD;
 
-// All phases over a whole picture of a size the fused tail (k_tail.h) covers, with its
-// scratch picture: the pass can end with that one launch instead of five (a->rec non-null)
-static bool whole_picture_pass(const xvcgpu_frame_pass_args *a, int phases) {
-  return a->scratch_rec && (phases & kFramePassAll) == kFramePassAll && a->n_cus > 0 &&
-         a->n_cus == a->n_cus_total && a->db_y_begin == 0 && a->db_y_end >= a->rec->h &&
-         a->dbh_y_end >= a->rec->h && a->ssd_y_begin == 0 && a->ssd_y_end >= a->rec->h &&
-         !(a->rec->w & 7) && !(a->rec->h & 7);
+// What a call runs (frame_pass_resolve): form 0 = no search, nothing behind it; fused_tail:
+// the form reconstructs into scratch_rec and one launch ends the pass; tail_on_hi: inverse
+// transform and that launch on ctx->hi_stream
+struct FramePassForm {
+  int form;
+  bool fused_tail, tail_on_hi;
+};
+
+// The form the caller names checked against what it can run (the table in xvcgpu.h): every
+// refusal names the field and happens here, before anything is enqueued.  plan: null = none
+static xvcgpu_status frame_pass_resolve(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_args *a,
+                                        int phases, const xvcgpu_me_plan *plan,
+                                        FramePassForm *r) {
+  if (!ctx || !a || !a->rec) return XVCGPU_INVALID_ARGUMENT;
+  // All phases over a whole picture of a size the fused tail (k_tail.h) covers, with its
+  // scratch picture: the pass can end with that one launch instead of five.  (It covers CUs
+  // without a side of 4: a plan that holds one makes the pass end with the separate launches)
+  const bool whole = a->scratch_rec && (phases & kFramePassAll) == kFramePassAll &&
+                     a->n_cus > 0 && a->n_cus == a->n_cus_total && a->db_y_begin == 0 &&
+                     a->db_y_end >= a->rec->h && a->dbh_y_end >= a->rec->h &&
+                     a->ssd_y_begin == 0 && a->ssd_y_end >= a->rec->h &&
+                     !(a->rec->w & 7) && !(a->rec->h & 7);
+  *r = {0, whole && !(plan && plan->n_small() > 0), false};
+  if (!(phases & XVC_FP_ENCODE) || a->n_cus <= 0) return XVCGPU_OK;
+  const int form = a->form;
+#define FP_NEED(cond, what) \
+  if (!(cond)) return fail(ctx, XVCGPU_INVALID_ARGUMENT, "frame_pass: " what)
+  FP_NEED(form >= XVC_FP_FORM_RECON_FROM_ME && form <= XVC_FP_FORM_RESIDUAL_RDOQ,
+          "form is not one of XVC_FP_FORM_*");
+  FP_NEED(a->orig && a->ref && a->d_me && a->d_results, "orig, ref, d_me and d_results");
+  const bool rdoq = a->d_rdoq_params != nullptr;
+  FP_NEED(!rdoq || a->d_rdoq_contexts, "d_rdoq_params without d_rdoq_contexts");
+  if (form == XVC_FP_FORM_RECON_FROM_ME || form == XVC_FP_FORM_FWD_FROM_ME) {
+    // the kernels that take a CU whole hold CUs of 8 ... 16 samples a side; the plan
+    // knows whether every job is one
+    FP_NEED(a->max_block_size <= 16, "this form needs max_block_size <= 16");
+    FP_NEED(!(plan && plan->n_small() > 0), "this form needs a plan without a CU side below 8");
+  } else {   // the prediction picture and the residual pipeline behind it
+    FP_NEED(a->pred && a->d_luma_tx_index, "this form needs pred and d_luma_tx_index");
+  }
+  if (form != XVC_FP_FORM_RECON_FROM_ME)
+    FP_NEED(a->d_tx && a->d_nnz && a->d_cus_own, "this form needs d_tx, d_nnz and d_cus_own");
+  if (form == XVC_FP_FORM_FWD_FROM_ME || form == XVC_FP_FORM_FWD_TRANSFORM) {
+    FP_NEED(rdoq, "this form needs d_rdoq_params and d_rdoq_contexts");
+    FP_NEED(a->d_coeffs && a->d_levels && a->d_level_off,
+            "this form needs d_coeffs, d_levels and d_level_off");
+  }
+  if (form == XVC_FP_FORM_FWD_FROM_ME)   // transform blocks in CU order: 3 * cu + comp
+    FP_NEED(a->n_tx == 3 * a->n_cus, "fwd_from_me needs n_tx == 3 * n_cus");
+  if (form == XVC_FP_FORM_RESIDUAL) FP_NEED(!rdoq, "residual is QuantFast: no d_rdoq_params");
+  if (form == XVC_FP_FORM_RESIDUAL_RDOQ) FP_NEED(rdoq, "residual_rdoq needs d_rdoq_params");
+#undef FP_NEED
+  r->form = form;
+  // the rest of the pass - inverse transform and the fused tail, two short kernels - on the
+  // high-priority stream: beside other pictures' searches (long-lived waves on every CU)
+  // their workgroups otherwise wait for slots many times their own duration
+  // (profiles/r03_bench_4320p_kernel_stats.csv: the tail 2152 us in flight against 118 alone)
+  r->tail_on_hi = ctx->hi_stream && r->fused_tail && form == XVC_FP_FORM_FWD_FROM_ME;
+  return XVCGPU_OK;
 }
 
-// plan: null = xvcgpu_frame_pass; else xvcgpu_frame_pass_planned
+// The forms; rec: where the unfiltered reconstruction goes
+static xvcgpu_status fp_recon_from_me(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_args *a,
+                                      xvcgpu_picture *rec) {
+  if (a->d_rdoq_params)
+    return xvcgpu_recon_from_me_rdoq(ctx, a->orig, a->ref, rec, a->d_me, a->d_results, a->n_cus,
+                                     a->qp_y, a->qp_c, 0, a->ref_poc, a->d_nnz, a->d_cus_own,
+                                     a->d_rdoq_contexts, a->d_rdoq_params);
+  return xvcgpu_recon_from_me(ctx, a->orig, a->ref, rec, a->d_me, a->d_results, a->n_cus,
+                              a->qp_y, a->qp_c, 0, a->ref_poc, a->d_nnz, a->d_cus_own);
+}
+
+// the packed quantiser, the caller's word about its blocks held for this call's batch
+static xvcgpu_status fp_quant_rdo(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_args *a,
+                                  bool classified) {
+  const int four_before = ctx->rdoq_four_lane_only;
+  xvcgpu_status st = XVCGPU_OK;
+  if (a->tx_four_lane_only && !four_before) st = xvcgpu_quant_rdo_set_four_lane_only(ctx, 1);
+  if (st == XVCGPU_OK)
+    st = classified
+             ? xvcgpu_quant_rdo_classified_batch(ctx, a->rec->bd, a->d_tx, a->n_tx, a->d_coeffs,
+                                                 a->d_level_off, a->n_coeffs, a->d_levels,
+                                                 a->d_nnz, a->d_rdoq_contexts, a->d_rdoq_params,
+                                                 a->d_cus_own)
+             : xvcgpu_quant_rdo_batch(ctx, a->rec->bd, a->d_tx, a->n_tx, a->d_coeffs,
+                                      a->d_level_off, a->n_coeffs, a->d_levels, a->d_nnz,
+                                      a->d_rdoq_contexts, a->d_rdoq_params);
+  ctx->rdoq_four_lane_only = four_before;
+  return st;
+}
+
+// Prediction + forward transform in one kernel: the prediction goes straight into the
+// reconstruction's picture (the inverse half then works in place and skips the blocks
+// without levels), the kernel classifies the blocks for the quantiser on the way, proves
+// the blocks it can all zero (k_rdoq.h) and writes the CU records.  *main_stream: set
+// where the pass goes on on ctx->hi_stream
+static xvcgpu_status fp_fwd_from_me(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_args *a,
+                                    xvcgpu_picture *rec, bool tail_on_hi,
+                                    hipStream_t *main_stream) {
+  xvcgpu_status st = xvcgpu_fwd_from_me_classify_prove(
+      ctx, a->orig, a->ref, rec, a->d_me, a->d_results, a->n_cus, a->qp_y, a->qp_c, a->ref_poc,
+      a->d_coeffs, a->d_level_off, a->n_coeffs, a->d_levels, a->d_nnz, a->d_cus_own,
+      a->d_rdoq_contexts, a->d_rdoq_params);
+  if (st == XVCGPU_OK) st = fp_quant_rdo(ctx, a, true);
+  if (st != XVCGPU_OK) return st;
+  if (tail_on_hi) {
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_hi_in, ctx->stream));
+    HIP_TRY(ctx, hipStreamWaitEvent(ctx->hi_stream, ctx->ev_hi_in, 0));
+    *main_stream = ctx->stream;
+    ctx->stream = ctx->hi_stream;
+  }
+  // blocks 3 * cu + comp, CUs up to 16x16: the U and V blocks of a CU share a wave
+  return xvcgpu_inv_transform_cu_order(ctx, rec, a->d_tx, a->n_cus, a->d_levels,
+                                       a->d_level_off, a->d_nnz);
+}
+
+// CUs of any size: the prediction picture, the form's residual pipeline over the transform
+// blocks (whole with QuantFast or RDOQ, or split around the packed quantiser), the CU records
+static xvcgpu_status fp_from_pred(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_args *a,
+                                  xvcgpu_picture *rec, int form) {
+  xvcgpu_status st = xvcgpu_mc_from_me(ctx, a->ref, a->pred, a->d_me, a->d_results, a->n_cus);
+  if (st != XVCGPU_OK) return st;
+  if (form == XVC_FP_FORM_RESIDUAL)
+    st = xvcgpu_residual_batch(ctx, a->orig, a->pred, rec, a->d_tx, a->n_tx, a->d_levels,
+                               a->d_level_off, a->d_nnz);
+  else if (form == XVC_FP_FORM_RESIDUAL_RDOQ)
+    st = xvcgpu_residual_rdoq_batch(ctx, a->orig, a->pred, rec, a->d_tx, a->n_tx, a->d_levels,
+                                    a->d_level_off, a->d_nnz, a->d_rdoq_contexts,
+                                    a->d_rdoq_params);
+  else {
+    st = xvcgpu_fwd_transform_batch(ctx, a->orig, a->pred, a->d_tx, a->n_tx, a->d_coeffs,
+                                    a->d_level_off);
+    if (st == XVCGPU_OK) st = fp_quant_rdo(ctx, a, false);
+    if (st == XVCGPU_OK)
+      st = xvcgpu_inv_transform_batch(ctx, a->pred, rec, a->d_tx, a->n_tx, a->d_levels,
+                                      a->d_level_off, a->d_nnz);
+  }
+  if (st != XVCGPU_OK) return st;
+  return xvcgpu_cu_info_from_me(ctx, a->d_me, a->d_results, a->d_nnz, a->d_luma_tx_index,
+                                a->n_cus, a->qp_y, a->qp_c, a->ref_poc, a->d_cus_own);
+}
+
+// resolve, search, the form's launches, tail.  plan: null = xvcgpu_frame_pass
 static xvcgpu_status frame_pass_impl(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_args *a,
                                      int phases, const xvcgpu_me_plan *plan) {
-  if (!ctx || !a || !a->rec) return XVCGPU_INVALID_ARGUMENT;
-  xvcgpu_status st = XVCGPU_OK;
-  // (the fused tail covers CUs without a side of 4: a plan that holds one makes the pass
-  // end with the separate launches, whatever scratch_rec says)
-  const bool fused_tail = whole_picture_pass(a, phases) && !(plan && plan->n_small() > 0);
-  xvcgpu_picture *const rec = fused_tail ? a->scratch_rec : a->rec;
+  FramePassForm r;
+  xvcgpu_status st = frame_pass_resolve(ctx, a, phases, plan, &r);
+  if (st != XVCGPU_OK) return st;
+  xvcgpu_picture *const rec = r.fused_tail ? a->scratch_rec : a->rec;
   hipStream_t main_stream = nullptr;   // set while the pass runs on ctx->hi_stream
-  struct Back {
-    xvcgpu_ctx *c;
-    hipStream_t *m;
-    ~Back() {   // every way out: the chain continues on its own stream, after the tail
-      if (!*m) return;
-      hipEventRecord(c->ev_hi_out, c->hi_stream);
-      c->stream = *m;
-      hipStreamWaitEvent(c->stream, c->ev_hi_out, 0);
-    }
-  } back = {ctx, &main_stream};
-  if ((phases & XVC_FP_ENCODE) && a->n_cus > 0) {
+  if (r.form) {
     // the pass's jobs are the CUs of its grid: where the caller's shape word says that they
     // are (almost) all 16x16 (16x8 in the bottom row of a 1080-line picture) the search's
     // exact-shape kernel (a pass of smaller CUs must not take it: its jobs would all be left
@@ -2491,125 +2622,34 @@ static xvcgpu_status frame_pass_impl(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_ar
                     XVCGPU_ME_FULLPEL | XVCGPU_ME_SUBPEL |
                         (a->me_shape & (XVCGPU_ME_HINT_SQ16 | XVCGPU_ME_ONLY_SQ16)),
                     a->d_me, a->n_cus, a->d_results, a->max_block_size);
-    if (st != XVCGPU_OK) return st;
-    // the kernels that take a CU whole (recon_from_me, fwd_from_me) hold CUs of 8 ... 16
-    // samples a side; the plan knows whether every job is one
-    // ... and QuantFast levels (d_levels without RDOQ) are stored by the residual
-    // pipeline only: recon_from_me keeps none
-    const bool any_size =
-        plan && (a->max_block_size > 16 || plan->n_small() > 0 ||
-                 (!a->d_rdoq_params && a->d_levels && a->pred && a->d_tx && a->d_luma_tx_index));
-    if (any_size && !(a->d_rdoq_params && a->pred)) {
-      // CUs of any size (xvcgpu_frame_pass_planned): prediction picture, the residual
-      // pipeline over the transform blocks, the CU records
-      if (a->d_rdoq_params || !a->pred || !a->d_tx || !a->d_luma_tx_index)
-        return fail(ctx, XVCGPU_INVALID_ARGUMENT,
-                    "frame_pass_planned: CUs above 16x16 or with a side below 8 need pred, "
-                    "d_tx, d_luma_tx_index (QuantFast) or the packed RDOQ arguments");
-      st = xvcgpu_mc_from_me(ctx, a->ref, a->pred, a->d_me, a->d_results, a->n_cus);
-      if (st == XVCGPU_OK)
-        st = xvcgpu_residual_batch(ctx, a->orig, a->pred, rec, a->d_tx, a->n_tx, a->d_levels,
-                                   a->d_level_off, a->d_nnz);
-      if (st == XVCGPU_OK)
-        st = xvcgpu_cu_info_from_me(ctx, a->d_me, a->d_results, a->d_nnz, a->d_luma_tx_index,
-                                    a->n_cus, a->qp_y, a->qp_c, a->ref_poc, a->d_cus_own);
-    } else if (a->d_rdoq_params && a->pred) {
-      bool in_place = false, classified = false;
-      if (!any_size && a->max_block_size <= 16 && a->n_tx == 3 * a->n_cus) {
-        // prediction + forward transform in one kernel (transform blocks in CU
-        // order, Y U V each: block 3 * cu + comp)
-        // (the prediction goes straight into the reconstruction's picture: the
-        // inverse half then works in place and skips the blocks without levels)
-        // and it classifies the blocks for the quantiser on the way (the
-        // coefficients are at hand: no separate pass over all of them)
-        // ... and proves the blocks it can all zero (k_rdoq.h)
-        st = xvcgpu_fwd_from_me_classify_prove(ctx, a->orig, a->ref, rec, a->d_me, a->d_results,
-                                               a->n_cus, a->qp_y, a->qp_c, a->ref_poc,
-                                               a->d_coeffs, a->d_level_off, a->n_coeffs,
-                                               a->d_levels, a->d_nnz, a->d_cus_own,
-                                               a->d_rdoq_contexts, a->d_rdoq_params);
-        in_place = classified = true;
-      } else {
-        st = xvcgpu_mc_from_me(ctx, a->ref, a->pred, a->d_me, a->d_results, a->n_cus);
-        if (st == XVCGPU_OK)
-          st = xvcgpu_fwd_transform_batch(ctx, a->orig, a->pred, a->d_tx, a->n_tx, a->d_coeffs,
-                                          a->d_level_off);
-      }
-      // the caller's word about its blocks holds for this call's batch
-      const int four_before = ctx->rdoq_four_lane_only;
-      if (st == XVCGPU_OK && a->tx_four_lane_only && !four_before)
-        st = xvcgpu_quant_rdo_set_four_lane_only(ctx, 1);
-      if (st == XVCGPU_OK)
-        st = classified
-                 ? xvcgpu_quant_rdo_classified_batch(ctx, a->rec->bd, a->d_tx, a->n_tx,
-                                                     a->d_coeffs, a->d_level_off, a->n_coeffs,
-                                                     a->d_levels, a->d_nnz, a->d_rdoq_contexts,
-                                                     a->d_rdoq_params, a->d_cus_own)
-                 : xvcgpu_quant_rdo_batch(ctx, a->rec->bd, a->d_tx, a->n_tx, a->d_coeffs,
-                                          a->d_level_off, a->n_coeffs, a->d_levels, a->d_nnz,
-                                          a->d_rdoq_contexts, a->d_rdoq_params);
-      ctx->rdoq_four_lane_only = four_before;
-      if (st == XVCGPU_OK) {
-        if (!a->d_tx || !a->d_levels || !a->d_level_off || !a->d_nnz) {
-          st = XVCGPU_INVALID_ARGUMENT;
-        } else if (a->n_tx > 0) {
-          const PicView &pv = in_place ? rec->v : a->pred->v;
-          if (ctx->hi_stream && fused_tail && in_place) {
-            // the rest of the pass - inverse transform and the fused tail, two short
-            // kernels - on the high-priority stream: beside other pictures' searches
-            // (long-lived waves on every CU) their workgroups otherwise wait for slots
-            // many times their own duration (profiles/r03_bench_4320p_kernel_stats.csv:
-            // the tail 2152 us in flight against 118 alone)
-            HIP_TRY(ctx, hipEventRecord(ctx->ev_hi_in, ctx->stream));
-            HIP_TRY(ctx, hipStreamWaitEvent(ctx->hi_stream, ctx->ev_hi_in, 0));
-            main_stream = ctx->stream;
-            ctx->stream = ctx->hi_stream;
-          }
-          if (in_place) {
-            // blocks 3 * cu + comp, CUs up to 16x16 (the condition of in_place): the
-            // U and V blocks of a CU share a wave
-            st = xvcgpu_inv_transform_cu_order(ctx, rec, a->d_tx, a->n_cus, a->d_levels,
-                                               a->d_level_off, a->d_nnz);
-          } else {
-            launch_residual<TX_MODE_INV>(ctx, pv, pv, rec->v, a->d_tx, a->n_tx, a->d_levels,
-                                         a->d_level_off, a->d_nnz, nullptr, false);
-          }
-          CHECK_LAUNCH(ctx, "inv_transform_batch");
-        }
-      }
-      if (st == XVCGPU_OK && !(classified && a->d_cus_own))   // (else written on the way)
-        st = xvcgpu_cu_info_from_me(ctx, a->d_me, a->d_results, a->d_nnz, a->d_luma_tx_index,
-                                    a->n_cus, a->qp_y, a->qp_c, a->ref_poc, a->d_cus_own);
-    } else if (a->d_rdoq_params)
-      st = xvcgpu_recon_from_me_rdoq(ctx, a->orig, a->ref, rec, a->d_me, a->d_results,
-                                     a->n_cus, a->qp_y, a->qp_c, 0, a->ref_poc, a->d_nnz,
-                                     a->d_cus_own, a->d_rdoq_contexts, a->d_rdoq_params);
-    else
-      st = xvcgpu_recon_from_me(ctx, a->orig, a->ref, rec, a->d_me, a->d_results, a->n_cus,
-                                a->qp_y, a->qp_c, 0, a->ref_poc, a->d_nnz, a->d_cus_own);
-    if (st != XVCGPU_OK) return st;
+    if (st != XVCGPU_OK) return st;   // (nothing behind a search that was refused)
+    switch (r.form) {
+      case XVC_FP_FORM_RECON_FROM_ME: st = fp_recon_from_me(ctx, a, rec); break;
+      case XVC_FP_FORM_FWD_FROM_ME:
+        st = fp_fwd_from_me(ctx, a, rec, r.tail_on_hi, &main_stream);
+        break;
+      default: st = fp_from_pred(ctx, a, rec, r.form); break;
+    }
   }
-  if (fused_tail)
-    return xvcgpu_deblock_pad_ssd(ctx, a->scratch_rec, a->rec, a->orig, a->d_cus, a->n_cus_total,
-                                  a->d_cu_map, a->map_stride, 0, 0, 0, a->shift_bitdepth,
-                                  a->d_ssd);
-  if (phases & XVC_FP_DEBLOCK_V) {
+  if (st == XVCGPU_OK && r.fused_tail)
+    st = xvcgpu_deblock_pad_ssd(ctx, a->scratch_rec, a->rec, a->orig, a->d_cus, a->n_cus_total,
+                                a->d_cu_map, a->map_stride, 0, 0, 0, a->shift_bitdepth, a->d_ssd);
+  if (r.fused_tail) phases = 0;
+  if (st == XVCGPU_OK && (phases & XVC_FP_DEBLOCK_V))
     st = xvcgpu_deblock_rows(ctx, a->rec, a->d_cus, a->n_cus_total, a->d_cu_map, a->map_stride,
                              0, 0, 0, 4, 0, a->db_y_begin, a->db_y_end);
-    if (st != XVCGPU_OK) return st;
-  }
-  if (phases & XVC_FP_DEBLOCK_H) {
+  if (st == XVCGPU_OK && (phases & XVC_FP_DEBLOCK_H))
     st = xvcgpu_deblock_rows(ctx, a->rec, a->d_cus, a->n_cus_total, a->d_cu_map, a->map_stride,
                              0, 0, 0, 4, 1, a->db_y_begin, a->dbh_y_end);
-    if (st != XVCGPU_OK) return st;
-  }
-  if (phases & XVC_FP_PAD) {
-    st = xvcgpu_pad_border(ctx, a->rec);
-    if (st != XVCGPU_OK) return st;
-  }
-  if (phases & XVC_FP_SSD)
+  if (st == XVCGPU_OK && (phases & XVC_FP_PAD)) st = xvcgpu_pad_border(ctx, a->rec);
+  if (st == XVCGPU_OK && (phases & XVC_FP_SSD))
     st = xvcgpu_picture_ssd_rows(ctx, a->orig, a->rec, 0, a->shift_bitdepth, a->ssd_y_begin,
                                  a->ssd_y_end, a->d_ssd);
+  if (main_stream) {   // every way out: the chain continues on its own stream, after the tail
+    hipEventRecord(ctx->ev_hi_out, ctx->hi_stream);
+    ctx->stream = main_stream;
+    hipStreamWaitEvent(ctx->stream, ctx->ev_hi_out, 0);
+  }
   return st;
 }
 
@@ -2623,129 +2663,125 @@ xvcgpu_status xvcgpu_frame_pass_planned(xvcgpu_ctx *ctx, const xvcgpu_frame_pass
   if (!ctx || !a || !plan || plan->n != a->n_cus || plan->d_blocks != a->d_me)
     return XVCGPU_INVALID_ARGUMENT;
   // (a plan of a smaller class would answer this pass's larger CUs as unsupported)
-  if (plan->max_launched != (a->max_block_size > 32 ? 64 : (a->max_block_size > 16 ? 32 : 16)))
+  if (plan->max_launched != me_class_of(a->max_block_size))
     return fail(ctx, XVCGPU_INVALID_ARGUMENT,
                 "frame_pass_planned: the plan was made for another max_block_size class");
   return frame_pass_impl(ctx, a, phases, plan);
 }
 
 /* ---- several pictures per call: every kernel launched once for all of them ---- */
+// Picture by picture.  The batched form runs everything on ctxs[0]'s stream; so that a
+// caller sees ONE ordering rule either way, a picture whose context has another stream is
+// fenced into that one: it starts after what it holds now, which continues only after it.
+static xvcgpu_status frame_pass_each(xvcgpu_ctx *const *ctxs,
+                                     const xvcgpu_frame_pass_args *const *args, int n,
+                                     int phases) {
+  xvcgpu_ctx *ctx = ctxs[0];
+  for (int i = 0; i < n; i++) {
+    if (!ctxs[i] || !args[i]) return XVCGPU_INVALID_ARGUMENT;
+    const bool foreign = ctxs[i]->stream != ctx->stream;
+    hipEvent_t before = nullptr, after = nullptr;
+    // an event belongs to the device that was current when it was created and
+    // can only be recorded on that device's streams: `before` is ctxs[0]'s,
+    // `after` the picture's own (contexts on another device are exactly what
+    // sends a call down this path); both are destroyed on every way out
+    auto fence_in = [&]() -> hipError_t {
+      hipError_t e = hipSetDevice(ctx->device);
+      if (e == hipSuccess) e = hipEventCreateWithFlags(&before, hipEventDisableTiming);
+      if (e == hipSuccess) e = hipEventRecord(before, ctx->stream);
+      if (e == hipSuccess) e = hipSetDevice(ctxs[i]->device);
+      if (e == hipSuccess) e = hipEventCreateWithFlags(&after, hipEventDisableTiming);
+      if (e == hipSuccess) e = hipStreamWaitEvent(ctxs[i]->stream, before, 0);
+      return e;
+    };
+    auto fence_out = [&]() -> hipError_t {
+      hipError_t e = hipSetDevice(ctxs[i]->device);
+      if (e == hipSuccess) e = hipEventRecord(after, ctxs[i]->stream);
+      if (e == hipSuccess) e = hipSetDevice(ctx->device);
+      if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, after, 0);
+      return e;
+    };
+    hipError_t herr = foreign ? fence_in() : hipSuccess;
+    xvcgpu_status st = XVCGPU_OK;
+    if (herr == hipSuccess) {
+      st = xvcgpu_frame_pass(ctxs[i], args[i], phases);
+      if (foreign && st == XVCGPU_OK) herr = fence_out();
+    }
+    if (before) hipEventDestroy(before);   // released when the recorded work has passed them
+    if (after) hipEventDestroy(after);
+    HIP_TRY(ctx, herr);
+    if (st != XVCGPU_OK) return st;
+  }
+  return XVCGPU_OK;
+}
+
 xvcgpu_status xvcgpu_frame_pass_multi(xvcgpu_ctx *const *ctxs,
                                       const xvcgpu_frame_pass_args *const *args, int n,
                                       int phases) {
   if (!ctxs || !args || n < 1 || !ctxs[0]) return XVCGPU_INVALID_ARGUMENT;
   xvcgpu_ctx *ctx = ctxs[0];
-  // the form the launches below cover: whole pictures of CUs up to 16x16 (and at
-  // least 8x8: scratch_rec), all phases, the packed RDOQ pipeline or QuantFast;
-  // anything else runs picture by picture, each on its own context
-  bool batched = n >= 2 && n <= XVC_MULTI_MAX && (phases & kFramePassAll) == kFramePassAll;
+  // the forms the launches below cover: whole pictures with the fused tail, every one
+  // fwd_from_me or every one recon_from_me with QuantFast; anything else (a block its own
+  // call would refuse too) runs picture by picture, each on its own context
+  bool batched = n >= 2 && n <= XVC_MULTI_MAX;
+  int form = 0;
   for (int i = 0; i < n && batched; i++) {
     const xvcgpu_frame_pass_args *a = args[i];
-    if (!ctxs[i] || !a || !a->orig || !a->ref || !a->rec) return XVCGPU_INVALID_ARGUMENT;
-    const bool rdoq_packed = a->d_rdoq_params && a->pred && a->n_tx == 3 * a->n_cus;
-    const bool fast = !a->d_rdoq_params;
-    batched = whole_picture_pass(a, phases) && a->max_block_size <= 16 && (rdoq_packed || fast) &&
-              (rdoq_packed == (args[0]->d_rdoq_params != nullptr)) &&
-              a->rec->w == args[0]->rec->w && a->rec->h == args[0]->rec->h &&
-              a->rec->bd == args[0]->rec->bd && ctxs[i]->device == ctx->device &&
-              // what the launches below dereference (the single-picture path
-              // validates the same pointers, so a picture missing one goes there)
-              a->d_me && a->d_results && a->d_cus && a->d_cu_map && a->d_ssd && a->d_nnz &&
-              a->d_cus_own &&
-              (!rdoq_packed || (a->d_tx && a->d_levels && a->d_coeffs && a->d_level_off &&
-                                a->d_luma_tx_index && a->d_rdoq_contexts));
+    FramePassForm r;
+    if (!ctxs[i] || !a) return XVCGPU_INVALID_ARGUMENT;
+    batched = frame_pass_resolve(ctxs[i], a, phases, nullptr, &r) == XVCGPU_OK && r.fused_tail &&
+              (r.form == XVC_FP_FORM_FWD_FROM_ME ||
+               (r.form == XVC_FP_FORM_RECON_FROM_ME && !a->d_rdoq_params)) &&
+              (i == 0 || r.form == form) && a->rec->w == args[0]->rec->w &&
+              a->rec->h == args[0]->rec->h && a->rec->bd == args[0]->rec->bd &&
+              ctxs[i]->device == ctx->device &&
+              // what the launches below dereference beyond the form's own fields (a picture
+              // missing one goes to the single call, which refuses it)
+              a->d_cus && a->d_cu_map && a->d_ssd && a->d_nnz && a->d_cus_own &&
+              (r.form != XVC_FP_FORM_FWD_FROM_ME || a->d_luma_tx_index);
+    form = r.form;
   }
-  if (!batched) {
-    // Picture by picture.  The batched form runs everything on ctxs[0]'s
-    // stream; so that a caller sees ONE ordering rule whichever form a call
-    // takes, a picture whose context has another stream is fenced into that
-    // stream: it starts after what ctxs[0]'s stream holds now, and ctxs[0]'s
-    // stream continues only after it.
-    for (int i = 0; i < n; i++) {
-      if (!ctxs[i] || !args[i]) return XVCGPU_INVALID_ARGUMENT;
-      const bool foreign = ctxs[i]->stream != ctx->stream;
-      hipEvent_t before = nullptr, after = nullptr;
-      // an event belongs to the device that was current when it was created and
-      // can only be recorded on that device's streams: `before` is ctxs[0]'s,
-      // `after` the picture's own (contexts on another device are exactly what
-      // sends a call down this path); both are destroyed on every way out
-      auto fence_in = [&]() -> hipError_t {
-        hipError_t e = hipSetDevice(ctx->device);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&before, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventRecord(before, ctx->stream);
-        if (e == hipSuccess) e = hipSetDevice(ctxs[i]->device);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&after, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipStreamWaitEvent(ctxs[i]->stream, before, 0);
-        return e;
-      };
-      auto fence_out = [&]() -> hipError_t {
-        hipError_t e = hipSetDevice(ctxs[i]->device);
-        if (e == hipSuccess) e = hipEventRecord(after, ctxs[i]->stream);
-        if (e == hipSuccess) e = hipSetDevice(ctx->device);
-        if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, after, 0);
-        return e;
-      };
-      hipError_t herr = foreign ? fence_in() : hipSuccess;
-      xvcgpu_status st = XVCGPU_OK;
-      if (herr == hipSuccess) {
-        st = xvcgpu_frame_pass(ctxs[i], args[i], phases);
-        if (foreign && st == XVCGPU_OK) herr = fence_out();
-      }
-      if (before) hipEventDestroy(before);   // released when the recorded work has passed them
-      if (after) hipEventDestroy(after);
-      HIP_TRY(ctx, herr);
-      if (st != XVCGPU_OK) return st;
-    }
-    return XVCGPU_OK;
-  }
-  const bool rdoq = args[0]->d_rdoq_params != nullptr;
-  const dim3 one(1);
+  if (!batched) return frame_pass_each(ctxs, args, n, phases);
+  const bool rdoq = form == XVC_FP_FORM_FWD_FROM_ME;
   int max_cus = 0, max_tx = 0;
   for (int i = 0; i < n; i++) {
     max_cus = std::max(max_cus, (int)args[i]->n_cus);
     max_tx = std::max(max_tx, (int)args[i]->n_tx);
   }
   const TxTableLayout lay = xvcgpu_tx_layout();
+  typedef const xvcgpu_frame_pass_args *Args;
   // 1. the motion searches
   {
-    MultiArgs<MeMultiArgs> m;
-    for (int i = 0; i < n; i++) {
-      const xvcgpu_frame_pass_args *a = args[i];
-      xvcgpu_ctx *c = ctxs[i];
-      const int e = c->me_epoch = (c->me_epoch + 1) % 3;   // the picture's own rotation records
-      MeMultiArgs &k = m.a[i];
-      k.orig = a->orig->v;
-      k.ref = a->ref->v;
-      k.blocks = a->d_me;
-      k.n = a->n_cus;
-      k.results = a->d_results;
-      k.sched.use = c->d_me_rot + e % 3;
-      k.sched.record = c->d_me_rot + (e + 1) % 3;
-      k.sched.clear = c->d_me_rot + (e + 2) % 3;
-    }
+    const MultiArgs<MeMultiArgs> m = multi_args<MeMultiArgs>(
+        ctxs, args, n, [](Args a, xvcgpu_ctx *c, MeMultiArgs &k) {
+          k.orig = a->orig->v;
+          k.ref = a->ref->v;
+          k.blocks = a->d_me;
+          k.n = a->n_cus;
+          k.results = a->d_results;
+          k.sched = me_sched_next(c);   // the picture's own rotation records
+        });
     hipLaunchKernelGGL(me_search_multi_kernel, dim3(me2_grid(max_cus, ME2_WAVES(16)).x, n),
                        dim3(64 * ME2_WAVES(16)), 0, ctx->stream, m, ctx->d_tz_pattern);
   }
   // 2. prediction + transform (RDOQ: forward half only, the quantiser follows)
   {
-    MultiArgs<ReconMultiArgs> m;
-    for (int i = 0; i < n; i++) {
-      const xvcgpu_frame_pass_args *a = args[i];
-      ReconMultiArgs &k = m.a[i];
-      k.orig = a->orig->v;
-      k.ref = a->ref->v;
-      k.rec = a->scratch_rec->v;   // (RDOQ: the prediction; the inverse half works in place)
-      k.blocks = a->d_me;
-      k.results = a->d_results;
-      k.n_cus = a->n_cus;
-      k.qp_y = rdoq ? 0 : a->qp_y;
-      k.qp_c = rdoq ? 0 : a->qp_c;
-      k.ref_poc = rdoq ? 0 : a->ref_poc;
-      k.nnz_out = rdoq ? nullptr : a->d_nnz;
-      k.cus = rdoq ? nullptr : a->d_cus_own;
-      k.coeffs = rdoq ? a->d_coeffs : nullptr;
-      k.coeff_off = rdoq ? a->d_level_off : nullptr;
-    }
+    const MultiArgs<ReconMultiArgs> m = multi_args<ReconMultiArgs>(
+        ctxs, args, n, [rdoq](Args a, xvcgpu_ctx *, ReconMultiArgs &k) {
+          k.orig = a->orig->v;
+          k.ref = a->ref->v;
+          k.rec = a->scratch_rec->v;   // (RDOQ: the prediction; the inverse half works in place)
+          k.blocks = a->d_me;
+          k.results = a->d_results;
+          k.n_cus = a->n_cus;
+          k.qp_y = rdoq ? 0 : a->qp_y;
+          k.qp_c = rdoq ? 0 : a->qp_c;
+          k.ref_poc = rdoq ? 0 : a->ref_poc;
+          k.nnz_out = rdoq ? nullptr : a->d_nnz;
+          k.cus = rdoq ? nullptr : a->d_cus_own;
+          k.coeffs = rdoq ? a->d_coeffs : nullptr;
+          k.coeff_off = rdoq ? a->d_level_off : nullptr;
+        });
     const int n_wg = (2 * max_cus + 3) / 4;
     const dim3 grid((n_wg + 7) / 8 * 8, n);
     if (rdoq)
@@ -2757,26 +2793,25 @@ xvcgpu_status xvcgpu_frame_pass_multi(xvcgpu_ctx *const *ctxs,
   }
   if (rdoq) {
     // 3. the quantiser: classification, class lists, the walks
-    MultiArgs<RdoqMultiArgs> q;
     for (int i = 0; i < n; i++) {
-      const xvcgpu_frame_pass_args *a = args[i];
-      xvcgpu_ctx *c = ctxs[i];
-      const xvcgpu_status st = ensure_rdoq_scratch(c, a->n_tx, a->n_coeffs);
+      const xvcgpu_status st = ensure_rdoq_scratch(ctxs[i], args[i]->n_tx, args[i]->n_coeffs);
       if (st != XVCGPU_OK) return st;
-      const int cap = c->rdoq_lists_cap;
-      RdoqMultiArgs &k = q.a[i];
-      k.blocks = a->d_tx;
-      k.n = a->n_tx;
-      k.coeffs = a->d_coeffs;
-      k.d_off = a->d_level_off;
-      k.levels = a->d_levels;
-      k.nnz_out = a->d_nnz;
-      k.l.count = c->d_rdoq_lists;
-      for (int cl = 0; cl < 3; cl++) k.l.list[cl] = c->d_rdoq_lists + 4 + (size_t)cl * cap;
-      k.l.cls = reinterpret_cast<signed char *>(c->d_rdoq_lists + 4 + 3 * (size_t)cap);
-      k.rq_ctx = a->d_rdoq_contexts;
-      k.rq_prm = a->d_rdoq_params;
     }
+    const MultiArgs<RdoqMultiArgs> q = multi_args<RdoqMultiArgs>(
+        ctxs, args, n, [](Args a, xvcgpu_ctx *c, RdoqMultiArgs &k) {
+          const int cap = c->rdoq_lists_cap;
+          k.blocks = a->d_tx;
+          k.n = a->n_tx;
+          k.coeffs = a->d_coeffs;
+          k.d_off = a->d_level_off;
+          k.levels = a->d_levels;
+          k.nnz_out = a->d_nnz;
+          k.l.count = c->d_rdoq_lists;
+          for (int cl = 0; cl < 3; cl++) k.l.list[cl] = c->d_rdoq_lists + 4 + (size_t)cl * cap;
+          k.l.cls = reinterpret_cast<signed char *>(c->d_rdoq_lists + 4 + 3 * (size_t)cap);
+          k.rq_ctx = a->d_rdoq_contexts;
+          k.rq_prm = a->d_rdoq_params;
+        });
     const int bd = args[0]->rec->bd;
     hipLaunchKernelGGL(rdoq_classify_multi_kernel, dim3((max_tx + 3) / 4, n), dim3(256), 0,
                        ctx->stream, q, bd);
@@ -2788,83 +2823,73 @@ xvcgpu_status xvcgpu_frame_pass_multi(xvcgpu_ctx *const *ctxs,
     hipLaunchKernelGGL(quant_rdo_packed_multi_kernel, dim3(g64, n), dim3(64), 0,
                        ctx->stream, q, bd);
     // 4. dequantisation + inverse transform + reconstruction
-    MultiArgs<InvMultiArgs> v;
-    for (int i = 0; i < n; i++) {
-      const xvcgpu_frame_pass_args *a = args[i];
-      InvMultiArgs &k = v.a[i];
-      k.pred = a->scratch_rec->v;
-      k.rec = a->scratch_rec->v;
-      k.blocks = a->d_tx;
-      k.n = a->n_tx;
-      k.levels = a->d_levels;
-      k.level_off = a->d_level_off;
-      k.nnz = a->d_nnz;
-    }
+    const MultiArgs<InvMultiArgs> v = multi_args<InvMultiArgs>(
+        ctxs, args, n, [](Args a, xvcgpu_ctx *, InvMultiArgs &k) {
+          k.pred = a->scratch_rec->v;
+          k.rec = a->scratch_rec->v;
+          k.blocks = a->d_tx;
+          k.n = a->n_tx;
+          k.levels = a->d_levels;
+          k.level_off = a->d_level_off;
+          k.nnz = a->d_nnz;
+        });
     const int n_wg = (max_tx + TX2_WAVES - 1) / TX2_WAVES;
     hipLaunchKernelGGL(inv_wave_multi_kernel, dim3((n_wg + 7) / 8 * 8, n), dim3(64 * TX2_WAVES), 0,
                        ctx->stream, v, ctx->d_tx_tables, ctx->d_tx_tables_t, lay);
     hipLaunchKernelGGL(inv_general_multi_kernel, dim3((max_tx + TX_THREADS - 1) / TX_THREADS, n),
                        dim3(TX_THREADS), 0, ctx->stream, v, ctx->d_tx_tables, lay);
     // 5. the CUs' deblocking records
-    MultiArgs<CuInfoMultiArgs> u;
-    for (int i = 0; i < n; i++) {
-      const xvcgpu_frame_pass_args *a = args[i];
-      CuInfoMultiArgs &k = u.a[i];
-      k.blocks = a->d_me;
-      k.results = a->d_results;
-      k.nnz = a->d_nnz;
-      k.luma_tx_index = a->d_luma_tx_index;
-      k.n = a->n_cus;
-      k.qp_y = a->qp_y;
-      k.qp_c = a->qp_c;
-      k.ref_poc = a->ref_poc;
-      k.cus = a->d_cus_own;
-    }
+    const MultiArgs<CuInfoMultiArgs> u = multi_args<CuInfoMultiArgs>(
+        ctxs, args, n, [](Args a, xvcgpu_ctx *, CuInfoMultiArgs &k) {
+          k.blocks = a->d_me;
+          k.results = a->d_results;
+          k.nnz = a->d_nnz;
+          k.luma_tx_index = a->d_luma_tx_index;
+          k.n = a->n_cus;
+          k.qp_y = a->qp_y;
+          k.qp_c = a->qp_c;
+          k.ref_poc = a->ref_poc;
+          k.cus = a->d_cus_own;
+        });
     hipLaunchKernelGGL(cu_info_multi_kernel, dim3((max_cus + 255) / 256, n), dim3(256), 0,
                        ctx->stream, u);
   }
   // 6. deblocking, border, SSD parts
   {
-    MultiArgs<TailMultiArgs> t;
-    int max_tiles = 0;
+    const int tiles = tail_tiles(args[0]->rec->w, args[0]->rec->h);   // one size for all
     for (int i = 0; i < n; i++) {
       const xvcgpu_frame_pass_args *a = args[i];
-      xvcgpu_ctx *c = ctxs[i];
-      const int tiles = tail_tiles(a->rec->w, a->rec->h);
-      const xvcgpu_status st = ensure_tail(c, tiles);
+      const xvcgpu_status st = ensure_tail(ctxs[i], tiles);
       if (st != XVCGPU_OK) return st;
-      if (a->orig->w != a->rec->w || a->orig->h != a->rec->h || !a->d_ssd || !a->d_cus ||
-          !a->d_cu_map || a->shift_bitdepth < 8)
+      if (a->orig->w != a->rec->w || a->orig->h != a->rec->h || a->shift_bitdepth < 8)
         return XVCGPU_INVALID_ARGUMENT;
-      TailMultiArgs &k = t.a[i];
-      k.d.bd = a->rec->bd;
-      k.d.pic_w = a->rec->w;
-      k.d.pic_h = a->rec->h;
-      k.d.bipred = 0;
-      k.d.beta_off = 0;
-      k.d.tc_off = 0;
-      k.d.sub = 4;
-      k.d.y_begin = 0;
-      k.d.y_end = a->rec->h;
-      k.d.cus = a->d_cus;
-      k.d.map = a->d_cu_map;
-      k.d.map_stride = a->map_stride;
-      k.d.map_rows = (a->rec->h + 3) / 4;
-      k.d.comp_mask = 3;
-      k.src = a->scratch_rec->v;
-      k.dst = a->rec->v;
-      k.orig = a->orig->v.c[0];
-      k.shift = 2 * (a->shift_bitdepth - 8);
-      k.tiles = tiles;
-      k.part = c->d_tail_part;
-      k.out = reinterpret_cast<unsigned long long *>(a->d_ssd);
-      max_tiles = std::max(max_tiles, tiles);
     }
-    hipLaunchKernelGGL(deblock_tail_multi_kernel, dim3((max_tiles + 7) / 8 * 8, n), dim3(256), 0,
+    const MultiArgs<TailMultiArgs> t = multi_args<TailMultiArgs>(
+        ctxs, args, n, [tiles](Args a, xvcgpu_ctx *c, TailMultiArgs &k) {
+          k.d.bd = a->rec->bd;
+          k.d.pic_w = a->rec->w;
+          k.d.pic_h = a->rec->h;
+          k.d.bipred = k.d.beta_off = k.d.tc_off = 0;
+          k.d.sub = 4;
+          k.d.y_begin = 0;
+          k.d.y_end = a->rec->h;
+          k.d.cus = a->d_cus;
+          k.d.map = a->d_cu_map;
+          k.d.map_stride = a->map_stride;
+          k.d.map_rows = (a->rec->h + 3) / 4;
+          k.d.comp_mask = 3;
+          k.src = a->scratch_rec->v;
+          k.dst = a->rec->v;
+          k.orig = a->orig->v.c[0];
+          k.shift = 2 * (a->shift_bitdepth - 8);
+          k.tiles = tiles;
+          k.part = c->d_tail_part;
+          k.out = reinterpret_cast<unsigned long long *>(a->d_ssd);
+        });
+    hipLaunchKernelGGL(deblock_tail_multi_kernel, dim3((tiles + 7) / 8 * 8, n), dim3(256), 0,
                        ctx->stream, t);
     hipLaunchKernelGGL(picture_ssd_sum_multi_kernel, dim3(1, n), dim3(256), 0, ctx->stream, t);
   }
-  (void)one;
   CHECK_LAUNCH(ctx, "frame_pass_multi");
   return XVCGPU_OK;
 }
@@ -2927,12 +2952,7 @@ xvcgpu_status xvcgpu_me_search_refs(xvcgpu_ctx *ctx, const xvcgpu_picture *orig,
   if (st != XVCGPU_OK) return st;
   if (n == 0) return XVCGPU_OK;
   Me2Sched sched = {nullptr, nullptr, nullptr};
-  if (flags & XVCGPU_ME_FULLPEL) {
-    const int e = ctx->me_epoch = (ctx->me_epoch + 1) % 3;
-    sched.use = ctx->d_me_rot + e % 3;
-    sched.record = ctx->d_me_rot + (e + 1) % 3;
-    sched.clear = ctx->d_me_rot + (e + 2) % 3;
-  }
+  if (flags & XVCGPU_ME_FULLPEL) sched = me_sched_next(ctx);
 #define ME_REFS(MS, PH)                                                                      \
   hipLaunchKernelGGL((me_search_refs_kernel<MS, PH>), me2_grid(n, ME2_WAVES(MS)),            \
                      dim3(64 * ME2_WAVES(MS)), 0, ctx->stream, orig->v, t, d_slots, d_blocks, \
@@ -3165,11 +3185,7 @@ xvcgpu_status xvcgpu_cs_segs_launch(xvcgpu_ctx *ctx, int kind, const xvcgpu_cs_s
         hipLaunchKernelGGL(cs_seg_merge_fold_kernel, dim3((max_n + 63) / 64, gy), dim3(64), 0, st, a);
         break;
       case XVC_CS_SEG_ME_REFS: {
-        const int ep = ctx->me_epoch = (ctx->me_epoch + 1) % 3;
-        Me2Sched sched;
-        sched.use = ctx->d_me_rot + ep % 3;
-        sched.record = ctx->d_me_rot + (ep + 1) % 3;
-        sched.clear = ctx->d_me_rot + (ep + 2) % 3;
+        const Me2Sched sched = me_sched_next(ctx);
 #define SEG_ME(MS, PH)                                                                      \
   hipLaunchKernelGGL((cs_seg_me_kernel<MS, PH>), dim3(me2_grid(max_n, ME2_WAVES(MS)).x, gy), \
                      dim3(64 * ME2_WAVES(MS)), 0, st, a, ctx->d_tz_pattern, sched)

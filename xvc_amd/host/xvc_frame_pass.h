@@ -101,7 +101,7 @@ class FramePass {
     std::vector<xvcgpu_me_block> me;
     std::vector<xvcgpu_tx_block> tx;
     std::vector<int32_t> luma;
-    int side = 16;
+    int side = 16, small = 16;
     for (size_t i = 0; i < partition.size(); i++) {
       const CuRect &p = partition[i];
       xvcgpu_me_block b = xvcgpu_me_block();
@@ -130,7 +130,12 @@ class FramePass {
       }
       side = p.w > side ? p.w : side;
       side = p.h > side ? p.h : side;
+      small = p.w < small ? p.w : small;
+      small = p.h < small ? p.h : small;
     }
+    // the kernels that take a CU whole hold CUs of 8 ... 16 samples a side: any other
+    // partition takes the any-size middle
+    form_ = side <= 16 && small >= 8 ? XVC_FP_FORM_RECON_FROM_ME : XVC_FP_FORM_RESIDUAL;
     me_shape_ = 0;
     max_cu_ = side <= 16 ? 16 : (side <= 32 ? 32 : 64);   // the search's block class
     Allocate(me, map);
@@ -180,6 +185,7 @@ class FramePass {
     if (!me.empty() && sq16 == me.size()) me_shape_ |= XVCGPU_ME_ONLY_SQ16;
     Allocate(me, map);
     max_cu_ = cu;
+    form_ = XVC_FP_FORM_RECON_FROM_ME;
   }
 
   ~FramePass() {
@@ -216,9 +222,10 @@ class FramePass {
     a.shift_bitdepth = bd_;
     a.d_ssd = d_ssd_->data();
     a.me_shape = me_shape_;
+    a.form = form_;
     const int phases = XVC_FP_ENCODE | XVC_FP_DEBLOCK_V | XVC_FP_DEBLOCK_H | XVC_FP_PAD |
                        XVC_FP_SSD;
-    if (plan_) {   // a partition: the any-size middle's arguments, the planned search
+    if (plan_) {   // a partition: the residual form's arguments, the planned search
       a.pred = pred_->get();
       a.d_tx = d_tx_->data();
       a.n_tx = 3 * n_cus_;
@@ -251,7 +258,7 @@ class FramePass {
   }
 
   const Context &ctx_;
-  int w_, h_, bd_, qp_, qp_c_, n_cus_, map_stride_, max_cu_, me_shape_;
+  int w_, h_, bd_, qp_, qp_c_, n_cus_, map_stride_, max_cu_, me_shape_, form_;
   xvcgpu_me_plan *plan_;
   std::unique_ptr<DeviceArray<xvcgpu_tx_block>> d_tx_;
   std::unique_ptr<DeviceArray<int32_t>> d_luma_;

@@ -300,15 +300,14 @@ class FramePass:
         self.w, self.h, self.bd = width, height, bitdepth
         self.desc = d = FrameDescriptors(width, height, qp, cu, search_range,
                                          row_range, rdoq, bitdepth, xcd_tiles, partition)
-        if partition is not None:
-            # the kernels that take a CU whole hold CUs of 8 ... 16 samples a side; `cu`
-            # below: what the grid's rules (cu <= 16, cu >= 8) look at
-            cu = 16 if (d.max_side <= 16 and d.min_side >= 8) else max(32, d.cu_size)
-        # the form of the launches between the search and the tail (_launches), named
-        # after the launch that sets it apart
-        if cu <= 16 and self.fused:
+        # the kernels that take a CU whole hold CUs of 8 ... 16 samples a side (the grid
+        # goes by its nominal side: what the picture edge cuts off a CU does not count)
+        max_side, small_side = (d.max_side, d.min_side) if partition is not None else (cu, cu)
+        whole_cu_kernels = max_side <= 16 and (small_side >= 8 or partition is None)
+        # the form (api.FP_FORM_NAMES) of the launches between the search and the tail
+        if whole_cu_kernels and self.fused:
             self.form = "recon_from_me"     # fused: QuantFast or the RDOQ kernel
-        elif cu <= 16 and self.rdoq_packed:
+        elif whole_cu_kernels and self.rdoq_packed:
             self.form = "fwd_from_me"       # packed RDOQ
         elif self.rdoq_packed:
             self.form = "fwd_transform"     # packed RDOQ behind mc_from_me
@@ -346,7 +345,6 @@ class FramePass:
         # unfiltered reconstruction in `scratch` -> deblocked, padded `rec` + SSD)
         # instead of deblock V, H, pad, SSD, SSD fold
         if partition is not None:
-            cu = d.min_side
             self.plan = ctx.me_plan(self.d_me.ptr, d.n_cus, d.cu_size)
             bad = int(self.plan.counts[api.ME_PLAN_BIN_NAMES.index("unsupported")])
             if bad:
@@ -358,11 +356,10 @@ class FramePass:
                 raise ValueError("partition: the motion search has no instance for %d CUs "
                                  "(sides must be 4, 8, 16, 32 or 64), first (x, y, w, h) = %r"
                                  % (bad, odd[0] if odd else None))
-        self.fused_tail = cu >= 8 and width % 8 == 0 and height % 8 == 0 and \
+        self.fused_tail = small_side >= 8 and width % 8 == 0 and height % 8 == 0 and \
             d.row_range == (0, d.h) and os.environ.get("XVC_TAIL_FUSED", "1") != "0"
         self.scratch = ctx.picture(width, height, bitdepth) if self.fused_tail else None
-        self.d_levels = self.d_level_off = None
-        self.n_levels = 0
+        self.d_levels, self.d_level_off, self.n_levels = None, None, 0
         if keep_levels:
             off, total = ctx.level_offsets(d.tx)
             self.d_level_off = ctx.buffer(off)
@@ -390,19 +387,16 @@ class FramePass:
             a.scratch_rec = self.scratch.h_pic if self.scratch is not None else None
             a.ssd_y_begin, a.ssd_y_end = 0, 1 << 30
             a.shift_bitdepth, a.d_ssd = self.bd, self.d_ssd.ptr
+            a.form = api.FP_FORM_NAMES.index(self.form)
             if self.rdoq:
                 a.d_rdoq_contexts, a.d_rdoq_params = self.d_rdoq_ctx.ptr, self.d_rdoq_prm.ptr
-            if self.rdoq_packed:
-                a.pred, a.d_tx, a.n_tx = self.pred.h_pic, self.d_tx.ptr, len(d.tx)
-                a.d_level_off, a.d_luma_tx_index = self.d_level_off.ptr, self.d_luma_idx.ptr
-                a.d_coeffs, a.d_levels = self.d_coeffs.ptr, self.d_levels.ptr
-                a.n_coeffs = self.n_levels
-            elif self.plan is not None and self.form == "residual":
-                # the any-size QuantFast middle of xvcgpu_frame_pass_planned
+            if self.form != "recon_from_me":    # the fields of the other forms (xvcgpu.h)
                 a.pred, a.d_tx, a.n_tx = self.pred.h_pic, self.d_tx.ptr, len(d.tx)
                 a.d_luma_tx_index = self.d_luma_idx.ptr
                 if self.d_levels is not None:
                     a.d_level_off, a.d_levels = self.d_level_off.ptr, self.d_levels.ptr
+            if self.rdoq_packed:
+                a.d_coeffs, a.n_coeffs = self.d_coeffs.ptr, self.n_levels
             a.tx_four_lane_only = int(self.tx_four_lane_only)
             a.me_shape = self.me_flags & (api.ME_HINT_SQ16 | api.ME_ONLY_SQ16)
             self._fp_args = a
@@ -418,8 +412,7 @@ class FramePass:
 
     def run_phases(self, orig, ref, rec, phases, ref_poc=0, rows=None, dbh_end=None,
                    ssd_rows=None, d_ssd=None):
-        """One call for the selected phases (api.FP_*).  Needs the fused
-        CompressAndEvalCbf kernel (CUs up to 16x16) for FP_ENCODE."""
+        """One call for the selected phases (api.FP_*)."""
         a = self._call_args(orig, ref, rec, ref_poc)
         if rows is not None:
             a.db_y_begin, a.db_y_end = rows
@@ -532,17 +525,8 @@ class FramePass:
 
     def run(self, orig, ref, rec, ref_poc=0, deblock=True, pad=True, ssd=True):
         """Enqueue one whole-picture frame pass (asynchronous)."""
-        d = self.desc
-        one_call = self.form in ("recon_from_me", "fwd_from_me")
-        if self.plan is not None and d.n_cus > 0 and self.form in ("residual", "fwd_transform"):
-            # xvcgpu_frame_pass_planned has the any-size middle behind the one call too, and
-            # takes it where the plan holds a CU above 16x16 or with a side below 8, or where
-            # QuantFast levels are kept; any other pass of these forms (fused=False on CUs
-            # of 8 ... 16) would get the fused kernels there: launch by launch instead
-            one_call = d.cu_size > 16 or d.min_side < 8 or \
-                (self.form == "residual" and self.d_levels is not None)
-        if one_call and d.row_range == (0, d.h):
-            # the whole sequence behind one C call (xvcgpu_frame_pass)
+        if self.desc.row_range == (0, self.desc.h):
+            # the whole sequence behind one C call (xvcgpu_frame_pass), whatever the form
             self.run_phases(orig, ref, rec, api.FP_ENCODE |
                             (api.FP_DEBLOCK_V | api.FP_DEBLOCK_H if deblock else 0) |
                             (api.FP_PAD if pad else 0) | (api.FP_SSD if ssd else 0), ref_poc)
