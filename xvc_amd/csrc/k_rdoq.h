@@ -1226,6 +1226,78 @@ struct RdoqLists {
 };
 #define RDOQ_CHUNK 4096   // blocks per workgroup of the compaction kernels (4 per thread)
 
+// The context's scratch behind the lists, for a capacity of `cap` blocks: count[4],
+// the three lists (cap ints each), the classes (cap bytes = cap / 4 ints), then the
+// compaction's per-chunk counts.  cap is a multiple of four (rdoq_scratch_cap): the
+// classes then start 16 bytes aligned behind count[4] and the three lists, which
+// rdoq_lists_kernel's 16-byte reads rely on.
+inline int rdoq_scratch_cap(int n) { return (n + n / 4 + 3) & ~3; }
+inline size_t rdoq_scratch_bytes(int cap) {
+  return sizeof(int) * (4 + 4 * (size_t)cap + 4 * ((size_t)cap / RDOQ_CHUNK + 2));
+}
+inline RdoqLists rdoq_scratch_lists(int *base, int cap) {
+  RdoqLists l;
+  l.count = base;
+  for (int c = 0; c < 3; c++) l.list[c] = base + 4 + (size_t)c * cap;
+  l.cls = reinterpret_cast<signed char *>(base + 4 + 3 * (size_t)cap);
+  l.part = base + 4 + 4 * (size_t)cap;
+  return l;
+}
+
+// ---- the pieces the list builders below are made of ----
+// the classes 0 / 1 / 2 among the four class bytes of word v (blocks i .. i + 3),
+// as far as they lie below `end`, added to cnt[]
+__device__ __forceinline__ void rq_count_word(uint32_t v, int i, int end, int cnt[3]) {
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const int c = (int)(signed char)(v >> (8 * k));
+    const bool in = i + k < end;
+    cnt[0] += in && c == 0;
+    cnt[1] += in && c == 1;
+    cnt[2] += in && c == 2;
+  }
+}
+// inclusive scan of a counter over the 64 lanes of a wave (the builders run it on
+// their three counters in turn)
+__device__ __forceinline__ int rq_wave_scan(int v) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int o = __shfl_up(v, d, 64);
+    if (lane >= d) v += o;
+  }
+  return v;
+}
+// the sixteen wave totals of a 1024-thread workgroup, tot[k][0..15], scanned by the
+// first wave: tot[k][16 + w] = inclusive total of waves 0..w.  The caller's barriers
+// stand before and behind it.
+template <int ROW>
+__device__ __forceinline__ void rq_wave_totals_scan(int (&tot)[3][ROW]) {
+  const int t = threadIdx.x;
+  if (t < 64) {
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      int v = t < 16 ? tot[k][t] : 0;
+#pragma unroll
+      for (int d = 1; d < 16; d <<= 1) {
+        const int o = __shfl_up(v, d, 64);
+        if (t >= d) v += o;
+      }
+      if (t < 16) tot[k][16 + t] = v;
+    }
+  }
+}
+// the listed blocks among i .. i + 3 (class bytes in word v, below `end`) appended to
+// their lists at pos[]
+__device__ __forceinline__ void rq_scatter_word(uint32_t v, int i, int end, const RdoqLists &l,
+                                                int pos[3]) {
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const int c = (int)(signed char)(v >> (8 * k));
+    if (i + k < end && c >= 0) l.list[c][pos[c]++] = i + k;
+  }
+}
+
 // 0 / 1: diagonal scan, 4x4 sub-blocks, at most four / sixteen of them - four lanes
 // per sub-block (wave_rdoq4); 2: everything else (the other scans, 2-wide blocks,
 // more than sixteen sub-blocks, 64-point sides) - a lane per sub-block (wave_rdoq)
@@ -1627,6 +1699,7 @@ __device__ __forceinline__ bool rq_prove_zero_lds(RqProveLds &pv, const xvcgpu_t
 // The class lists from the per-block classes, without atomics (a few thousand
 // atomicAdds on three addresses took 150 us): one workgroup, every thread
 // counts its contiguous chunk, an LDS scan gives the chunk's place in each list.
+// The builder of xvcgpu_frame_pass_multi (rdoq_compact_multi_kernel, k_multi.h).
 // grid: 1; block: 1024.
 __device__ __forceinline__ void rdoq_compact_kernel_body(int n, RdoqLists l) {
   __shared__ int part[3][1024];
@@ -1636,17 +1709,7 @@ __device__ __forceinline__ void rdoq_compact_kernel_body(int n, RdoqLists l) {
   const int a = t * per, e = a + per < n ? a + per : n;
   const uint32_t *cw = reinterpret_cast<const uint32_t *>(l.cls);
   int cnt[3] = {0, 0, 0};
-  for (int i = a; i < e; i += 4) {
-    const uint32_t v = cw[i >> 2];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      const int c = (int)(signed char)(v >> (8 * k));
-      const bool in = i + k < e;
-      cnt[0] += in && c == 0;
-      cnt[1] += in && c == 1;
-      cnt[2] += in && c == 2;
-    }
-  }
+  for (int i = a; i < e; i += 4) rq_count_word(cw[i >> 2], i, e, cnt);
 #pragma unroll
   for (int k = 0; k < 3; k++) part[k][t] = cnt[k];
   __syncthreads();
@@ -1655,48 +1718,19 @@ __device__ __forceinline__ void rdoq_compact_kernel_body(int n, RdoqLists l) {
   int inc[3];
 #pragma unroll
   for (int k = 0; k < 3; k++) {
-    int v = cnt[k];
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int o = __shfl_up(v, d, 64);
-      if ((t & 63) >= d) v += o;
-    }
-    inc[k] = v;
-    if ((t & 63) == 63) part[k][t >> 6] = v;  // wave totals (slots 0..15 reused after the sync)
+    inc[k] = rq_wave_scan(cnt[k]);
+    if ((t & 63) == 63) part[k][t >> 6] = inc[k];  // wave totals (slots 0..15 reused after the sync)
   }
   __syncthreads();
-  if (t < 64) {
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-      int v = t < 16 ? part[k][t] : 0;
-#pragma unroll
-      for (int d = 1; d < 16; d <<= 1) {
-        const int o = __shfl_up(v, d, 64);
-        if (t >= d) v += o;
-      }
-      if (t < 16) part[k][16 + t] = v;  // inclusive totals of waves 0..t
-    }
-  }
+  rq_wave_totals_scan(part);
   __syncthreads();
   int pos[3];
 #pragma unroll
   for (int k = 0; k < 3; k++)
     pos[k] = inc[k] - cnt[k] + ((t >> 6) ? part[k][16 + (t >> 6) - 1] : 0);
-  for (int i = a; i < e; i += 4) {
-    const uint32_t v = cw[i >> 2];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      const int c = (int)(signed char)(v >> (8 * k));
-      if (i + k < e && c >= 0) l.list[c][pos[c]++] = i + k;
-    }
-  }
+  for (int i = a; i < e; i += 4) rq_scatter_word(cw[i >> 2], i, e, l, pos);
   if (t == 1023)
     for (int k = 0; k < 3; k++) l.count[k] = part[k][16 + 15];
-}
-
-__global__ void __launch_bounds__(1024)
-rdoq_compact_kernel(int n, RdoqLists l) {
-  rdoq_compact_kernel_body(n, l);
 }
 
 // The same lists from many workgroups, still without atomics and in block order
@@ -1705,28 +1739,12 @@ rdoq_compact_kernel(int n, RdoqLists l) {
 // RDOQ_CHUNK blocks, four per thread.  Launch 1 counts the chunk's classes; launch
 // 2 sums the counts of the chunks in front of it (at most a few hundred), scans
 // its own threads' counts and scatters.  grid: ceil(n / RDOQ_CHUNK); block: 1024.
-__device__ __forceinline__ void rdoq_chunk_counts(int n, const RdoqLists &l, int cnt[3]) {
-  const int i = (int)blockIdx.x * RDOQ_CHUNK + 4 * (int)threadIdx.x;
-  cnt[0] = cnt[1] = cnt[2] = 0;
-  if (i < n) {
-    const uint32_t v = reinterpret_cast<const uint32_t *>(l.cls)[i >> 2];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      const int c = (int)(signed char)(v >> (8 * k));
-      const bool in = i + k < n;
-      cnt[0] += in && c == 0;
-      cnt[1] += in && c == 1;
-      cnt[2] += in && c == 2;
-    }
-  }
-}
-
 __global__ void __launch_bounds__(1024)
 rdoq_count_kernel(int n, RdoqLists l) {
   __shared__ int wsum[3][16];
-  int cnt[3];
-  rdoq_chunk_counts(n, l, cnt);
-  const int t = threadIdx.x;
+  const int t = threadIdx.x, i = (int)blockIdx.x * RDOQ_CHUNK + 4 * t;
+  int cnt[3] = {0, 0, 0};
+  if (i < n) rq_count_word(reinterpret_cast<const uint32_t *>(l.cls)[i >> 2], i, n, cnt);
 #pragma unroll
   for (int k = 0; k < 3; k++) {
     const int v = wave_reduce_add_i32(cnt[k]);
@@ -1766,53 +1784,27 @@ rdoq_scatter_kernel(int n, RdoqLists l) {
     }
     __syncthreads();
   }
-  int cnt[3];
-  rdoq_chunk_counts(n, l, cnt);
+  const int i = b * RDOQ_CHUNK + 4 * t;
+  const uint32_t *cw = reinterpret_cast<const uint32_t *>(l.cls);
+  int cnt[3] = {0, 0, 0};
+  if (i < n) rq_count_word(cw[i >> 2], i, n, cnt);
   int inc[3];
 #pragma unroll
-  for (int k = 0; k < 3; k++) {
-    int v = cnt[k];
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int o = __shfl_up(v, d, 64);
-      if ((t & 63) >= d) v += o;
-    }
-    inc[k] = v;
-  }
+  for (int k = 0; k < 3; k++) inc[k] = rq_wave_scan(cnt[k]);
   __syncthreads();   // base[] read by everybody before part[] is reused
-  const int b0 = base[0], b1 = base[1], b2 = base[2];
+  const int bs[3] = {base[0], base[1], base[2]};
   __syncthreads();
 #pragma unroll
   for (int k = 0; k < 3; k++)
     if ((t & 63) == 63) part[k][t >> 6] = inc[k];
   __syncthreads();
-  if (t < 64) {
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-      int v = t < 16 ? part[k][t] : 0;
-#pragma unroll
-      for (int d = 1; d < 16; d <<= 1) {
-        const int o = __shfl_up(v, d, 64);
-        if (t >= d) v += o;
-      }
-      if (t < 16) part[k][16 + t] = v;
-    }
-  }
+  rq_wave_totals_scan(part);
   __syncthreads();
-  const int bs[3] = {b0, b1, b2};
   int pos[3];
 #pragma unroll
   for (int k = 0; k < 3; k++)
     pos[k] = bs[k] + inc[k] - cnt[k] + ((t >> 6) ? part[k][16 + (t >> 6) - 1] : 0);
-  const int i = b * RDOQ_CHUNK + 4 * t;
-  if (i < n) {
-    const uint32_t v = reinterpret_cast<const uint32_t *>(l.cls)[i >> 2];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      const int c = (int)(signed char)(v >> (8 * k));
-      if (i + k < n && c >= 0) l.list[c][pos[c]++] = i + k;
-    }
-  }
+  if (i < n) rq_scatter_word(cw[i >> 2], i, n, l, pos);
   if (b == (int)gridDim.x - 1 && t == 1023)
     for (int k = 0; k < 3; k++) l.count[k] = bs[k] + part[k][16 + 15];
 }
@@ -1820,7 +1812,7 @@ rdoq_scatter_kernel(int n, RdoqLists l) {
 // The same lists in ONE launch, for batches small enough that a redundant read of
 // the classes costs less than a second launch and the hand-over through l.part: a
 // workgroup of 256 threads owns RDOQ_LISTS_CHUNK blocks (four per thread, the
-// per-thread shape of rdoq_chunk_counts) and counts the classes of all the chunks
+// per-thread shape of the two kernels above) and counts the classes of all the chunks
 // in front of it itself - 1024 bytes per chunk, sixteen at a time, resident in L2
 // (1080p: 24 workgroups, the last one reads 23 KB).  That read grows with the
 // square of n: the caller keeps the two launches above for large batches.  Four
@@ -1841,8 +1833,8 @@ rdoq_lists_kernel(int n, RdoqLists l) {
   const int t = threadIdx.x, b = blockIdx.x, wv = t >> 6;
   const uint32_t *cw = reinterpret_cast<const uint32_t *>(l.cls);
   // the chunks in front of this one: 64 * b 16-byte words of classes, all of them
-  // inside n.  l.cls is 16-byte aligned (ensure_rdoq_scratch keeps the lists'
-  // capacity a multiple of four), so the reads cover the prefix and nothing else
+  // inside n.  l.cls is 16-byte aligned (rdoq_scratch_cap), so the reads cover the
+  // prefix and nothing else
   int v[3] = {0, 0, 0};
   {
     const uint4 *q = reinterpret_cast<const uint4 *>(cw);
@@ -1864,46 +1856,27 @@ rdoq_lists_kernel(int n, RdoqLists l) {
   int cnt[3] = {0, 0, 0};
   if (i < n) {
     mine = cw[i >> 2];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      const int c = (int)(signed char)(mine >> (8 * k));
-      const bool in = i + k < n;
-      cnt[0] += in && c == 0;
-      cnt[1] += in && c == 1;
-      cnt[2] += in && c == 2;
-    }
+    rq_count_word(mine, i, n, cnt);
   }
   int inc[3];
 #pragma unroll
   for (int k = 0; k < 3; k++) {
     const int w = wave_reduce_add_i32(v[k]);
-    int s = cnt[k];
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int o = __shfl_up(s, d, 64);
-      if ((t & 63) >= d) s += o;
-    }
-    inc[k] = s;
+    inc[k] = rq_wave_scan(cnt[k]);
     if ((t & 63) == 0) wsum[k][wv] = w;
-    if ((t & 63) == 63) wtot[k][wv] = s;
+    if ((t & 63) == 63) wtot[k][wv] = inc[k];
   }
   __syncthreads();
-  int base[3], pos[3];
+  int pos[3];
 #pragma unroll
   for (int k = 0; k < 3; k++) {
-    base[k] = wsum[k][0] + wsum[k][1] + wsum[k][2] + wsum[k][3];
+    const int base = wsum[k][0] + wsum[k][1] + wsum[k][2] + wsum[k][3];
     int before = 0;
 #pragma unroll
     for (int w = 0; w < 3; w++) before += w < wv ? wtot[k][w] : 0;
-    pos[k] = base[k] + before + inc[k] - cnt[k];
+    pos[k] = base + before + inc[k] - cnt[k];
   }
-  if (i < n) {
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      const int c = (int)(signed char)(mine >> (8 * k));
-      if (i + k < n && c >= 0) l.list[c][pos[c]++] = i + k;
-    }
-  }
+  if (i < n) rq_scatter_word(mine, i, n, l, pos);
   if (b == (int)gridDim.x - 1 && t == 255)
     for (int k = 0; k < 3; k++) l.count[k] = pos[k];   // base + the chunk's total
 }

@@ -61,6 +61,32 @@ xvcgpu_status fail(xvcgpu_ctx *ctx, xvcgpu_status st, const char *what,
 
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
+// Grow-only scratch of a context: *slot holds room for *cap units (items, tiles, rows,
+// blocks - the caller's measure).  Where `want` is more, the old buffer is freed once the
+// context's stream - whose work may still use it - has drained, and `bytes` are
+// allocated, zeroed on the context's stream where the scratch's readers rely on that.
+template <typename T>
+xvcgpu_status grow_scratch(xvcgpu_ctx *ctx, T **slot, int *cap, int want, size_t bytes,
+                           bool zero, const char *what) {
+  if (want <= *cap) return XVCGPU_OK;
+  if (*slot) {
+    hipStreamSynchronize(ctx->stream);
+    hipFree(*slot);
+    *slot = nullptr;
+    *cap = 0;
+  }
+  const hipError_t e = hipMalloc(slot, bytes);
+  if (e != hipSuccess) return fail(ctx, XVCGPU_OUT_OF_MEMORY, what, e);
+  if (zero) hipMemsetAsync(*slot, 0, bytes, ctx->stream);
+  *cap = want;
+  return XVCGPU_OK;
+}
+
+// the context's RDOQ scratch as the kernels see it (the layout: k_rdoq.h)
+RdoqLists rdoq_lists_of(const xvcgpu_ctx *ctx) {
+  return rdoq_scratch_lists(ctx->d_rdoq_lists, ctx->rdoq_lists_cap);
+}
+
 // Blocks visited by ComparePicture on a w x h plane (sample_metric.cc:64-88).
 inline int ssd_items(int w, int h) {
   const int mbx = w & ~(w - 1), mby = h & ~(h - 1);
@@ -924,15 +950,15 @@ xvcgpu_status xvcgpu_debug_rdoq_lists(xvcgpu_ctx *ctx, int32_t counts[3], int32_
   counts[0] = counts[1] = counts[2] = 0;
   if (!ctx->d_rdoq_lists || !ctx->rdoq_last_n) return XVCGPU_OK;
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  HIP_TRY(ctx, hipMemcpy(counts, ctx->d_rdoq_lists, 3 * sizeof(int32_t), hipMemcpyDeviceToHost));
+  const RdoqLists l = rdoq_lists_of(ctx);
+  HIP_TRY(ctx, hipMemcpy(counts, l.count, 3 * sizeof(int32_t), hipMemcpyDeviceToHost));
   for (int c = 0; c < 3; c++) {
     if (counts[c] < 0 || counts[c] > ctx->rdoq_last_n)
       return fail(ctx, XVCGPU_DEVICE_ERROR, "rdoq list count out of range");
     if (counts[c] > cap) return fail(ctx, XVCGPU_INVALID_ARGUMENT, "rdoq lists: cap too small");
     if (counts[c])
-      HIP_TRY(ctx, hipMemcpy(lists + (size_t)c * cap,
-                             ctx->d_rdoq_lists + 4 + (size_t)c * ctx->rdoq_lists_cap,
-                             counts[c] * sizeof(int32_t), hipMemcpyDeviceToHost));
+      HIP_TRY(ctx, hipMemcpy(lists + (size_t)c * cap, l.list[c], counts[c] * sizeof(int32_t),
+                             hipMemcpyDeviceToHost));
   }
   return XVCGPU_OK;
 }
@@ -1426,7 +1452,8 @@ xvcgpu_status xvcgpu_residual_rdoq_batch(xvcgpu_ctx *ctx, const xvcgpu_picture *
   return XVCGPU_OK;
 }
 
-// workgroups per class of quant_rdo_packed_kernel (k_rdoq.h)
+// workgroups per class of quant_rdo_packed_kernel (k_rdoq.h); -DRDOQ_GRID16= ... at build
+// time is the knob for experiments, nothing reads the environment
 #ifndef RDOQ_GRID16
 #define RDOQ_GRID16 8192   // blocks of up to sixteen sub-blocks: one per wave
 #endif
@@ -1437,28 +1464,14 @@ xvcgpu_status xvcgpu_residual_rdoq_batch(xvcgpu_ctx *ctx, const xvcgpu_picture *
 #define RDOQ_GRID64 512
 #endif
 
-static xvcgpu_status ensure_rdoq_scratch(xvcgpu_ctx *ctx, int n, size_t n_coeffs) {
-  // scratch: class lists (3 x n) + counters + the per-block classes
-  if (n > ctx->rdoq_lists_cap) {
-    if (ctx->d_rdoq_lists) {
-      hipStreamSynchronize(ctx->stream);
-      hipFree(ctx->d_rdoq_lists);
-      ctx->d_rdoq_lists = nullptr;
-      ctx->rdoq_lists_cap = 0;
-    }
-    // a multiple of four: the classes then start 16 bytes aligned behind count[4] and
-    // the three lists, which rdoq_lists_kernel's 16-byte reads rely on
-    const int cap = (n + n / 4 + 3) & ~3;
-    // count[4], three lists and the classes (cap bytes = cap / 4 ints), then the
-    // compaction's per-chunk counts
-    if (hipMalloc(&ctx->d_rdoq_lists,
-                  sizeof(int) * (4 * (size_t)cap + 4 + 4 * ((size_t)cap / RDOQ_CHUNK + 2))) !=
-        hipSuccess)
-      return fail(ctx, XVCGPU_OUT_OF_MEMORY, "rdoq lists");
-    ctx->rdoq_lists_cap = cap;
-  }
-  (void)n_coeffs;  // the per-coefficient records live in LDS
-  return XVCGPU_OK;
+// Scratch of the packed quantiser: the class lists, their counters and the per-block
+// classes (k_rdoq.h: rdoq_scratch_lists), with a quarter of headroom; grown by the
+// first batch of a size, or ahead of it by xvcgpu_quant_rdo_reserve.
+static xvcgpu_status ensure_rdoq_scratch(xvcgpu_ctx *ctx, int n) {
+  if (n <= ctx->rdoq_lists_cap) return XVCGPU_OK;   // (the headroom is for the next batch)
+  const int cap = rdoq_scratch_cap(n);
+  return grow_scratch(ctx, &ctx->d_rdoq_lists, &ctx->rdoq_lists_cap, cap, rdoq_scratch_bytes(cap),
+                      false, "rdoq lists");
 }
 
 xvcgpu_status xvcgpu_quant_rdo_class_counts(xvcgpu_ctx *ctx, int32_t out[3]) {
@@ -1466,7 +1479,8 @@ xvcgpu_status xvcgpu_quant_rdo_class_counts(xvcgpu_ctx *ctx, int32_t out[3]) {
   out[0] = out[1] = out[2] = 0;
   if (!ctx->d_rdoq_lists) return XVCGPU_OK;
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  HIP_TRY(ctx, hipMemcpy(out, ctx->d_rdoq_lists, 3 * sizeof(int32_t), hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(out, rdoq_lists_of(ctx).count, 3 * sizeof(int32_t),
+                         hipMemcpyDeviceToHost));
   return XVCGPU_OK;
 }
 
@@ -1490,35 +1504,37 @@ xvcgpu_status xvcgpu_quant_rdo_set_four_lane_only(xvcgpu_ctx *ctx, int on) {
 
 xvcgpu_status xvcgpu_quant_rdo_reserve(xvcgpu_ctx *ctx, int n, size_t n_coeffs) {
   if (!ctx || n < 0) return XVCGPU_INVALID_ARGUMENT;
-  return ensure_rdoq_scratch(ctx, n, n_coeffs);
+  (void)n_coeffs;   // the per-coefficient records live in LDS
+  return ensure_rdoq_scratch(ctx, n);
 }
 
-static RdoqLists rdoq_lists_of(xvcgpu_ctx *ctx) {
-  const int cap = ctx->rdoq_lists_cap;   // a multiple of four: cls is 16-byte aligned
-  RdoqLists l;
-  l.count = ctx->d_rdoq_lists;
-  for (int c = 0; c < 3; c++) l.list[c] = ctx->d_rdoq_lists + 4 + (size_t)c * cap;
-  l.cls = reinterpret_cast<signed char *>(ctx->d_rdoq_lists + 4 + 3 * (size_t)cap);
-  l.part = ctx->d_rdoq_lists + 4 + 4 * (size_t)cap;
-  return l;
+// The class sizes are only known on the device: a bounded number of workgroups per
+// class that walk their list (k_rdoq.h), for a batch of n blocks
+struct RdoqGrids {
+  int g16, g4, g64;
+};
+static RdoqGrids rdoq_walk_grids(int n) {
+  return {std::min(n, RDOQ_GRID16), std::min((n + 3) / 4, RDOQ_GRID4), std::min(n, RDOQ_GRID64)};
 }
 
 // classified: the blocks' classes are already in the context's RdoqLists::cls
-// (written by the forward transform of xvcgpu_frame_pass, FwdClassify)
+// (written by the forward transform of xvcgpu_frame_pass, FwdClassify); four_only: the
+// general class's launch is skipped (xvcgpu_quant_rdo_set_four_lane_only, or the frame
+// pass's tx_four_lane_only)
 static xvcgpu_status quant_rdo_launch(xvcgpu_ctx *ctx, int bitdepth,
                                       const xvcgpu_tx_block *d_blocks, int n,
                                       const int16_t *d_coeffs, const uint32_t *d_offsets,
                                       size_t n_coeffs, int16_t *d_levels, int32_t *d_nnz,
                                       const xvcgpu_rdoq_contexts *d_contexts,
                                       const xvcgpu_rdoq_params *d_params, bool classified,
-                                      xvcgpu_cu_info *d_cu_patch = nullptr) {
+                                      bool four_only, xvcgpu_cu_info *d_cu_patch = nullptr) {
   if (!ctx || n < 0 || bitdepth < 8 || bitdepth > 12 ||
       (n && (!d_blocks || !d_coeffs || !d_offsets || !d_levels || !d_contexts || !d_params ||
              !n_coeffs)))
     return XVCGPU_INVALID_ARGUMENT;
   if (n == 0) return XVCGPU_OK;
   {
-    const xvcgpu_status st_ = ensure_rdoq_scratch(ctx, n, n_coeffs);
+    const xvcgpu_status st_ = ensure_rdoq_scratch(ctx, n);
     if (st_ != XVCGPU_OK) return st_;
   }
   const RdoqLists l = rdoq_lists_of(ctx);
@@ -1549,24 +1565,15 @@ static xvcgpu_status quant_rdo_launch(xvcgpu_ctx *ctx, int bitdepth,
     hipLaunchKernelGGL(rdoq_scatter_kernel, dim3(chunks), dim3(1024), 0, ctx->stream, n, l);
   }
   ctx->rdoq_last_n = n;
-  // the class sizes are only known on the device: a bounded number of workgroups
-  // per class that walk their list (k_rdoq.h)
-  static const int grid16 = [] {
-    const char *e = getenv("XVCGPU_RDOQ_GRID16");
-    const int v = e ? atoi(e) : 0;
-    return v > 0 ? v : RDOQ_GRID16;
-  }();
-  const int g16 = std::min(n, grid16), g4 = std::min((n + 3) / 4, RDOQ_GRID4),
-            g64 = std::min(n, RDOQ_GRID64);
+  const RdoqGrids g = rdoq_walk_grids(n);
   // (the general class's launch holds 255 vector registers a wave: even with an empty list
   // it waits for room beside other streams' kernels - 190 us in flight at 2160p; a caller
   // that knows its blocks says so and the launch is not made)
-  const bool four_only = ctx->rdoq_four_lane_only != 0;
-  hipLaunchKernelGGL(quant_rdo_packed4_kernel, dim3(g16 + g4), dim3(64), 0, ctx->stream,
-                     bitdepth, d_blocks, l, g16, d_coeffs, d_offsets, d_levels, d_nnz,
+  hipLaunchKernelGGL(quant_rdo_packed4_kernel, dim3(g.g16 + g.g4), dim3(64), 0, ctx->stream,
+                     bitdepth, d_blocks, l, g.g16, d_coeffs, d_offsets, d_levels, d_nnz,
                      d_contexts, d_params, d_cu_patch, four_only ? ctx->h_rdoq_misuse : nullptr);
   if (!four_only)
-    hipLaunchKernelGGL(quant_rdo_packed_kernel, dim3(g64), dim3(64), 0, ctx->stream,
+    hipLaunchKernelGGL(quant_rdo_packed_kernel, dim3(g.g64), dim3(64), 0, ctx->stream,
                        bitdepth, d_blocks, l, d_coeffs, d_offsets, d_levels, d_nnz,
                        d_contexts, d_params, d_cu_patch);
   CHECK_LAUNCH(ctx, "quant_rdo_batch");
@@ -1580,7 +1587,7 @@ xvcgpu_status xvcgpu_quant_rdo_batch(xvcgpu_ctx *ctx, int bitdepth,
                                      const xvcgpu_rdoq_contexts *d_contexts,
                                      const xvcgpu_rdoq_params *d_params) {
   return quant_rdo_launch(ctx, bitdepth, d_blocks, n, d_coeffs, d_offsets, n_coeffs, d_levels,
-                          d_nnz, d_contexts, d_params, false);
+                          d_nnz, d_contexts, d_params, false, ctx && ctx->rdoq_four_lane_only);
 }
 
 xvcgpu_status xvcgpu_quant_rdo_classified_batch(xvcgpu_ctx *ctx, int bitdepth,
@@ -1592,7 +1599,8 @@ xvcgpu_status xvcgpu_quant_rdo_classified_batch(xvcgpu_ctx *ctx, int bitdepth,
                                                 const xvcgpu_rdoq_params *d_params,
                                                 xvcgpu_cu_info *d_cus) {
   return quant_rdo_launch(ctx, bitdepth, d_blocks, n, d_coeffs, d_offsets, n_coeffs, d_levels,
-                          d_nnz, d_contexts, d_params, true, d_cus);
+                          d_nnz, d_contexts, d_params, true, ctx && ctx->rdoq_four_lane_only,
+                          d_cus);
 }
 
 xvcgpu_status xvcgpu_fwd_from_me_classify(xvcgpu_ctx *ctx, const xvcgpu_picture *orig,
@@ -1622,7 +1630,7 @@ xvcgpu_status xvcgpu_fwd_from_me_classify_prove(
     return fail(ctx, XVCGPU_INVALID_ARGUMENT, "picture mismatch");
   if (n == 0) return XVCGPU_OK;
   {
-    const xvcgpu_status st = ensure_rdoq_scratch(ctx, 3 * n, n_coeffs);
+    const xvcgpu_status st = ensure_rdoq_scratch(ctx, 3 * n);
     if (st != XVCGPU_OK) return st;
   }
   ctx->rdoq_qp_hint = qp_y;
@@ -1823,17 +1831,8 @@ xvcgpu_status xvcgpu_deblock(xvcgpu_ctx *ctx, xvcgpu_picture *rec,
 // Scratch for the per-block results of xvcgpu_picture_ssd; grown when a larger
 // picture is created, so no allocation happens on the measurement path.
 static xvcgpu_status ensure_ssd_part(xvcgpu_ctx *ctx, int items) {
-  if (items <= ctx->ssd_part_cap) return XVCGPU_OK;
-  if (ctx->d_ssd_part) {
-    hipStreamSynchronize(ctx->stream);
-    hipFree(ctx->d_ssd_part);
-    ctx->d_ssd_part = nullptr;
-    ctx->ssd_part_cap = 0;
-  }
-  hipError_t e = hipMalloc(&ctx->d_ssd_part, sizeof(unsigned long long) * 2 * items);
-  if (e != hipSuccess) return fail(ctx, XVCGPU_OUT_OF_MEMORY, "hipMalloc", e);
-  ctx->ssd_part_cap = items;
-  return XVCGPU_OK;
+  return grow_scratch(ctx, &ctx->d_ssd_part, &ctx->ssd_part_cap, items,
+                      sizeof(unsigned long long) * 2 * items, false, "ssd scratch");
 }
 
 xvcgpu_status xvcgpu_picture_ssd(xvcgpu_ctx *ctx, const xvcgpu_picture *a,
@@ -1869,19 +1868,8 @@ xvcgpu_status xvcgpu_picture_ssd_rows(xvcgpu_ctx *ctx, const xvcgpu_picture *a,
 // Scratch of xvcgpu_deblock_pad_ssd: per-tile results; sized when a picture is
 // created.
 static xvcgpu_status ensure_tail(xvcgpu_ctx *ctx, int tiles) {
-  if (tiles <= ctx->tail_cap) return XVCGPU_OK;
-  if (ctx->d_tail_part) {
-    hipStreamSynchronize(ctx->stream);
-    hipFree(ctx->d_tail_part);
-    ctx->d_tail_part = nullptr;
-    ctx->tail_cap = 0;
-  }
-  const size_t bytes = sizeof(unsigned long long) * (2 * (size_t)tiles + 2);
-  hipError_t e = hipMalloc(&ctx->d_tail_part, bytes);
-  if (e != hipSuccess) return fail(ctx, XVCGPU_OUT_OF_MEMORY, "hipMalloc", e);
-  hipMemsetAsync(ctx->d_tail_part, 0, bytes, ctx->stream);
-  ctx->tail_cap = tiles;
-  return XVCGPU_OK;
+  return grow_scratch(ctx, &ctx->d_tail_part, &ctx->tail_cap, tiles,
+                      sizeof(unsigned long long) * (2 * (size_t)tiles + 2), true, "tail scratch");
 }
 
 xvcgpu_status xvcgpu_deblock_pad_ssd(xvcgpu_ctx *ctx, const xvcgpu_picture *src,
@@ -1938,19 +1926,8 @@ static const int kStatsHistWords = 4096;
 // Scratch of the statistics passes; like the SSD scratch it is sized when a
 // picture is created, never on a measurement path.
 static xvcgpu_status ensure_stats(xvcgpu_ctx *ctx, int rows) {
-  if (rows <= ctx->stats_rows_cap) return XVCGPU_OK;
-  if (ctx->d_stats) {
-    hipStreamSynchronize(ctx->stream);
-    hipFree(ctx->d_stats);
-    ctx->d_stats = nullptr;
-    ctx->stats_rows_cap = 0;
-  }
-  const size_t bytes = sizeof(uint32_t) * ((size_t)kStatsHistWords + rows);
-  hipError_t e = hipMalloc(&ctx->d_stats, bytes);
-  if (e != hipSuccess) return fail(ctx, XVCGPU_OUT_OF_MEMORY, "hipMalloc", e);
-  hipMemsetAsync(ctx->d_stats, 0, bytes, ctx->stream);
-  ctx->stats_rows_cap = rows;
-  return XVCGPU_OK;
+  return grow_scratch(ctx, &ctx->d_stats, &ctx->stats_rows_cap, rows,
+                      sizeof(uint32_t) * ((size_t)kStatsHistWords + rows), true, "stats scratch");
 }
 
 xvcgpu_status xvcgpu_picture_import(xvcgpu_ctx *ctx, xvcgpu_picture *pic,
@@ -2363,13 +2340,11 @@ xvcgpu_status xvcgpu_intra_recon_waves(xvcgpu_ctx *ctx, xvcgpu_picture *rec,
   }
   if (grid < 0) return XVCGPU_UNSUPPORTED;
   // the waves' counters
-  if (ctx->intra_done_cap < n_waves) {
-    if (ctx->d_intra_done) hipFree(ctx->d_intra_done);
-    ctx->d_intra_done = nullptr;
-    ctx->intra_done_cap = 0;
-    if (hipMalloc(&ctx->d_intra_done, sizeof(int) * (size_t)(n_waves + 256)) != hipSuccess)
-      return XVCGPU_OUT_OF_MEMORY;
-    ctx->intra_done_cap = n_waves + 256;
+  if (ctx->intra_done_cap < n_waves) {   // (grown with headroom for the next picture)
+    const xvcgpu_status st =
+        grow_scratch(ctx, &ctx->d_intra_done, &ctx->intra_done_cap, n_waves + 256,
+                     sizeof(int) * (size_t)(n_waves + 256), false, "intra wave counters");
+    if (st != XVCGPU_OK) return st;
   }
   HIP_TRY(ctx, hipMemsetAsync(ctx->d_intra_done, 0, sizeof(int) * (size_t)n_waves, ctx->stream));
   int *done = ctx->d_intra_done;
@@ -2532,23 +2507,14 @@ static xvcgpu_status fp_recon_from_me(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_a
                               a->qp_y, a->qp_c, 0, a->ref_poc, a->d_nnz, a->d_cus_own);
 }
 
-// the packed quantiser, the caller's word about its blocks held for this call's batch
+// the packed quantiser; the caller's word about its blocks holds for this call's batch
 static xvcgpu_status fp_quant_rdo(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_args *a,
                                   bool classified) {
-  const int four_before = ctx->rdoq_four_lane_only;
-  xvcgpu_status st = XVCGPU_OK;
-  if (a->tx_four_lane_only && !four_before) st = xvcgpu_quant_rdo_set_four_lane_only(ctx, 1);
-  if (st == XVCGPU_OK)
-    st = classified
-             ? xvcgpu_quant_rdo_classified_batch(ctx, a->rec->bd, a->d_tx, a->n_tx, a->d_coeffs,
-                                                 a->d_level_off, a->n_coeffs, a->d_levels,
-                                                 a->d_nnz, a->d_rdoq_contexts, a->d_rdoq_params,
-                                                 a->d_cus_own)
-             : xvcgpu_quant_rdo_batch(ctx, a->rec->bd, a->d_tx, a->n_tx, a->d_coeffs,
-                                      a->d_level_off, a->n_coeffs, a->d_levels, a->d_nnz,
-                                      a->d_rdoq_contexts, a->d_rdoq_params);
-  ctx->rdoq_four_lane_only = four_before;
-  return st;
+  return quant_rdo_launch(ctx, a->rec->bd, a->d_tx, a->n_tx, a->d_coeffs, a->d_level_off,
+                          a->n_coeffs, a->d_levels, a->d_nnz, a->d_rdoq_contexts,
+                          a->d_rdoq_params, classified,
+                          ctx->rdoq_four_lane_only || a->tx_four_lane_only,
+                          classified ? a->d_cus_own : nullptr);
 }
 
 // Prediction + forward transform in one kernel: the prediction goes straight into the
@@ -2794,21 +2760,18 @@ xvcgpu_status xvcgpu_frame_pass_multi(xvcgpu_ctx *const *ctxs,
   if (rdoq) {
     // 3. the quantiser: classification, class lists, the walks
     for (int i = 0; i < n; i++) {
-      const xvcgpu_status st = ensure_rdoq_scratch(ctxs[i], args[i]->n_tx, args[i]->n_coeffs);
+      const xvcgpu_status st = ensure_rdoq_scratch(ctxs[i], args[i]->n_tx);
       if (st != XVCGPU_OK) return st;
     }
     const MultiArgs<RdoqMultiArgs> q = multi_args<RdoqMultiArgs>(
         ctxs, args, n, [](Args a, xvcgpu_ctx *c, RdoqMultiArgs &k) {
-          const int cap = c->rdoq_lists_cap;
           k.blocks = a->d_tx;
           k.n = a->n_tx;
           k.coeffs = a->d_coeffs;
           k.d_off = a->d_level_off;
           k.levels = a->d_levels;
           k.nnz_out = a->d_nnz;
-          k.l.count = c->d_rdoq_lists;
-          for (int cl = 0; cl < 3; cl++) k.l.list[cl] = c->d_rdoq_lists + 4 + (size_t)cl * cap;
-          k.l.cls = reinterpret_cast<signed char *>(c->d_rdoq_lists + 4 + 3 * (size_t)cap);
+          k.l = rdoq_lists_of(c);
           k.rq_ctx = a->d_rdoq_contexts;
           k.rq_prm = a->d_rdoq_params;
         });
@@ -2816,11 +2779,10 @@ xvcgpu_status xvcgpu_frame_pass_multi(xvcgpu_ctx *const *ctxs,
     hipLaunchKernelGGL(rdoq_classify_multi_kernel, dim3((max_tx + 3) / 4, n), dim3(256), 0,
                        ctx->stream, q, bd);
     hipLaunchKernelGGL(rdoq_compact_multi_kernel, dim3(1, n), dim3(1024), 0, ctx->stream, q);
-    const int g16 = std::min(max_tx, RDOQ_GRID16),
-              g4 = std::min((max_tx + 3) / 4, RDOQ_GRID4), g64 = std::min(max_tx, RDOQ_GRID64);
-    hipLaunchKernelGGL(quant_rdo_packed4_multi_kernel, dim3(g16 + g4, n), dim3(64), 0,
-                       ctx->stream, q, bd, g16);
-    hipLaunchKernelGGL(quant_rdo_packed_multi_kernel, dim3(g64, n), dim3(64), 0,
+    const RdoqGrids g = rdoq_walk_grids(max_tx);
+    hipLaunchKernelGGL(quant_rdo_packed4_multi_kernel, dim3(g.g16 + g.g4, n), dim3(64), 0,
+                       ctx->stream, q, bd, g.g16);
+    hipLaunchKernelGGL(quant_rdo_packed_multi_kernel, dim3(g.g64, n), dim3(64), 0,
                        ctx->stream, q, bd);
     // 4. dequantisation + inverse transform + reconstruction
     const MultiArgs<InvMultiArgs> v = multi_args<InvMultiArgs>(

@@ -87,8 +87,8 @@ struct xvcgpu_ctx {
   int rdoq_last_n;                 // blocks of the last quantiser call (xvcgpu_debug_rdoq_lists)
   int rdoq_four_lane_only;         // xvcgpu_quant_rdo_set_four_lane_only: the general class's launch is skipped
   int *h_rdoq_misuse;              // page-locked: set by the walk when such a batch held a general-class block
-  // scratch of xvcgpu_quant_rdo_batch (k_rdoq.h): the three class lists + their
-  // counters, and 26 bytes per coefficient of the batch
+  // scratch of xvcgpu_quant_rdo_batch: the three class lists, their counters, the
+  // per-block classes and the compaction's per-chunk counts (k_rdoq.h: rdoq_scratch_lists)
   int *d_rdoq_lists;
   int rdoq_lists_cap;      // in blocks
 };
