@@ -182,6 +182,121 @@ def test_planned_search_equals_sized(gpu, phases, bd):
     R.destroy()
 
 
+BIN_SHAPES = {
+    "16x16": [(16, 16)], "16x8": [(16, 8)], "8x8": [(8, 8)],
+    "other16": [(4, 4), (8, 4), (4, 16), (8, 16), (16, 4)],
+    "c32": [(32, 32), (32, 8), (16, 32)],
+    "c64_team": [(64, 64), (64, 8), (32, 64)],
+    "c64_wave": [(64, 4), (4, 64)],
+}
+BIN_SHAPES["lic16"] = [s for k in ("16x16", "16x8", "8x8", "other16") for s in BIN_SHAPES[k]]
+BIN_SHAPES["lic32"] = BIN_SHAPES["c32"]
+BIN_SHAPES["lic64"] = BIN_SHAPES["c64_team"] + BIN_SHAPES["c64_wave"]
+BIN_JOBS = 48       # at most, per list
+ME_USE_LIC = 2      # XVC_ME_USE_LIC (include/xvc_inter_bits.h; xvc_amd.api has no name for it)
+
+
+def _one_bin_list(name, pw, ph):
+    """(descriptors, the bin they fall into, LIC jobs announced): jobs of one plan bin only,
+    spread over the picture, mvp = prev = 0, range 96.  "unsupported": 12x16 jobs and LIC
+    jobs of every class that the search is not told about."""
+    lic = name.startswith("lic")
+    shapes = BIN_SHAPES["lic16"] + BIN_SHAPES["lic32"] + BIN_SHAPES["lic64"] + [(12, 16)] * 6 \
+        if name == "unsupported" else BIN_SHAPES[name]
+    n = max(len(shapes), BIN_JOBS // len(shapes) * len(shapes))
+    parts = []
+    for i in range(n):
+        w, h = shapes[i % len(shapes)]
+        parts.append(((i * 44) % (pw - w + 1) & ~3, (i * 28) % (ph - h + 1) & ~3, w, h))
+    me = me_list(parts)
+    if lic or name == "unsupported":
+        me["fullpel_mv"] = np.where(me["w"] == 12, 0, ME_USE_LIC)
+    return me, name, lic
+
+
+@pytest.fixture(scope="module", params=[10, 12])
+def one_bin_case(request, xo):
+    """The pictures and, per bin, its list with the oracle's answers (computed once)."""
+    import helpers
+    from test_gpu_parity import to_me_struct
+    bd, pw, ph = request.param, 320, 192
+    orig, ref = helpers.make_pics(np.random.default_rng(4100 + bd), bd, pw, ph, BL, (40, 26))
+    lists = []
+    for name in list(BIN_SHAPES) + ["unsupported"]:
+        me, bin_name, lic = _one_bin_list(name, pw, ph)
+        want = None
+        if name != "unsupported":
+            want = []
+            for b in me:
+                s = to_me_struct(b)
+                (fx, fy), cost = xo.tz_search(bd, s, pw, ph, orig, ref, BL)
+                (sx, sy), sd = xo.subpel_search(bd, s, pw, ph, orig, ref, BL, (fx, fy))
+                want.append((fx, fy, cost, sx, sy, sd))
+            want = np.array(want, np.int64)
+            # the step-5 grid and the record write are on the tested path: an answer 8 or
+            # more samples from the start (mvp = prev = 0) in some component
+            if not lic:
+                assert (np.abs(want[:, :2]).max(axis=1) >= 8).any(), name
+        lists.append((me, bin_name, lic, want))
+    return bd, pw, ph, orig, ref, lists
+
+
+def test_every_bin_alone(gpu, one_bin_case):
+    """Every plan bin as the only one of its search - so it is the launch that keeps the
+    straggler-first record -, every phase mask: the planned search twice with one plan (the
+    second call rotates by the record the first one wrote) and the sized search give the
+    same records; fused, they are the oracle's job by job; a job no instance takes reads
+    0xffffffff in both fields."""
+    api, ctx = gpu
+    bd, pw, ph, orig, ref, lists = one_bin_case
+    O, R = ctx.picture(pw, ph, bd), ctx.picture(pw, ph, bd)
+    O.upload([orig, None, None], BL)
+    R.upload([ref, None, None], BL)
+    names = list(api.ME_PLAN_BIN_NAMES)
+    for me, bin_name, lic, want in lists:
+        n = len(me)
+        assert n <= BIN_JOBS
+        d_me = ctx.buffer(me)
+        plan = ctx.me_plan(d_me.ptr, n, 64)
+        if want is None:    # (the plan bins a LIC job as such: who was told is the search's)
+            assert plan.counts[names.index("lic16"):].sum() == n and \
+                plan.counts[names.index("unsupported")] > 0, plan.counts
+        else:
+            assert plan.counts[names.index(bin_name)] == n, (bin_name, plan.counts)
+        start = np.zeros(n, api.MERES_DTYPE)
+        rng = np.random.default_rng(11)
+        start["fullpel_x"], start["fullpel_y"] = rng.integers(-8, 9, n), rng.integers(-8, 9, n)
+        start["fullpel_cost"], start["subpel_dist"] = 0x55555555, 0x66666666
+        for flags in (api.ME_FULLPEL | api.ME_SUBPEL, api.ME_FULLPEL, api.ME_SUBPEL):
+            fl = flags | (api.ME_LIC_JOBS if lic else 0)
+            got = []
+            for form in ("planned", "planned again", "sized"):
+                d_r = ctx.buffer(start)
+                if form == "sized":
+                    ctx.me_search_dev(O, R, fl, d_me.ptr, n, d_r.ptr, 64)
+                else:
+                    ctx.me_search_planned(O, R, fl, plan, d_r.ptr)
+                ctx.sync()
+                got.append(d_r.to_array(api.MERES_DTYPE, n))
+                d_r.free()
+            for form, g in zip(("planned again", "sized"), got[1:]):
+                bad = np.nonzero(g != got[0])[0]
+                assert len(bad) == 0, (bin_name, flags, form, bad[:8], got[0][bad[:4]], g[bad[:4]])
+            g = got[0]
+            if want is None:
+                assert (g["fullpel_cost"] == 0xffffffff).all(), (bin_name, flags)
+                assert (g["subpel_dist"] == 0xffffffff).all(), (bin_name, flags)
+            elif flags == api.ME_FULLPEL | api.ME_SUBPEL:
+                cols = ("fullpel_x", "fullpel_y", "fullpel_cost", "mv_x", "mv_y", "subpel_dist")
+                have = np.stack([g[c].astype(np.int64) for c in cols], axis=1)
+                bad = np.nonzero((have != want).any(axis=1))[0]
+                assert len(bad) == 0, (bin_name, bad[:8], have[bad[:4]], want[bad[:4]], me[bad[:4]])
+        plan.destroy()
+        d_me.free()
+    O.destroy()
+    R.destroy()
+
+
 def _run_partition_pass(api, ctx, xo, name, pic, bd, qp, rdoq, check_steps=False):
     import oracle_frame
     from xvc_amd import pipeline, synth

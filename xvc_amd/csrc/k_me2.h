@@ -930,6 +930,30 @@ __device__ __forceinline__ int me2_rotated_wg(int block, int n_wg, const Me2Rot 
   return base + local;
 }
 
+// The reference's ordered strict-< fold of a sub-pel pass = (lowest cost, lowest index in
+// issue order), one candidate per lane: dist[lane] its raw sum, oi its index in issue order.
+// By every wave of a team alike (same inputs, same result).
+__device__ __forceinline__ void me2_subpel_fold(const MeCtx &c, const xvcgpu_me_block &b,
+                                                const uint32_t *dist, int pass, int oi,
+                                                int base_x, int base_y, uint32_t &best_cost,
+                                                uint32_t &best_dist, int &best_x, int &best_y) {
+  const int lane = ME2_LANE;
+  uint32_t my_cost = 0xffffffffu, my_dist = 0;
+  if (lane < 9 - pass) {
+    int mx, my;
+    me2_subpel_mv(pass, oi, base_x, base_y, mx, my);
+    my_dist = dist[lane] >> (c.bd - 8);
+    my_cost = my_dist + ((c.lambda * d_mvd_bits(b.mvp_x, b.mvp_y, mx, my, 0)) >> 16);
+  }
+  const uint32_t gmin = wave_min_key(my_cost);
+  const uint32_t gk = wave_min_key(my_cost == gmin ? ((uint32_t)oi << 8) | (uint32_t)lane : 0xffffu);
+  if (gmin < best_cost) {
+    best_cost = gmin;
+    best_dist = (uint32_t)__builtin_amdgcn_readlane((int)my_dist, (int)(gk & 63u));
+    me2_subpel_mv(pass, (int)(gk >> 8), base_x, base_y, best_x, best_y);
+  }
+}
+
 // grid: ceil(n / waves) workgroups (padded to 8); block: ME2_WAVES(MS) waves, one
 // job per wave.  Handles the jobs whose block fits class MS (max(w,h) <= MS)
 // and no smaller class.
@@ -1331,22 +1355,7 @@ me2_search_job(Shared &s, const PicView &orig, const PicView &ref, const xvcgpu_
         best_dist = s.dist[0] >> (c.bd - 8);
         break;
       }
-      // the reference's ordered strict-< fold = (lowest cost, lowest index in issue order),
-      // one candidate per lane
-      uint32_t my_cost = 0xffffffffu, my_dist = 0;
-      if (lane < n) {
-        int mx, my;
-        me2_subpel_mv(pass, oi, base_x, base_y, mx, my);
-        my_dist = s.dist[lane] >> (c.bd - 8);
-        my_cost = my_dist + ((c.lambda * d_mvd_bits(b.mvp_x, b.mvp_y, mx, my, 0)) >> 16);
-      }
-      const uint32_t gmin = wave_min_key(my_cost);
-      const uint32_t gk = wave_min_key(my_cost == gmin ? ((uint32_t)oi << 8) | (uint32_t)lane : 0xffffu);
-      if (gmin < best_cost) {
-        best_cost = gmin;
-        best_dist = (uint32_t)__builtin_amdgcn_readlane((int)my_dist, (int)(gk & 63u));
-        me2_subpel_mv(pass, (int)(gk >> 8), base_x, base_y, best_x, best_y);
-      }
+      me2_subpel_fold(c, b, s.dist, pass, oi, base_x, base_y, best_cost, best_dist, best_x, best_y);
     }
     res.mv_x = best_x;
     res.mv_y = best_y;
@@ -1358,9 +1367,10 @@ me2_search_job(Shared &s, const PicView &orig, const PicView &ref, const xvcgpu_
   if (lane == 0) results[bi] = res;
 }
 
-// Who takes a job (me_search_wave_take, and the search plan of k_me_plan.h): a job no
-// instance of the call takes (a size the search does not have, or larger than the caller's
-// max_block_size, or a LIC job nobody announced) is answered with the
+// Who takes a job - the one size and class test of the search (me_search_wave_take, the
+// team body, and the plan's bins in k_me_plan.h; the table of DESIGN.md section 8): a job
+// no instance of the call takes (a size the search does not have, or larger than the
+// caller's max_block_size, or a LIC job nobody announced) is answered with the
 // XVCGPU_ME_UNSUPPORTED record instead of being left as it was.
 struct Me2JobClass {
   bool valid, lic;
@@ -1375,6 +1385,12 @@ __device__ __forceinline__ Me2JobClass me2_job_class(const xvcgpu_me_block &b, i
   c.valid = pow2 && b.w >= 4 && b.h >= 4 && b.w <= 64 && b.h <= 64 && c.mx <= max_launched &&
             (!c.lic || lic_launched);
   return c;
+}
+__device__ __forceinline__ xvcgpu_me_result me2_unsupported_record() {
+  xvcgpu_me_result r;
+  r.fullpel_x = r.fullpel_y = r.mv_x = r.mv_y = 0;
+  r.fullpel_cost = r.subpel_dist = 0xffffffffu;
+  return r;
 }
 
 // Job bi of a search call by this wave: the descriptor read and checked, the instance
@@ -1397,12 +1413,7 @@ me_search_wave_take(Shared &s, const PicView &orig, const PicView &ref,
     const bool lic = jc.lic, valid = jc.valid;
     if (lic != LIC && valid) return;  // the other set of instances
     if (MS == 16 && !LIC && !valid) {
-      if (ME2_LANE == 0) {
-        xvcgpu_me_result r;
-        r.fullpel_x = r.fullpel_y = r.mv_x = r.mv_y = 0;
-        r.fullpel_cost = r.subpel_dist = 0xffffffffu;
-        results[bi] = r;
-      }
+      if (ME2_LANE == 0) results[bi] = me2_unsupported_record();
       return;
     }
     if (!valid || mx > MS || (MS > 16 && mx <= MS / 2)) return;  // other class
@@ -1421,16 +1432,40 @@ me_search_wave_take(Shared &s, const PicView &orig, const PicView &ref,
   else if (SEL != 1)
     me2_search_job<MS, PH, LIC, 0, 0>(s, orig, ref, b, bi, results, tz_pattern, sched, chunk, local,
                                       refs, slots);
-  else if (only && ME2_LANE == 0) {  // XVCGPU_ME_ONLY_SQ16: nobody else takes it
-    xvcgpu_me_result r;
-    r.fullpel_x = r.fullpel_y = r.mv_x = r.mv_y = 0;
-    r.fullpel_cost = r.subpel_dist = 0xffffffffu;
-    results[bi] = r;
-  }
+  else if (only && ME2_LANE == 0)  // XVCGPU_ME_ONLY_SQ16: nobody else takes it
+    results[bi] = me2_unsupported_record();
 }
 
+// A wave's entry into a search launch over n slots, one slot per wave: its LDS slice, its
+// slot (false: none - a padding workgroup) and where it sits (chunk = the XCD, local = the
+// workgroup's place in that XCD's share: what the straggler-first record counts).  grid:
+// ceil(n / waves) workgroups padded to 8, XCD-swizzled and rotated; block: ME2_WAVES(MS)
+// waves.  Workgroup 0 resets the third record where the launch was given one.
+template <int MS, int PH, bool LIC>
+__device__ __forceinline__ bool
+me2_wave_entry(int n, const Me2Sched &sched, Me2SharedT<MS, (PH & XVCGPU_ME_SUBPEL) != 0> *&s,
+               int &slot, int &chunk, int &local) {
+  constexpr int WPG = ME2_WAVES(MS);
+  constexpr bool kSched = !LIC && (PH & XVCGPU_ME_FULLPEL) != 0;
+  __shared__ Me2SharedT<MS, (PH & XVCGPU_ME_SUBPEL) != 0> s_all[WPG];
+  // one wave per workgroup: the lane number is threadIdx.x itself (one register, not two)
+  if (WPG == 1) __builtin_assume(threadIdx.x < 64u);
+  s = &s_all[threadIdx.x >> 6];
+  const int n_wg = (n + WPG - 1) / WPG;
+  int len;
+  const int wg = me2_rotated_wg(blockIdx.x, n_wg, kSched ? sched.use : nullptr, chunk, local,
+                                len);
+  if (kSched && sched.clear && blockIdx.x == 0 && threadIdx.x < 8)
+    sched.clear->first[threadIdx.x] = 0x7fffffff;
+  if (wg < 0) return false;
+  // the slot is the same in all lanes of the wave: tell the compiler, so that the
+  // descriptor and everything derived from it sits in scalar registers (it cost a dozen
+  // VGPRs and, under the 128-register cap, five spilled dwords)
+  slot = __builtin_amdgcn_readfirstlane(wg * WPG + (int)(threadIdx.x >> 6));
+  return slot < n;
+}
 
-
+// Slot = job index; the wave takes the job or leaves it (me_search_wave_take).
 template <int MS, int PH, bool LIC = false, int SEL = 0>
 __device__ __forceinline__ void
 me_search_wave_body(const PicView &orig, const PicView &ref,
@@ -1439,29 +1474,17 @@ me_search_wave_body(const PicView &orig, const PicView &ref,
                     Me2Sched sched, int max_launched, bool lic_launched,
                     const RefTable *refs = nullptr, const uint8_t *slots = nullptr,
                     bool only = false) {
-  constexpr int WPG = ME2_WAVES(MS);
-  constexpr bool kSched = !LIC && (PH & XVCGPU_ME_FULLPEL) != 0;
-  typedef Me2SharedT<MS, (PH & XVCGPU_ME_SUBPEL) != 0> Shared;
-  __shared__ Shared s_all[WPG];
-  // one wave per workgroup: the lane number is threadIdx.x itself (one register, not two)
-  if (WPG == 1) __builtin_assume(threadIdx.x < 64u);
-  Shared &s = s_all[threadIdx.x >> 6];
-  // job = (workgroup, wave); workgroups are XCD-swizzled and rotated
-  const int n_wg = (n + WPG - 1) / WPG;
-  int chunk, local, len;
-  const int wg = me2_rotated_wg(blockIdx.x, n_wg, kSched ? sched.use : nullptr, chunk, local,
-                                len);
-  if (kSched && blockIdx.x == 0 && threadIdx.x < 8) sched.clear->first[threadIdx.x] = 0x7fffffff;
-  if (wg < 0) return;
-  // the job index is the same in all lanes of the wave: tell the compiler, so
-  // that the descriptor and everything derived from it sits in scalar registers
-  // (it cost a dozen VGPRs and, under the 128-register cap, five spilled dwords)
-  const int bi = __builtin_amdgcn_readfirstlane(wg * WPG + (int)(threadIdx.x >> 6));
-  if (bi >= n) return;
-  me_search_wave_take<MS, PH, LIC, SEL>(s, orig, ref, blocks, bi, results, tz_pattern, sched, chunk,
+  // Every launch that comes through here with a full-pel instance carries the context's
+  // schedule (me_sched_next): xvcgpu_me_search_sized and _refs with XVCGPU_ME_FULLPEL, the
+  // multi kernel, the engine's segments.  Only a plan's launches (me_plan_wave_body) may
+  // come without - so the entry's null test folds away here, as on a caller's word.
+  if (!LIC && (PH & XVCGPU_ME_FULLPEL) != 0) __builtin_assume(sched.clear != nullptr);
+  Me2SharedT<MS, (PH & XVCGPU_ME_SUBPEL) != 0> *s;
+  int bi, chunk, local;
+  if (!me2_wave_entry<MS, PH, LIC>(n, sched, s, bi, chunk, local)) return;
+  me_search_wave_take<MS, PH, LIC, SEL>(*s, orig, ref, blocks, bi, results, tz_pattern, sched, chunk,
                                         local, max_launched, lic_launched, refs, slots, only);
 }
-
 
 template <int MS, int PH, bool LIC = false, int SEL = 0>
 __global__ void __launch_bounds__(64 * ME2_WAVES(MS), ME2_MIN_WAVES(MS))
@@ -1475,7 +1498,10 @@ me_search_wave_kernel(PicView orig, PicView ref,
 
 // The exact-shape jobs of the 16 class (16x16, 16x8), both phases, in a kernel of their own
 // for a job list that is (almost) all such CUs - a picture's frame pass: with the block
-// size compiled in the job fits 96 registers, five waves per SIMD instead of four; the
+// size compiled in the job fits 96 registers, five waves per SIMD instead of four (6864 B
+// LDS, scratch 164 B / lane: 77 spilled VGPRs; the any-size me_search_wave_kernel<16, 3>:
+// 128 registers, four waves, scratch 140 B / lane; hipcc
+// -Rpass-analysis=kernel-resource-usage, gfx950); the
 // spilled registers sit in the step-5 grid loop, which one job in thousands runs (with
 // the any-size instance in the same kernel the allocator spilled the lane number and
 // the descriptor at the kernel's entry: 7.5 MB of scratch writes per 1080p launch).
@@ -1568,14 +1594,11 @@ me_subpel_team_body(const PicView &orig, const PicView &ref, const xvcgpu_me_blo
   if (bi < 0) return;
   if (order) bi = order[bi];   // the slots of a plan's bin (k_me_plan.h)
   const xvcgpu_me_block b = blocks[bi];
-  {
-    const int mx = b.w > b.h ? b.w : b.h;
-    const bool pow2 = (b.w & (b.w - 1)) == 0 && (b.h & (b.h - 1)) == 0;
-    if (!pow2 || mx > MS || mx <= MS / 2 ||
-        !me2_subpel_fast(b.w, b.h, orig.bd, (b.fullpel_mv & XVC_ME_USE_LIC) != 0))
-      return;
+  {  // the jobs of class MS on the packed path (me2_job_class: a LIC job is not valid here)
+    const Me2JobClass jc = me2_job_class(b, MS, false);
+    if (!jc.valid || jc.mx <= MS / 2 || !me2_subpel_fast(b.w, b.h, orig.bd)) return;
   }
-  const int tid = threadIdx.x, lane = ME2_LANE;
+  const int tid = threadIdx.x;
   int slot = 0;
   if (slots) {
     slot = __builtin_amdgcn_readfirstlane((int)slots[bi]);
@@ -1633,23 +1656,9 @@ me_subpel_team_body(const PicView &orig, const PicView &ref, const xvcgpu_me_blo
     int best_x = res.mv_x, best_y = res.mv_y;
     for (int pass = 0; pass < 2; pass++) {
       const int base_x = best_x, base_y = best_y;
-      const int nc = 9 - pass;
       const int oi = me2_subpel_fast_pass<MS, NW>(s, c, b, pic_w, pic_h, fpx, fpy, pass, base_x,
                                                   base_y, held ME2_CLK_PASS);
-      uint32_t my_cost = 0xffffffffu, my_dist = 0;
-      if (lane < nc) {
-        int mx, my;
-        me2_subpel_mv(pass, oi, base_x, base_y, mx, my);
-        my_dist = s.dist[lane] >> (c.bd - 8);
-        my_cost = my_dist + ((c.lambda * d_mvd_bits(b.mvp_x, b.mvp_y, mx, my, 0)) >> 16);
-      }
-      const uint32_t gmin = wave_min_key(my_cost);
-      const uint32_t gk = wave_min_key(my_cost == gmin ? ((uint32_t)oi << 8) | (uint32_t)lane : 0xffffu);
-      if (gmin < best_cost) {
-        best_cost = gmin;
-        best_dist = (uint32_t)__builtin_amdgcn_readlane((int)my_dist, (int)(gk & 63u));
-        me2_subpel_mv(pass, (int)(gk >> 8), base_x, base_y, best_x, best_y);
-      }
+      me2_subpel_fold(c, b, s.dist, pass, oi, base_x, base_y, best_cost, best_dist, best_x, best_y);
     }
     res.mv_x = best_x;
     res.mv_y = best_y;

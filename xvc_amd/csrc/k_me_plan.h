@@ -10,15 +10,14 @@
 // 64-jobs-per-wave leftover kernel for everything of the 16 class that is not 16x16 / 16x8.
 // A pass's descriptors are fixed when the pass is built, so they are sorted then.
 //
-// Bins (XVCGPU_ME_PLAN_*, xvcgpu_types.h): the exact shapes 16x16, 16x8, 8x8; the other
-// jobs of the 16 class; the 32 class; the 64 class split into the jobs the sub-pel team
-// kernel takes (both sides >= 8) and the rest; the XVC_ME_USE_LIC jobs by class; the jobs
-// no instance takes.  The classification is me_search_wave_take's (me2_job_class, k_me2.h).
+// Bins (XVCGPU_ME_PLAN_*, xvcgpu_types.h), their instances and launches: the table of
+// DESIGN.md section 8.  The classification is me2_job_class's (k_me2.h).
 //
 // The instances are me2_search_job's (k_me2.h); new here: the entry that reads its job
-// through the bin's list, the 8x8 exact-shape instance and the kernel that answers the
-// last bin.  Resources of the exact-shape instances (both phases, one wave per
-// workgroup, launch bound 5 waves per SIMD as me_search_sq16_kernel; hipcc
+// through the bin's list (after me2_wave_entry, the wave entry it shares with the sized
+// form), the 8x8 exact-shape instance and the kernel that answers the last bin.
+// Resources of the exact-shape instances (both phases, one wave per workgroup, launch
+// bound 5 waves per SIMD as me_search_sq16_kernel; hipcc
 // -Rpass-analysis=kernel-resource-usage, gfx950):
 //   me_plan_kernel<16, 3, false, 16, 16>  96 VGPRs, 5 waves / SIMD, 6864 B LDS, scratch 152 B / lane
 //   me_plan_kernel<16, 3, false, 16, 8>   96 VGPRs, 5 waves / SIMD, 6864 B LDS, scratch 148 B / lane
@@ -119,34 +118,21 @@ me_plan_kernel_build(const xvcgpu_me_block *blocks, int n, int max_launched, int
   }
 }
 
-// Slots [0, n) of `order` by one wave each: the job index read through the list, the
-// class and the shape are the plan's word (no test here).  Grid, XCD chunking and the
-// straggler-first rotation as me_search_wave_body, over the bin's own count.
+// Slots [0, n) of `order` by one wave each (me2_wave_entry over the bin's own count): the
+// job index read through the list, the class and the shape are the plan's word (no test).
 // FW, FH > 0: the exact-shape instance.
 template <int MS, int PH, bool LIC, int FW, int FH>
 __device__ __forceinline__ void
 me_plan_wave_body(const PicView &orig, const PicView &ref, const xvcgpu_me_block *blocks,
                   const int *order, int n, xvcgpu_me_result *results, const TzCand *tz_pattern,
                   Me2Sched sched) {
-  constexpr int WPG = ME2_WAVES(MS);
-  constexpr bool kSched = !LIC && (PH & XVCGPU_ME_FULLPEL) != 0;
-  typedef Me2SharedT<MS, (PH & XVCGPU_ME_SUBPEL) != 0> Shared;
-  __shared__ Shared s_all[WPG];
-  if (WPG == 1) __builtin_assume(threadIdx.x < 64u);
-  Shared &s = s_all[threadIdx.x >> 6];
-  const int n_wg = (n + WPG - 1) / WPG;
-  int chunk, local, len;
-  const int wg = me2_rotated_wg(blockIdx.x, n_wg, kSched ? sched.use : nullptr, chunk, local,
-                                len);
-  if (kSched && sched.clear && blockIdx.x == 0 && threadIdx.x < 8)
-    sched.clear->first[threadIdx.x] = 0x7fffffff;
-  if (wg < 0) return;
-  const int slot = __builtin_amdgcn_readfirstlane(wg * WPG + (int)(threadIdx.x >> 6));
-  if (slot >= n) return;
+  Me2SharedT<MS, (PH & XVCGPU_ME_SUBPEL) != 0> *s;
+  int slot, chunk, local;
+  if (!me2_wave_entry<MS, PH, LIC>(n, sched, s, slot, chunk, local)) return;
   // wave-uniform: the descriptor and what derives from it stay in scalar registers
   const int bi = __builtin_amdgcn_readfirstlane(order[slot]);
   const xvcgpu_me_block b = blocks[bi];
-  me2_search_job<MS, PH, LIC, FW, FH>(s, orig, ref, b, bi, results, tz_pattern, sched, chunk,
+  me2_search_job<MS, PH, LIC, FW, FH>(*s, orig, ref, b, bi, results, tz_pattern, sched, chunk,
                                       local, nullptr, nullptr);
 }
 
@@ -171,10 +157,7 @@ __global__ void __launch_bounds__(256)
 me_plan_unsupported_kernel(const int *order, int n, xvcgpu_me_result *results) {
   const int slot = (int)(blockIdx.x * 256 + threadIdx.x);
   if (slot >= n) return;
-  xvcgpu_me_result r;
-  r.fullpel_x = r.fullpel_y = r.mv_x = r.mv_y = 0;
-  r.fullpel_cost = r.subpel_dist = 0xffffffffu;
-  results[order[slot]] = r;
+  results[order[slot]] = me2_unsupported_record();
 }
 
 #endif  // XVCGPU_K_ME_PLAN_H_

@@ -233,6 +233,84 @@ MultiArgs<T> multi_args(xvcgpu_ctx *const *ctxs, const xvcgpu_frame_pass_args *c
   return m;
 }
 
+// one wave per job, ME2_WAVES(MS) of them a workgroup: the workgroups padded to 8 (the XCDs)
+dim3 me2_grid(int n, int waves, unsigned y = 1) {
+  const int n_wg = (n + waves - 1) / waves;
+  return dim3((n_wg + 7) / 8 * 8, y);
+}
+// the sub-pel team: one workgroup per job, padded likewise
+dim3 me_team_grid(int n, unsigned y = 1) { return dim3((n + 7) / 8 * 8, y); }
+
+// An instance of the search kernels: the class, the phases compiled in, LIC or not.
+template <int MS_, int PH_, bool LIC_>
+struct MeInst { static constexpr int MS = MS_, PH = PH_; static constexpr bool LIC = LIC_; };
+// The launches of class MS for the phases PHASES, LIC or not, in order (the table of
+// DESIGN.md section 8): wave(MeInst) per wave instance, team() for the four-wave team.
+// - The 16 class runs both phases fused (measured faster than two launches: waves in the
+//   latency-bound full-pel search overlap waves in the VALU-bound sub-pel search on the same
+//   SIMD); a single-phase call gets an instance with only that phase's registers and LDS.
+// - Every other class, and every LIC job, gets one launch per phase: the larger classes'
+//   sub-pel instance holds 23 / 76 KB of LDS per wave (one workgroup per CU), and fused with
+//   it the full-pel search runs at that occupancy too (32x32: 36 + 64 us apart, 120 us fused;
+//   32x16: 38 + 112 vs 198; tools/time_me_classes.py).
+// - The 64 class's jobs on the packed sub-pel path go to the team; its <64, SUBPEL> wave
+//   instance leaves those alone.
+template <int MS, int PHASES, bool LIC, class Wave, class Team>
+void me_class_launches(Wave &&wave, Team &&team) {
+  if constexpr (MS == 16 && !LIC && PHASES == 3) {
+    wave(MeInst<16, 3, false>());
+  } else {
+    if constexpr ((PHASES & XVCGPU_ME_FULLPEL) != 0) wave(MeInst<MS, XVCGPU_ME_FULLPEL, LIC>());
+    if constexpr ((PHASES & XVCGPU_ME_SUBPEL) != 0) {
+      wave(MeInst<MS, XVCGPU_ME_SUBPEL, LIC>());
+      if constexpr (MS == 64 && !LIC) team();
+    }
+  }
+}
+// (the class, then the phases too, as run-time values; another class: nothing)
+template <int PHASES, bool LIC, class Wave, class Team>
+void me_launches_of(int cls, Wave &&wave, Team &&team) {
+  if (cls == 16) me_class_launches<16, PHASES, LIC>(wave, team);
+  else if (cls == 32) me_class_launches<32, PHASES, LIC>(wave, team);
+  else if (cls == 64) me_class_launches<64, PHASES, LIC>(wave, team);
+}
+template <bool LIC, class Wave, class Team>
+void me_launches(int cls, int ph, Wave &&wave, Team &&team) {
+  if (ph == 3) me_launches_of<3, LIC>(cls, wave, team);
+  else if (ph == XVCGPU_ME_FULLPEL) me_launches_of<XVCGPU_ME_FULLPEL, LIC>(cls, wave, team);
+  else if (ph == XVCGPU_ME_SUBPEL) me_launches_of<XVCGPU_ME_SUBPEL, LIC>(cls, wave, team);
+}
+
+// Is instance <ms, inst_ph, lic> (inst_ph 0: the team) among its class's launches for ph?
+bool me_class_has(int ms, bool lic, int ph, int inst_ph) {
+  bool has = false;
+  auto wave = [&](auto inst) { has |= decltype(inst)::PH == inst_ph; };
+  auto team = [&] { has |= inst_ph == 0; };
+  if (lic) me_launches<true>(ms, ph, wave, team);
+  else me_launches<false>(ms, ph, wave, team);
+  return has;
+}
+
+// What one planned search hands to its launches, and a launch over slots [at, at + cnt)
+struct MePlanCall {
+  hipStream_t stream;
+  PicView orig, ref;
+  const xvcgpu_me_block *blocks;
+  const int *order;
+  xvcgpu_me_result *results;
+  const TzCand *tz_pattern;
+};
+template <int MS, int PH, bool LIC, int FW = 0, int FH = 0>
+void me_plan_launch(const MePlanCall &c, int at, int cnt, const Me2Sched &sched) {
+  hipLaunchKernelGGL((me_plan_kernel<MS, PH, LIC, FW, FH>), me2_grid(cnt, ME2_WAVES(MS)),
+                     dim3(64 * ME2_WAVES(MS)), 0, c.stream, c.orig, c.ref, c.blocks, c.order + at,
+                     cnt, c.results, c.tz_pattern, sched);
+}
+void me_plan_launch_team(const MePlanCall &c, int at, int cnt, const Me2Sched &) {
+  hipLaunchKernelGGL((me_plan_team_kernel<64, 4>), me_team_grid(cnt), dim3(256), 0, c.stream,
+                     c.orig, c.ref, c.blocks, c.order + at, cnt, c.results);
+}
+
 }  // namespace
 
 extern "C" {
@@ -814,11 +892,6 @@ xvcgpu_status xvcgpu_mc_metric_batch(xvcgpu_ctx *ctx, const xvcgpu_picture *orig
   return XVCGPU_OK;
 }
 
-static dim3 me2_grid(int n, int waves) {
-  const int n_wg = (n + waves - 1) / waves;
-  return dim3((n_wg + 7) / 8 * 8);
-}
-
 // the search's block class: the smallest of 16 / 32 / 64 that holds max_block_size
 static int me_class_of(int max_block_size) {
   return max_block_size > 32 ? 64 : (max_block_size > 16 ? 32 : 16);
@@ -843,80 +916,43 @@ xvcgpu_status xvcgpu_me_search_sized(xvcgpu_ctx *ctx, const xvcgpu_picture *orig
   if (orig->w != ref->w || orig->h != ref->h || orig->bd != ref->bd)
     return fail(ctx, XVCGPU_INVALID_ARGUMENT, "picture mismatch");
   if (n == 0) return XVCGPU_OK;
-  // one wave per job; the LDS footprint is a compile-time function of the
-  // block-size class, each class kernel skips the jobs of the other classes.
-  // The phases are compile-time instances: a single-phase call gets a kernel
-  // with only that phase's registers and LDS; the usual both-phases call runs
-  // the fused instance (measured faster than two launches: waves in the
-  // latency-bound full-pel search overlap waves in the VALU-bound sub-pel
-  // search on the same SIMD).
+  // every class kernel runs over the whole list and skips the jobs of the other classes
   Me2Sched sched = {nullptr, nullptr, nullptr};
   if (flags & XVCGPU_ME_FULLPEL) sched = me_sched_next(ctx);
+  const int ml = me_class_of(max_block_size), ph = flags & 3;
   const bool lic_jobs = (flags & XVCGPU_ME_LIC_JOBS) != 0;
-  // (the caller's word only counts where it can be kept: both phases, the 16 class alone)
-  const bool only_sq16 = (flags & XVCGPU_ME_ONLY_SQ16) && (flags & 3) == 3 && max_block_size <= 16;
-#define ME_LAUNCH_T(MS, PH, LIC)                                                        \
-  hipLaunchKernelGGL((me_search_wave_kernel<MS, PH, LIC>), me2_grid(n, ME2_WAVES(MS)),  \
-                     dim3(64 * ME2_WAVES(MS)), 0, ctx->stream, orig->v, ref->v,         \
-                     d_blocks, n, d_results, ctx->d_tz_pattern, sched,                  \
-                     me_class_of(max_block_size), lic_jobs)
-#define ME_LAUNCH(MS, PH) ME_LAUNCH_T(MS, PH, false)
-  // jobs of CUs that try local illumination compensation (XVC_ME_USE_LIC): their
-  // own instances, the two phases as two launches
-#define ME_LAUNCH_LIC(MS)                                        \
-  do {                                                           \
-    if (flags & XVCGPU_ME_FULLPEL) ME_LAUNCH_T(MS, 1, true);     \
-    if (flags & XVCGPU_ME_SUBPEL) ME_LAUNCH_T(MS, 2, true);      \
-  } while (0)
-#define ME_LAUNCH_SQ16()                                                                \
-  do {                                                                                  \
-    const int ml = me_class_of(max_block_size);                                         \
-    hipLaunchKernelGGL(me_search_sq16_kernel, me2_grid(n, ME2_WAVES(16)),                \
-                       dim3(64 * ME2_WAVES(16)), 0, ctx->stream, orig->v, ref->v,       \
-                       d_blocks, n, d_results, ctx->d_tz_pattern, sched, ml, lic_jobs,  \
-                       only_sq16);                                                      \
-    if (!only_sq16)                                                                     \
-      hipLaunchKernelGGL(me_search_leftover_kernel, dim3((n + 63) / 64), dim3(64), 0,    \
-                         ctx->stream, orig->v, ref->v, d_blocks, n, d_results,          \
-                         ctx->d_tz_pattern, ml, lic_jobs);                              \
-  } while (0)
-#define ME_LAUNCH_CLASS(MS)                                \
-  do {                                                     \
-    if ((flags & 3) == 3 && MS == 16 && (flags & (XVCGPU_ME_HINT_SQ16 | XVCGPU_ME_ONLY_SQ16))) \
-      ME_LAUNCH_SQ16();                                                                  \
-    else if ((flags & 3) == 3) ME_LAUNCH(MS, 3);           \
-    else if (flags & XVCGPU_ME_FULLPEL) ME_LAUNCH(MS, 1);  \
-    else ME_LAUNCH(MS, 2);                                 \
-  } while (0)
-  // The larger classes run the two phases as two launches: their sub-pel
-  // instance holds 23 / 76 KB of LDS per wave (one workgroup per CU), and fused
-  // with it the full-pel search runs at that occupancy too (32x32: 36 + 64 us
-  // apart, 120 us fused; 32x16: 38 + 112 vs 198; tools/time_me_classes.py).
-#define ME_LAUNCH_SPLIT(MS)                                \
-  do {                                                     \
-    if (flags & XVCGPU_ME_FULLPEL) ME_LAUNCH(MS, 1);       \
-    if (flags & XVCGPU_ME_SUBPEL) ME_LAUNCH(MS, 2);        \
-  } while (0)
-  ME_LAUNCH_CLASS(16);
-  if (max_block_size > 16) ME_LAUNCH_SPLIT(32);
-  if (max_block_size > 32) {
-    ME_LAUNCH_SPLIT(64);
-    // 64-class jobs on the packed sub-pel path: a team of four waves per job
-    // (the <64, SUBPEL> wave instance above leaves those to it)
-    if (flags & XVCGPU_ME_SUBPEL)
-      hipLaunchKernelGGL((me_subpel_team_kernel<64, 4>), dim3((n + 7) / 8 * 8), dim3(256), 0,
-                         ctx->stream, orig->v, ref->v, d_blocks, n, d_results);
-  }
-  if (lic_jobs) {
-    ME_LAUNCH_LIC(16);
-    if (max_block_size > 16) ME_LAUNCH_LIC(32);
-    if (max_block_size > 32) ME_LAUNCH_LIC(64);
-  }
-#undef ME_LAUNCH_LIC
-#undef ME_LAUNCH_SPLIT
-#undef ME_LAUNCH_CLASS
-#undef ME_LAUNCH
-#undef ME_LAUNCH_T
+  // The sized form's own: the fused 16-class launch as the exact-shape kernel plus the
+  // leftover kernel (XVCGPU_ME_HINT_SQ16), or the exact-shape kernel alone
+  // (XVCGPU_ME_ONLY_SQ16 - the caller's word only counts where it can be kept: both
+  // phases, the 16 class alone).
+  const bool sq16 = (flags & (XVCGPU_ME_HINT_SQ16 | XVCGPU_ME_ONLY_SQ16)) != 0;
+  const bool only_sq16 = (flags & XVCGPU_ME_ONLY_SQ16) && ph == 3 && max_block_size <= 16;
+  auto wave = [&](auto inst) {
+    typedef decltype(inst) I;
+    const dim3 grid = me2_grid(n, ME2_WAVES(I::MS)), block(64 * ME2_WAVES(I::MS));
+    if constexpr (I::MS == 16 && I::PH == 3 && !I::LIC) {
+      if (sq16) {
+        hipLaunchKernelGGL(me_search_sq16_kernel, grid, block, 0, ctx->stream, orig->v, ref->v,
+                           d_blocks, n, d_results, ctx->d_tz_pattern, sched, ml, lic_jobs,
+                           only_sq16);
+        if (!only_sq16)
+          hipLaunchKernelGGL(me_search_leftover_kernel, dim3((n + 63) / 64), dim3(64), 0,
+                             ctx->stream, orig->v, ref->v, d_blocks, n, d_results,
+                             ctx->d_tz_pattern, ml, lic_jobs);
+        return;
+      }
+    }
+    hipLaunchKernelGGL((me_search_wave_kernel<I::MS, I::PH, I::LIC>), grid, block, 0,
+                       ctx->stream, orig->v, ref->v, d_blocks, n, d_results, ctx->d_tz_pattern,
+                       sched, ml, lic_jobs);
+  };
+  auto team = [&] {
+    hipLaunchKernelGGL((me_subpel_team_kernel<64, 4>), me_team_grid(n), dim3(256), 0,
+                       ctx->stream, orig->v, ref->v, d_blocks, n, d_results);
+  };
+  for (int cls = 16; cls <= ml; cls *= 2) me_launches<false>(cls, ph, wave, team);
+  // jobs of CUs that try local illumination compensation (XVC_ME_USE_LIC): their own instances
+  for (int cls = 16; lic_jobs && cls <= ml; cls *= 2) me_launches<true>(cls, ph, wave, team);
   CHECK_LAUNCH(ctx, "me_search");
   return XVCGPU_OK;
 }
@@ -1029,6 +1065,38 @@ void xvcgpu_me_plan_destroy(xvcgpu_ctx *ctx, xvcgpu_me_plan *plan) {
   delete plan;
 }
 
+// The planned search's launches, in launch order: one row per (bins, instance).  A row runs
+// where me_class_launches has its instance among the class's launches for the asked
+// phases - the exact-shape rows with the fused call only, the whole 16 class through the
+// any-size instance with a single phase -, its depth condition holds and its bins have jobs.
+struct MePlanRow {
+  int first, end;   // the bins [first, end)
+  int ms, ph;       // the instance: class, phases (3 fused, 1 full-pel, 2 sub-pel; 0: the team)
+  bool lic;
+  int depth;        // 0: any bit depth; 1: up to 10 bit (me2_subpel_fast); -1: above
+  void (*launch)(const MePlanCall &c, int at, int cnt, const Me2Sched &sched);
+};
+static const MePlanRow kMePlanRows[] = {
+    {XVCGPU_ME_PLAN_16X16, XVCGPU_ME_PLAN_16X8, 16, 3, false, 0, me_plan_launch<16, 3, false, 16, 16>},
+    {XVCGPU_ME_PLAN_16X8, XVCGPU_ME_PLAN_8X8, 16, 3, false, 0, me_plan_launch<16, 3, false, 16, 8>},
+    {XVCGPU_ME_PLAN_8X8, XVCGPU_ME_PLAN_OTHER16, 16, 3, false, 0, me_plan_launch<16, 3, false, 8, 8>},
+    {XVCGPU_ME_PLAN_OTHER16, XVCGPU_ME_PLAN_C32, 16, 3, false, 0, me_plan_launch<16, 3, false>},
+    {XVCGPU_ME_PLAN_16X16, XVCGPU_ME_PLAN_C32, 16, 1, false, 0, me_plan_launch<16, 1, false>},
+    {XVCGPU_ME_PLAN_16X16, XVCGPU_ME_PLAN_C32, 16, 2, false, 0, me_plan_launch<16, 2, false>},
+    {XVCGPU_ME_PLAN_C32, XVCGPU_ME_PLAN_C64_TEAM, 32, 1, false, 0, me_plan_launch<32, 1, false>},
+    {XVCGPU_ME_PLAN_C32, XVCGPU_ME_PLAN_C64_TEAM, 32, 2, false, 0, me_plan_launch<32, 2, false>},
+    {XVCGPU_ME_PLAN_C64_TEAM, XVCGPU_ME_PLAN_LIC16, 64, 1, false, 0, me_plan_launch<64, 1, false>},
+    {XVCGPU_ME_PLAN_C64_TEAM, XVCGPU_ME_PLAN_LIC16, 64, 2, false, -1, me_plan_launch<64, 2, false>},
+    {XVCGPU_ME_PLAN_C64_WAVE, XVCGPU_ME_PLAN_LIC16, 64, 2, false, 1, me_plan_launch<64, 2, false>},
+    {XVCGPU_ME_PLAN_C64_TEAM, XVCGPU_ME_PLAN_C64_WAVE, 64, 0, false, 1, me_plan_launch_team},
+    {XVCGPU_ME_PLAN_LIC16, XVCGPU_ME_PLAN_LIC32, 16, 1, true, 0, me_plan_launch<16, 1, true>},
+    {XVCGPU_ME_PLAN_LIC16, XVCGPU_ME_PLAN_LIC32, 16, 2, true, 0, me_plan_launch<16, 2, true>},
+    {XVCGPU_ME_PLAN_LIC32, XVCGPU_ME_PLAN_LIC64, 32, 1, true, 0, me_plan_launch<32, 1, true>},
+    {XVCGPU_ME_PLAN_LIC32, XVCGPU_ME_PLAN_LIC64, 32, 2, true, 0, me_plan_launch<32, 2, true>},
+    {XVCGPU_ME_PLAN_LIC64, XVCGPU_ME_PLAN_UNSUPPORTED, 64, 1, true, 0, me_plan_launch<64, 1, true>},
+    {XVCGPU_ME_PLAN_LIC64, XVCGPU_ME_PLAN_UNSUPPORTED, 64, 2, true, 0, me_plan_launch<64, 2, true>},
+};
+
 xvcgpu_status xvcgpu_me_search_planned(xvcgpu_ctx *ctx, const xvcgpu_picture *orig,
                                        const xvcgpu_picture *ref, int flags,
                                        const xvcgpu_me_plan *plan,
@@ -1043,81 +1111,31 @@ xvcgpu_status xvcgpu_me_search_planned(xvcgpu_ctx *ctx, const xvcgpu_picture *or
   if (flags & XVCGPU_ME_FULLPEL) sched = me_sched_next(ctx);
   const int *first = plan->first;
   const int ph = flags & 3;
+  const bool lic_jobs = (flags & XVCGPU_ME_LIC_JOBS) != 0;
+  const MePlanCall call = {ctx->stream, orig->v, ref->v, plan->d_blocks, plan->d_order, d_results,
+                           ctx->d_tz_pattern};
+  // the jobs of every row in this search: 0 where it does not run or its bins are empty
+  constexpr int kRows = sizeof(kMePlanRows) / sizeof(kMePlanRows[0]);
+  int jobs[kRows];
   // The straggler-first record (k_me2.h) counts positions inside one launch's job list: it
-  // is kept by ONE launch, the full-pel launch with the most jobs, from search to search
-  // of the same plan; the other launches run in list order.
+  // is kept by ONE launch, the non-LIC full-pel row with the most jobs, from search to search
+  // of the same plan; the other launches run in list order.  (No such row: nobody rotates
+  // and nobody resets the third record - stale values are clamped by me2_rotated_wg.)
+  int keeper = -1;
+  for (int k = 0; k < kRows; k++) {
+    const MePlanRow &r = kMePlanRows[k];
+    const bool depth_ok = r.depth == 0 || (r.depth > 0) == (orig->bd <= 10);
+    const bool runs = me_class_has(r.ms, r.lic, ph, r.ph) && depth_ok && (!r.lic || lic_jobs);
+    jobs[k] = runs ? first[r.end] - first[r.first] : 0;
+    if (!r.lic && (r.ph & XVCGPU_ME_FULLPEL) && jobs[k] > (keeper < 0 ? 0 : jobs[keeper]))
+      keeper = k;
+  }
   const Me2Sched none = {nullptr, nullptr, nullptr};
-  // (the ranges below are those of the PLAN_LAUNCH calls further down: a new bin goes into
-  // both.  No full-pel job outside the LIC bins: sched_bin stays -1, nobody rotates and
-  // nobody resets the third record - stale values are clamped by me2_rotated_wg.)
-  int sched_bin = -1;
-  if (flags & XVCGPU_ME_FULLPEL) {
-    static const int both[][2] = {{XVCGPU_ME_PLAN_16X16, XVCGPU_ME_PLAN_16X8},
-                                  {XVCGPU_ME_PLAN_16X8, XVCGPU_ME_PLAN_8X8},
-                                  {XVCGPU_ME_PLAN_8X8, XVCGPU_ME_PLAN_OTHER16},
-                                  {XVCGPU_ME_PLAN_OTHER16, XVCGPU_ME_PLAN_C32},
-                                  {XVCGPU_ME_PLAN_C32, XVCGPU_ME_PLAN_C64_TEAM},
-                                  {XVCGPU_ME_PLAN_C64_TEAM, XVCGPU_ME_PLAN_LIC16}};
-    static const int single[][2] = {{XVCGPU_ME_PLAN_16X16, XVCGPU_ME_PLAN_C32},
-                                    {XVCGPU_ME_PLAN_C32, XVCGPU_ME_PLAN_C64_TEAM},
-                                    {XVCGPU_ME_PLAN_C64_TEAM, XVCGPU_ME_PLAN_LIC16}};
-    const int (*r)[2] = ph == 3 ? both : single;
-    int most = 0;
-    for (int k = 0; k < (ph == 3 ? 6 : 3); k++)
-      if (first[r[k][1]] - first[r[k][0]] > most) {
-        most = first[r[k][1]] - first[r[k][0]];
-        sched_bin = r[k][0];
-      }
-  }
-  // slots [first[A], first[B]) by instance <MS, PH, LIC, FW, FH>: nothing where empty
-#define PLAN_LAUNCH(A, B, MS, PH, LIC, FW, FH)                                                  \
-  do {                                                                                          \
-    const int cnt_ = first[B] - first[A];                                                       \
-    if (cnt_ > 0)                                                                               \
-      hipLaunchKernelGGL((me_plan_kernel<MS, PH, LIC, FW, FH>), me2_grid(cnt_, ME2_WAVES(MS)),  \
-                         dim3(64 * ME2_WAVES(MS)), 0, ctx->stream, orig->v, ref->v,             \
-                         plan->d_blocks, plan->d_order + first[A], cnt_, d_results,             \
-                         ctx->d_tz_pattern, (A) == sched_bin ? sched : none);                   \
-  } while (0)
-  // the larger classes and the LIC jobs: the two phases as two launches (xvcgpu_me_search_sized)
-#define PLAN_SPLIT(A, B, MS, LIC)                                           \
-  do {                                                                      \
-    if (flags & XVCGPU_ME_FULLPEL) PLAN_LAUNCH(A, B, MS, 1, LIC, 0, 0);     \
-    if (flags & XVCGPU_ME_SUBPEL) PLAN_LAUNCH(A, B, MS, 2, LIC, 0, 0);      \
-  } while (0)
-  if (ph == 3) {
-    PLAN_LAUNCH(XVCGPU_ME_PLAN_16X16, XVCGPU_ME_PLAN_16X8, 16, 3, false, 16, 16);
-    PLAN_LAUNCH(XVCGPU_ME_PLAN_16X8, XVCGPU_ME_PLAN_8X8, 16, 3, false, 16, 8);
-    PLAN_LAUNCH(XVCGPU_ME_PLAN_8X8, XVCGPU_ME_PLAN_OTHER16, 16, 3, false, 8, 8);
-    PLAN_LAUNCH(XVCGPU_ME_PLAN_OTHER16, XVCGPU_ME_PLAN_C32, 16, 3, false, 0, 0);
-  } else {   // a single phase: the whole 16 class through the any-size instance
-    PLAN_SPLIT(XVCGPU_ME_PLAN_16X16, XVCGPU_ME_PLAN_C32, 16, false);
-  }
-  PLAN_SPLIT(XVCGPU_ME_PLAN_C32, XVCGPU_ME_PLAN_C64_TEAM, 32, false);
-  if (flags & XVCGPU_ME_FULLPEL)
-    PLAN_LAUNCH(XVCGPU_ME_PLAN_C64_TEAM, XVCGPU_ME_PLAN_LIC16, 64, 1, false, 0, 0);
-  if (flags & XVCGPU_ME_SUBPEL) {
-    const int team = first[XVCGPU_ME_PLAN_C64_WAVE] - first[XVCGPU_ME_PLAN_C64_TEAM];
-    if (orig->bd > 10) {   // (me2_subpel_fast: no packed path above 10 bit)
-      PLAN_LAUNCH(XVCGPU_ME_PLAN_C64_TEAM, XVCGPU_ME_PLAN_LIC16, 64, 2, false, 0, 0);
-    } else {
-      PLAN_LAUNCH(XVCGPU_ME_PLAN_C64_WAVE, XVCGPU_ME_PLAN_LIC16, 64, 2, false, 0, 0);
-      if (team > 0)
-        hipLaunchKernelGGL((me_plan_team_kernel<64, 4>), dim3((team + 7) / 8 * 8), dim3(256), 0,
-                           ctx->stream, orig->v, ref->v, plan->d_blocks,
-                           plan->d_order + first[XVCGPU_ME_PLAN_C64_TEAM], team, d_results);
-    }
-  }
-  int bad_from = XVCGPU_ME_PLAN_UNSUPPORTED;
-  if (flags & XVCGPU_ME_LIC_JOBS) {
-    PLAN_SPLIT(XVCGPU_ME_PLAN_LIC16, XVCGPU_ME_PLAN_LIC32, 16, true);
-    PLAN_SPLIT(XVCGPU_ME_PLAN_LIC32, XVCGPU_ME_PLAN_LIC64, 32, true);
-    PLAN_SPLIT(XVCGPU_ME_PLAN_LIC64, XVCGPU_ME_PLAN_UNSUPPORTED, 64, true);
-  } else {
-    bad_from = XVCGPU_ME_PLAN_LIC16;   // not announced: nobody takes them
-  }
-#undef PLAN_SPLIT
-#undef PLAN_LAUNCH
+  for (int k = 0; k < kRows; k++)
+    if (jobs[k] > 0)
+      kMePlanRows[k].launch(call, first[kMePlanRows[k].first], jobs[k], k == keeper ? sched : none);
+  // LIC jobs not announced: nobody takes them
+  const int bad_from = lic_jobs ? XVCGPU_ME_PLAN_UNSUPPORTED : XVCGPU_ME_PLAN_LIC16;
   const int bad = first[XVCGPU_ME_PLAN_BINS] - first[bad_from];
   if (bad > 0)
     hipLaunchKernelGGL(me_plan_unsupported_kernel, dim3((bad + 255) / 256), dim3(256), 0,
@@ -2727,7 +2745,7 @@ xvcgpu_status xvcgpu_frame_pass_multi(xvcgpu_ctx *const *ctxs,
           k.results = a->d_results;
           k.sched = me_sched_next(c);   // the picture's own rotation records
         });
-    hipLaunchKernelGGL(me_search_multi_kernel, dim3(me2_grid(max_cus, ME2_WAVES(16)).x, n),
+    hipLaunchKernelGGL(me_search_multi_kernel, me2_grid(max_cus, ME2_WAVES(16), n),
                        dim3(64 * ME2_WAVES(16)), 0, ctx->stream, m, ctx->d_tz_pattern);
   }
   // 2. prediction + transform (RDOQ: forward half only, the quantiser follows)
@@ -2915,28 +2933,17 @@ xvcgpu_status xvcgpu_me_search_refs(xvcgpu_ctx *ctx, const xvcgpu_picture *orig,
   if (n == 0) return XVCGPU_OK;
   Me2Sched sched = {nullptr, nullptr, nullptr};
   if (flags & XVCGPU_ME_FULLPEL) sched = me_sched_next(ctx);
-#define ME_REFS(MS, PH)                                                                      \
-  hipLaunchKernelGGL((me_search_refs_kernel<MS, PH>), me2_grid(n, ME2_WAVES(MS)),            \
-                     dim3(64 * ME2_WAVES(MS)), 0, ctx->stream, orig->v, t, d_slots, d_blocks, \
-                     n, d_results, ctx->d_tz_pattern, sched, block_class)
-#define ME_REFS_SPLIT(MS)                            \
-  do {                                               \
-    if (flags & XVCGPU_ME_FULLPEL) ME_REFS(MS, 1);   \
-    if (flags & XVCGPU_ME_SUBPEL) ME_REFS(MS, 2);    \
-  } while (0)
-  if (block_class == 16) {
-    if ((flags & 3) == 3) ME_REFS(16, 3);
-    else ME_REFS_SPLIT(16);
-  } else if (block_class == 32) {
-    ME_REFS_SPLIT(32);
-  } else {
-    ME_REFS_SPLIT(64);
-    if (flags & XVCGPU_ME_SUBPEL)
-      hipLaunchKernelGGL((me_subpel_team_refs_kernel<64, 4>), dim3((n + 7) / 8 * 8), dim3(256), 0,
-                         ctx->stream, orig->v, t, d_slots, d_blocks, n, d_results);
-  }
-#undef ME_REFS_SPLIT
-#undef ME_REFS
+  auto wave = [&](auto inst) {
+    typedef decltype(inst) I;
+    hipLaunchKernelGGL((me_search_refs_kernel<I::MS, I::PH>), me2_grid(n, ME2_WAVES(I::MS)),
+                       dim3(64 * ME2_WAVES(I::MS)), 0, ctx->stream, orig->v, t, d_slots,
+                       d_blocks, n, d_results, ctx->d_tz_pattern, sched, block_class);
+  };
+  auto team = [&] {
+    hipLaunchKernelGGL((me_subpel_team_refs_kernel<64, 4>), me_team_grid(n), dim3(256), 0,
+                       ctx->stream, orig->v, t, d_slots, d_blocks, n, d_results);
+  };
+  me_launches<false>(block_class, flags & 3, wave, team);
   CHECK_LAUNCH(ctx, "me_search_refs");
   return XVCGPU_OK;
 }
@@ -3148,22 +3155,16 @@ xvcgpu_status xvcgpu_cs_segs_launch(xvcgpu_ctx *ctx, int kind, const xvcgpu_cs_s
         break;
       case XVC_CS_SEG_ME_REFS: {
         const Me2Sched sched = me_sched_next(ctx);
-#define SEG_ME(MS, PH)                                                                      \
-  hipLaunchKernelGGL((cs_seg_me_kernel<MS, PH>), dim3(me2_grid(max_n, ME2_WAVES(MS)).x, gy), \
-                     dim3(64 * ME2_WAVES(MS)), 0, st, a, ctx->d_tz_pattern, sched)
-        if (key == 16) {
-          SEG_ME(16, 3);
-        } else if (key == 32) {
-          SEG_ME(32, 1);
-          SEG_ME(32, 2);
-        } else if (key == 64) {
-          SEG_ME(64, 1);
-          SEG_ME(64, 2);
-          hipLaunchKernelGGL(cs_seg_me_team_kernel, dim3((max_n + 7) / 8 * 8, gy), dim3(256), 0, st, a);
-        } else {
-          return XVCGPU_INVALID_ARGUMENT;
-        }
-#undef SEG_ME
+        if (key != 16 && key != 32 && key != 64) return XVCGPU_INVALID_ARGUMENT;
+        auto wave = [&](auto inst) {
+          typedef decltype(inst) I;
+          hipLaunchKernelGGL((cs_seg_me_kernel<I::MS, I::PH>), me2_grid(max_n, ME2_WAVES(I::MS), gy),
+                             dim3(64 * ME2_WAVES(I::MS)), 0, st, a, ctx->d_tz_pattern, sched);
+        };
+        auto team = [&] {
+          hipLaunchKernelGGL(cs_seg_me_team_kernel, me_team_grid(max_n, gy), dim3(256), 0, st, a);
+        };
+        me_launches_of<3, false>(key, wave, team);   // both phases, always
         break;
       }
       case XVC_CS_SEG_BI_REFS: {
