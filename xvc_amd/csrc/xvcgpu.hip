@@ -31,6 +31,7 @@
 #include "k_intra_waves.h"
 #include "k_cu_state.h"
 #include "k_cs_engine.h"
+#include "k_fp_bi.h"
 #include "xvcgpu_internal.h"
 
 namespace {
@@ -1346,6 +1347,61 @@ xvcgpu_status xvcgpu_cu_info_from_me(xvcgpu_ctx *ctx,
   return XVCGPU_OK;
 }
 
+/* ---- SearchMotion's decisions for a B picture (k_fp_bi.h) ---- */
+xvcgpu_status xvcgpu_fp_bi_uni_fold(xvcgpu_ctx *ctx, const xvcgpu_me_block *d_me_l0,
+                                    const xvcgpu_me_block *d_me_l1,
+                                    const xvcgpu_me_result *d_results_l0,
+                                    const xvcgpu_me_result *d_results_l1, int n,
+                                    uint32_t side_bits_l0, uint32_t side_bits_l1,
+                                    xvcgpu_bi_block *d_bi_jobs_l0, xvcgpu_bi_block *d_bi_jobs_l1,
+                                    xvcgpu_fp_bi_result *d_choice) {
+  if (!ctx || n < 0 ||
+      (n && (!d_me_l0 || !d_me_l1 || !d_results_l0 || !d_results_l1 || !d_bi_jobs_l0 ||
+             !d_bi_jobs_l1 || !d_choice)))
+    return XVCGPU_INVALID_ARGUMENT;
+  if (n == 0) return XVCGPU_OK;
+  hipLaunchKernelGGL(fp_bi_uni_fold_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream,
+                     d_me_l0, d_me_l1, d_results_l0, d_results_l1, n, side_bits_l0, side_bits_l1,
+                     d_bi_jobs_l0, d_bi_jobs_l1, d_choice);
+  CHECK_LAUNCH(ctx, "fp_bi_uni_fold");
+  return XVCGPU_OK;
+}
+
+xvcgpu_status xvcgpu_fp_bi_choice(xvcgpu_ctx *ctx, const xvcgpu_me_block *d_me_l0,
+                                  const xvcgpu_me_block *d_me_l1,
+                                  const xvcgpu_me_result *d_results_l0,
+                                  const xvcgpu_me_result *d_results_l1,
+                                  const xvcgpu_me_result *d_bi_results_l0,
+                                  const xvcgpu_me_result *d_bi_results_l1, int n,
+                                  uint32_t side_bits_bi, xvcgpu_fp_bi_result *d_choice,
+                                  xvcgpu_inter_block *d_inter) {
+  if (!ctx || n < 0 ||
+      (n && (!d_me_l0 || !d_me_l1 || !d_results_l0 || !d_results_l1 || !d_bi_results_l0 ||
+             !d_bi_results_l1 || !d_choice || !d_inter)))
+    return XVCGPU_INVALID_ARGUMENT;
+  if (n == 0) return XVCGPU_OK;
+  hipLaunchKernelGGL(fp_bi_choice_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream,
+                     d_me_l0, d_me_l1, d_results_l0, d_results_l1, d_bi_results_l0,
+                     d_bi_results_l1, n, side_bits_bi, d_choice, d_inter);
+  CHECK_LAUNCH(ctx, "fp_bi_choice");
+  return XVCGPU_OK;
+}
+
+xvcgpu_status xvcgpu_cu_info_from_choice(xvcgpu_ctx *ctx, const xvcgpu_me_block *d_blocks,
+                                         const xvcgpu_fp_bi_result *d_choice,
+                                         const int32_t *d_nnz, const int32_t *d_luma_tx_index,
+                                         int n, int qp_y, int qp_c, int ref_poc_l0,
+                                         int ref_poc_l1, xvcgpu_cu_info *d_cus) {
+  if (!ctx || n < 0 || (n && (!d_blocks || !d_choice || !d_nnz || !d_cus)))
+    return XVCGPU_INVALID_ARGUMENT;
+  if (n == 0) return XVCGPU_OK;
+  hipLaunchKernelGGL(cu_info_from_choice_kernel, dim3((n + 255) / 256), dim3(256), 0,
+                     ctx->stream, d_blocks, d_choice, d_nnz, d_luma_tx_index, n, qp_y, qp_c,
+                     ref_poc_l0, ref_poc_l1, d_cus);
+  CHECK_LAUNCH(ctx, "cu_info_from_choice");
+  return XVCGPU_OK;
+}
+
 xvcgpu_status xvcgpu_recon_from_me(xvcgpu_ctx *ctx, const xvcgpu_picture *orig,
                                    const xvcgpu_picture *ref, xvcgpu_picture *rec,
                                    const xvcgpu_me_block *d_blocks,
@@ -2560,30 +2616,70 @@ static xvcgpu_status fp_fwd_from_me(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_arg
                                        a->d_level_off, a->d_nnz);
 }
 
-// CUs of any size: the prediction picture, the form's residual pipeline over the transform
-// blocks (whole with QuantFast or RDOQ, or split around the packed quantiser), the CU records
+// The form's residual pipeline behind a prediction picture, over the transform blocks: whole
+// with QuantFast or RDOQ, or split around the packed quantiser
+static xvcgpu_status fp_residual(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_args *a,
+                                 xvcgpu_picture *rec, int form) {
+  if (form == XVC_FP_FORM_RESIDUAL)
+    return xvcgpu_residual_batch(ctx, a->orig, a->pred, rec, a->d_tx, a->n_tx, a->d_levels,
+                                 a->d_level_off, a->d_nnz);
+  if (form == XVC_FP_FORM_RESIDUAL_RDOQ)
+    return xvcgpu_residual_rdoq_batch(ctx, a->orig, a->pred, rec, a->d_tx, a->n_tx, a->d_levels,
+                                      a->d_level_off, a->d_nnz, a->d_rdoq_contexts,
+                                      a->d_rdoq_params);
+  xvcgpu_status st = xvcgpu_fwd_transform_batch(ctx, a->orig, a->pred, a->d_tx, a->n_tx,
+                                                a->d_coeffs, a->d_level_off);
+  if (st == XVCGPU_OK) st = fp_quant_rdo(ctx, a, false);
+  if (st == XVCGPU_OK)
+    st = xvcgpu_inv_transform_batch(ctx, a->pred, rec, a->d_tx, a->n_tx, a->d_levels,
+                                    a->d_level_off, a->d_nnz);
+  return st;
+}
+
+// CUs of any size: the prediction picture, the form's residual pipeline, the CU records
 static xvcgpu_status fp_from_pred(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_args *a,
                                   xvcgpu_picture *rec, int form) {
   xvcgpu_status st = xvcgpu_mc_from_me(ctx, a->ref, a->pred, a->d_me, a->d_results, a->n_cus);
-  if (st != XVCGPU_OK) return st;
-  if (form == XVC_FP_FORM_RESIDUAL)
-    st = xvcgpu_residual_batch(ctx, a->orig, a->pred, rec, a->d_tx, a->n_tx, a->d_levels,
-                               a->d_level_off, a->d_nnz);
-  else if (form == XVC_FP_FORM_RESIDUAL_RDOQ)
-    st = xvcgpu_residual_rdoq_batch(ctx, a->orig, a->pred, rec, a->d_tx, a->n_tx, a->d_levels,
-                                    a->d_level_off, a->d_nnz, a->d_rdoq_contexts,
-                                    a->d_rdoq_params);
-  else {
-    st = xvcgpu_fwd_transform_batch(ctx, a->orig, a->pred, a->d_tx, a->n_tx, a->d_coeffs,
-                                    a->d_level_off);
-    if (st == XVCGPU_OK) st = fp_quant_rdo(ctx, a, false);
-    if (st == XVCGPU_OK)
-      st = xvcgpu_inv_transform_batch(ctx, a->pred, rec, a->d_tx, a->n_tx, a->d_levels,
-                                      a->d_level_off, a->d_nnz);
-  }
+  if (st == XVCGPU_OK) st = fp_residual(ctx, a, rec, form);
   if (st != XVCGPU_OK) return st;
   return xvcgpu_cu_info_from_me(ctx, a->d_me, a->d_results, a->d_nnz, a->d_luma_tx_index,
                                 a->n_cus, a->qp_y, a->qp_c, a->ref_poc, a->d_cus_own);
+}
+
+// How a pass ends: the fused tail's one launch from scratch_rec, or the phases' separate
+// launches.  pic_is_bipred: the deblocking filter's word for a B picture
+static xvcgpu_status fp_tail(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_args *a, int phases,
+                             bool fused_tail, int pic_is_bipred) {
+  if (fused_tail)
+    return xvcgpu_deblock_pad_ssd(ctx, a->scratch_rec, a->rec, a->orig, a->d_cus, a->n_cus_total,
+                                  a->d_cu_map, a->map_stride, pic_is_bipred, 0, 0,
+                                  a->shift_bitdepth, a->d_ssd);
+  xvcgpu_status st = XVCGPU_OK;
+  if (phases & XVC_FP_DEBLOCK_V)
+    st = xvcgpu_deblock_rows(ctx, a->rec, a->d_cus, a->n_cus_total, a->d_cu_map, a->map_stride,
+                             pic_is_bipred, 0, 0, 4, 0, a->db_y_begin, a->db_y_end);
+  if (st == XVCGPU_OK && (phases & XVC_FP_DEBLOCK_H))
+    st = xvcgpu_deblock_rows(ctx, a->rec, a->d_cus, a->n_cus_total, a->d_cu_map, a->map_stride,
+                             pic_is_bipred, 0, 0, 4, 1, a->db_y_begin, a->dbh_y_end);
+  if (st == XVCGPU_OK && (phases & XVC_FP_PAD)) st = xvcgpu_pad_border(ctx, a->rec);
+  if (st == XVCGPU_OK && (phases & XVC_FP_SSD))
+    st = xvcgpu_picture_ssd_rows(ctx, a->orig, a->rec, 0, a->shift_bitdepth, a->ssd_y_begin,
+                                 a->ssd_y_end, a->d_ssd);
+  return st;
+}
+
+// One list's search of the pass, through its plan or sized.  The pass's jobs are the CUs of
+// its grid: where the caller's shape word says that they are (almost) all 16x16 (16x8 in the
+// bottom row of a 1080-line picture) the search's exact-shape kernel (a pass of smaller CUs
+// must not take it: its jobs would all be left to the few waves of the leftover kernel)
+static xvcgpu_status fp_search(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_args *a,
+                               const xvcgpu_picture *ref, const xvcgpu_me_block *d_me,
+                               xvcgpu_me_result *d_results, const xvcgpu_me_plan *plan) {
+  const int flags = XVCGPU_ME_FULLPEL | XVCGPU_ME_SUBPEL;
+  if (plan) return xvcgpu_me_search_planned(ctx, a->orig, ref, flags, plan, d_results);
+  return xvcgpu_me_search_sized(
+      ctx, a->orig, ref, flags | (a->me_shape & (XVCGPU_ME_HINT_SQ16 | XVCGPU_ME_ONLY_SQ16)),
+      d_me, a->n_cus, d_results, a->max_block_size);
 }
 
 // resolve, search, the form's launches, tail.  plan: null = xvcgpu_frame_pass
@@ -2595,17 +2691,7 @@ static xvcgpu_status frame_pass_impl(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_ar
   xvcgpu_picture *const rec = r.fused_tail ? a->scratch_rec : a->rec;
   hipStream_t main_stream = nullptr;   // set while the pass runs on ctx->hi_stream
   if (r.form) {
-    // the pass's jobs are the CUs of its grid: where the caller's shape word says that they
-    // are (almost) all 16x16 (16x8 in the bottom row of a 1080-line picture) the search's
-    // exact-shape kernel (a pass of smaller CUs must not take it: its jobs would all be left
-    // to the few waves of the leftover kernel)
-    st = plan ? xvcgpu_me_search_planned(ctx, a->orig, a->ref,
-                                         XVCGPU_ME_FULLPEL | XVCGPU_ME_SUBPEL, plan, a->d_results)
-              : xvcgpu_me_search_sized(
-                    ctx, a->orig, a->ref,
-                    XVCGPU_ME_FULLPEL | XVCGPU_ME_SUBPEL |
-                        (a->me_shape & (XVCGPU_ME_HINT_SQ16 | XVCGPU_ME_ONLY_SQ16)),
-                    a->d_me, a->n_cus, a->d_results, a->max_block_size);
+    st = fp_search(ctx, a, a->ref, a->d_me, a->d_results, plan);
     if (st != XVCGPU_OK) return st;   // (nothing behind a search that was refused)
     switch (r.form) {
       case XVC_FP_FORM_RECON_FROM_ME: st = fp_recon_from_me(ctx, a, rec); break;
@@ -2615,20 +2701,7 @@ static xvcgpu_status frame_pass_impl(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_ar
       default: st = fp_from_pred(ctx, a, rec, r.form); break;
     }
   }
-  if (st == XVCGPU_OK && r.fused_tail)
-    st = xvcgpu_deblock_pad_ssd(ctx, a->scratch_rec, a->rec, a->orig, a->d_cus, a->n_cus_total,
-                                a->d_cu_map, a->map_stride, 0, 0, 0, a->shift_bitdepth, a->d_ssd);
-  if (r.fused_tail) phases = 0;
-  if (st == XVCGPU_OK && (phases & XVC_FP_DEBLOCK_V))
-    st = xvcgpu_deblock_rows(ctx, a->rec, a->d_cus, a->n_cus_total, a->d_cu_map, a->map_stride,
-                             0, 0, 0, 4, 0, a->db_y_begin, a->db_y_end);
-  if (st == XVCGPU_OK && (phases & XVC_FP_DEBLOCK_H))
-    st = xvcgpu_deblock_rows(ctx, a->rec, a->d_cus, a->n_cus_total, a->d_cu_map, a->map_stride,
-                             0, 0, 0, 4, 1, a->db_y_begin, a->dbh_y_end);
-  if (st == XVCGPU_OK && (phases & XVC_FP_PAD)) st = xvcgpu_pad_border(ctx, a->rec);
-  if (st == XVCGPU_OK && (phases & XVC_FP_SSD))
-    st = xvcgpu_picture_ssd_rows(ctx, a->orig, a->rec, 0, a->shift_bitdepth, a->ssd_y_begin,
-                                 a->ssd_y_end, a->d_ssd);
+  if (st == XVCGPU_OK) st = fp_tail(ctx, a, phases, r.fused_tail, 0);
   if (main_stream) {   // every way out: the chain continues on its own stream, after the tail
     hipEventRecord(ctx->ev_hi_out, ctx->hi_stream);
     ctx->stream = main_stream;
@@ -2651,6 +2724,78 @@ xvcgpu_status xvcgpu_frame_pass_planned(xvcgpu_ctx *ctx, const xvcgpu_frame_pass
     return fail(ctx, XVCGPU_INVALID_ARGUMENT,
                 "frame_pass_planned: the plan was made for another max_block_size class");
   return frame_pass_impl(ctx, a, phases, plan);
+}
+
+xvcgpu_status xvcgpu_frame_pass_bi(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_bi_args *b,
+                                   const xvcgpu_me_plan *plan_l0, const xvcgpu_me_plan *plan_l1,
+                                   int phases) {
+  if (!ctx || !b || !b->p.rec) return XVCGPU_INVALID_ARGUMENT;
+  const xvcgpu_frame_pass_args *a = &b->p;
+  const int n = a->n_cus;
+#define FPB_NEED(cond, what) \
+  if (!(cond)) return fail(ctx, XVCGPU_INVALID_ARGUMENT, "frame_pass_bi: " what)
+  FPB_NEED(n == a->n_cus_total && a->db_y_begin == 0 && a->db_y_end >= a->rec->h &&
+               a->dbh_y_end >= a->rec->h && a->ssd_y_begin == 0 && a->ssd_y_end >= a->rec->h,
+           "whole pictures only (no row shard)");
+  if ((phases & XVC_FP_ENCODE) && n > 0) {
+    FPB_NEED(a->form == XVC_FP_FORM_FWD_TRANSFORM || a->form == XVC_FP_FORM_RESIDUAL ||
+                 a->form == XVC_FP_FORM_RESIDUAL_RDOQ,
+             "the form must be one with a prediction picture: FWD_TRANSFORM, RESIDUAL or "
+             "RESIDUAL_RDOQ");
+    FPB_NEED(a->orig && b->ref1 && b->d_me_l1 && b->d_results_l1,
+             "orig, ref1, d_me_l1 and d_results_l1");
+    FPB_NEED(b->ref1->w == a->orig->w && b->ref1->h == a->orig->h && b->ref1->bd == a->orig->bd,
+             "ref1 is not a picture of orig's size");
+    FPB_NEED(b->d_bi_jobs[0] && b->d_bi_jobs[1] && b->d_bi_results[0] && b->d_bi_results[1] &&
+                 b->d_choice && b->d_inter,
+             "d_bi_jobs, d_bi_results, d_choice and d_inter");
+    FPB_NEED(!plan_l0 == !plan_l1, "both plans or neither");
+    if (plan_l0) {
+      FPB_NEED(plan_l0->n == n && plan_l0->d_blocks == a->d_me,
+               "plan_l0 was not made from p.d_me");
+      FPB_NEED(plan_l1->n == n && plan_l1->d_blocks == b->d_me_l1,
+               "plan_l1 was not made from d_me_l1");
+      FPB_NEED(plan_l0->max_launched == me_class_of(a->max_block_size) &&
+                   plan_l1->max_launched == plan_l0->max_launched,
+               "a plan was made for another max_block_size class");
+    }
+  }
+#undef FPB_NEED
+  FramePassForm r;
+  xvcgpu_status st = frame_pass_resolve(ctx, a, phases, plan_l0, &r);
+  if (st != XVCGPU_OK) return st;
+  if (plan_l1 && plan_l1->n_small() > 0) r.fused_tail = false;
+  xvcgpu_picture *const rec = r.fused_tail ? a->scratch_rec : a->rec;
+  if (r.form) {
+    st = fp_search(ctx, a, a->ref, a->d_me, a->d_results, plan_l0);
+    if (st == XVCGPU_OK) st = fp_search(ctx, a, b->ref1, b->d_me_l1, b->d_results_l1, plan_l1);
+    if (st == XVCGPU_OK)
+      st = xvcgpu_fp_bi_uni_fold(ctx, a->d_me, b->d_me_l1, a->d_results, b->d_results_l1, n,
+                                 b->side_bits_uni[0], b->side_bits_uni[1], b->d_bi_jobs[0],
+                                 b->d_bi_jobs[1], b->d_choice);
+    // SearchBiIterative's one step, the CUs that refine list 0, then those that refine list 1
+    if (st == XVCGPU_OK)
+      st = xvcgpu_bipred_search(ctx, a->orig, b->ref1, a->ref, b->d_bi_jobs[0], n,
+                                b->d_bi_results[0], a->max_block_size);
+    if (st == XVCGPU_OK)
+      st = xvcgpu_bipred_search(ctx, a->orig, a->ref, b->ref1, b->d_bi_jobs[1], n,
+                                b->d_bi_results[1], a->max_block_size);
+    if (st == XVCGPU_OK)
+      st = xvcgpu_fp_bi_choice(ctx, a->d_me, b->d_me_l1, a->d_results, b->d_results_l1,
+                               b->d_bi_results[0], b->d_bi_results[1], n, b->side_bits_bi,
+                               b->d_choice, b->d_inter);
+    if (st == XVCGPU_OK) {
+      // (the prediction reads its `rec` for LIC jobs only: there are none)
+      const xvcgpu_picture *refs[2] = {a->ref, b->ref1};
+      st = xvcgpu_inter_pred_batch(ctx, refs, 2, a->rec, a->pred, b->d_inter, 3 * n);
+    }
+    if (st == XVCGPU_OK) st = fp_residual(ctx, a, rec, r.form);
+    if (st == XVCGPU_OK)
+      st = xvcgpu_cu_info_from_choice(ctx, a->d_me, b->d_choice, a->d_nnz, a->d_luma_tx_index, n,
+                                      a->qp_y, a->qp_c, a->ref_poc, b->ref_poc_l1, a->d_cus_own);
+  }
+  if (st == XVCGPU_OK) st = fp_tail(ctx, a, phases, r.fused_tail, 1);
+  return st;
 }
 
 /* ---- several pictures per call: every kernel launched once for all of them ---- */
