@@ -1295,6 +1295,83 @@ xvcgpu_status xvcgpu_frame_pass_bi(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_bi_a
                                    const xvcgpu_me_plan *plan_l0, const xvcgpu_me_plan *plan_l1,
                                    int phases);
 
+/* ---- the frame pass of a B picture, several reference pictures per list ---- *
+ * xvcgpu_frame_pass_bi with num_ref[l] = 1 .. XVC_CS_MAX_REFS pictures per list as the
+ * reference encoder codes a B picture: inside a sub-GOP the lists name the same pictures in
+ * opposite order, SearchRefIdx then re-uses list 0's result for list 1
+ * (same_poc_in_l0[r] >= 0, inter_search.cc:536-542) and the final choice is made against
+ * the best of the pictures only list 1 names (cost_l1_unique, :247-257).  ENCODE runs, on
+ * the context's stream, without synchronising or allocating:
+ *
+ *   1  one search per (l, r) that is not re-used (d_me[l][r] on refs[slot[l][r]] ->
+ *      d_results[l][r]), sized or through plans[l][r]
+ *   2  xvcgpu_fp_bi_refs_uni_fold
+ *   3  the refinement by block class: without plans xvcgpu_bipred_search_refs once per class
+ *      16, 32, 64 up to p.max_block_size over the whole job list (the 16 launch answers
+ *      jobs of the other classes with the unsupported record, the later launches overwrite
+ *      it); with plans xvcgpu_bipred_search_refs_planned
+ *   4  xvcgpu_fp_bi_refs_choice
+ *   5  xvcgpu_inter_pred_batch(refs, n_refs -> p.pred, d_inter)
+ *   6  the residual pipeline of p.form
+ *   7  xvcgpu_cu_info_from_choice_refs
+ *
+ * and the phases behind it are xvcgpu_frame_pass's with pic_is_bipred = 1.  Scope: one
+ * refinement iteration, translational motion (no LIC, no affine), a job's mvp standing for
+ * both AMVP entries of its (list, picture), the caller's closed-form side bits (3 / 3 / 5)
+ * to which the device adds RefIdxBits(num_ref, r) = num_ref <= 1 ? 0 : r + 1 - (r == num_ref
+ * - 1), whole pictures, p.form FWD_TRANSFORM, RESIDUAL or RESIDUAL_RDOQ.  Not: pictures
+ * with only back references (force_l1_mvd_zero, refused), more iterations, real AMVP
+ * derivation, CABAC-priced bits, a multi-picture form, row shards.
+ * plans[l][r]: one plan for every searched (l, r), made from d_me[l][r] / n_cus /
+ * max_block_size, or all NULL (entries of re-used pictures are ignored).  Refused with
+ * XVCGPU_INVALID_ARGUMENT and a message naming the field, before the first launch: num_ref
+ * out of range, same_poc_in_l0[r] >= num_ref[0], a re-used entry whose slot or POC differs
+ * from its twin's, a slot >= n_refs, force_l1_mvd_zero, a missing array, plans for some
+ * searched entries only or not made from their jobs, the forms RECON_FROM_ME and
+ * FWD_FROM_ME, part of a picture, a picture of another size or depth.
+ *
+ * The three decision kernels read the tables of the args block (num_ref, same_poc_in_l0,
+ * slot, ref_poc, d_me, d_results, side bits, the work arrays; p.n_cus CUs; the cu_info form
+ * also p.d_nnz, p.d_luma_tx_index, p.qp_y, p.qp_c, p.d_cus_own) and nothing else of it.
+ * xvcgpu_fp_bi_refs_uni_fold: per (l, r) in index order dist and vector are the search's,
+ * or list 0's of same_poc_in_l0[r] for a re-used picture; cost = dist + (((side_bits_uni[l]
+ * + RefIdxBits + 1 + GetMvdBits against d_me[l][r]'s mvp) * lambda16) >> 16), a 64-bit
+ * product; best per list on strict <; cost_l1_unique over the unique pictures only;
+ * search_list = cost_0 <= cost_1 ? 1 : 0 =: s.  Job [i * Rmax + k], k < num_ref[s]: blk =
+ * d_me[s][k][i], boot_mv = the uni-directional vector of (s, k), other_mv = the winner of
+ * list 1 - s; slot bytes {slot[s][k], slot[1-s][best_ref[1-s]]}; k >= num_ref[s]: slot bytes
+ * XVC_FP_BI_NO_JOB, the job untouched.  A CU with an XVCGPU_ME_UNSUPPORTED search result:
+ * the record all ones, no job in any slot.
+ * xvcgpu_fp_bi_refs_choice: walks k in picture order from UINT32_MAX on strict <; bits =
+ * side_bits_bi + for both lists RefIdxBits + 1 + mvd bits of that list's (picture, vector)
+ * against that (l, r) job's mvp; ChooseUniOrBi(cost_l0, cost_l1_unique, cost_bi): bi on <=
+ * both, else list 0 on cost_l0 <= cost_l1_unique, else the best unique list-1 state; writes
+ * the record and the CU's prediction jobs d_inter[3 i + comp] with ref[l] = the table slot of
+ * the chosen picture, or -1.
+ * xvcgpu_cu_info_from_choice_refs: xvcgpu_cu_info_from_choice with ref_idx0 = the chosen
+ * list-0 index or -1 and ref_poc[l] = the chosen picture's POC or -1. */
+xvcgpu_status xvcgpu_fp_bi_refs_uni_fold(xvcgpu_ctx *ctx,
+                                         const xvcgpu_frame_pass_bi_refs_args *a);
+xvcgpu_status xvcgpu_fp_bi_refs_choice(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_bi_refs_args *a);
+xvcgpu_status xvcgpu_cu_info_from_choice_refs(xvcgpu_ctx *ctx,
+                                              const xvcgpu_frame_pass_bi_refs_args *a);
+/* The refinement jobs of a CU list laid out by CU (job [cu * jobs_per_cu + k], slot bytes as
+ * xvcgpu_bipred_search_refs) through the CU list's search plan: one launch per non-empty
+ * class of the plan (16: the exact-shape bins and other16; 32: c32; 64: both c64 bins) over
+ * that class's CUs only, workgroup g taking job order[g / jobs_per_cu] * jobs_per_cu + g %
+ * jobs_per_cu.  Results equal the per-class xvcgpu_bipred_search_refs launches record for
+ * record (the CUs of the plan's unsupported bin get the unsupported record where their slots
+ * name a job).  A plan with LIC jobs is refused.  jobs_per_cu: 1 .. XVC_CS_MAX_REFS. */
+xvcgpu_status xvcgpu_bipred_search_refs_planned(xvcgpu_ctx *ctx, const xvcgpu_picture *orig,
+                                                const xvcgpu_picture *const *refs, int n_refs,
+                                                const xvcgpu_me_plan *plan, int jobs_per_cu,
+                                                const xvcgpu_bi_block *d_jobs,
+                                                const uint8_t *d_slots,
+                                                xvcgpu_me_result *d_results);
+xvcgpu_status xvcgpu_frame_pass_bi_refs(
+    xvcgpu_ctx *ctx, const xvcgpu_frame_pass_bi_refs_args *a,
+    const xvcgpu_me_plan *const plans[2][XVC_CS_MAX_REFS], int phases);
+
 /* ---- tables (host side, no GPU needed) ---------------------------------- *
  * The 8-bit-fraction transform matrices the kernels use (transform_data.cc:
  * 109-796), for table-equality tests. out: size*size int16 row-major. */

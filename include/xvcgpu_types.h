@@ -640,6 +640,63 @@ typedef struct xvcgpu_frame_pass_bi_args {
   xvcgpu_inter_block *d_inter;      /* 3 * n_cus: the CUs' prediction jobs Y, U, V  */
 } xvcgpu_frame_pass_bi_args;
 
+/* What InterSearch::SearchMotion ends with for one CU of a B picture with several reference
+ * pictures per list (xvcgpu_frame_pass_bi_refs), and what shows why.  Unused entries
+ * (r >= num_ref[l], k >= num_ref[search_list], no unique list-1 picture) hold UINT32_MAX as
+ * a cost, -1 as an index and 0 as a vector.  A CU whose search has no kernel instance
+ * (XVCGPU_ME_UNSUPPORTED): every byte 0xff. */
+typedef struct xvcgpu_fp_bi_refs_result {
+  int32_t inter_dir;          /* 0 L0, 1 L1, 2 bi                                        */
+  int32_t search_list;        /* the refined list                                        */
+  int32_t ref_idx[2];         /* the chosen state's picture per list; -1: list unused    */
+  int32_t mv[2][2];           /* [list][x, y], 1/16 pel; the unused list is zero         */
+  uint32_t cost_list[2];      /* SearchRefIdx's cost per list (best picture)             */
+  uint32_t cost_l1_unique;    /* ... over the pictures only list 1 names; UINT32_MAX: none */
+  uint32_t cost_bi;           /* SearchBiIterative's cost after the one iteration        */
+  uint32_t cost;              /* the chosen state's                                      */
+  int32_t best_ref[2];        /* the picture behind cost_list[l]                         */
+  int32_t best_ref_l1_unique; /* the picture behind cost_l1_unique; -1: none             */
+  uint32_t cost_uni[2][XVC_CS_MAX_REFS]; /* per (list, picture)                          */
+  uint32_t bi_cost[XVC_CS_MAX_REFS];     /* per picture k of search_list                 */
+  int32_t bi_mv[XVC_CS_MAX_REFS][2];     /* the refined vector into picture k            */
+} xvcgpu_fp_bi_refs_result;
+
+/* xvcgpu_frame_pass_bi_refs: the frame pass of a B picture whose lists name up to
+ * XVC_CS_MAX_REFS pictures each.  p is the P pass's block; p.ref, p.d_me, p.d_results and
+ * p.ref_poc are ignored (the tables below say them per list and picture).  All arrays are
+ * allocated by the caller. */
+#define XVC_FP_BI_MAX_REF_PICS 6   /* distinct reference pictures of a call */
+#define XVC_FP_BI_NO_JOB 255       /* first slot byte of a refinement job nobody runs */
+typedef struct xvcgpu_frame_pass_bi_refs_args {
+  xvcgpu_frame_pass_args p;
+  int32_t num_ref[2];                       /* 1 .. XVC_CS_MAX_REFS per list             */
+  int8_t same_poc_in_l0[XVC_CS_MAX_REFS];   /* list-1 picture r: the list-0 index of the
+                                             * same picture (re-used: not searched), or -1 */
+  uint8_t force_l1_mvd_zero;                /* PictureData::DetermineForceBipredL1MvdZero;
+                                             * set: refused (out of scope)               */
+  int32_t n_refs;                           /* 1 .. XVC_FP_BI_MAX_REF_PICS               */
+  const struct xvcgpu_picture *refs[XVC_FP_BI_MAX_REF_PICS]; /* the distinct pictures    */
+  uint8_t slot[2][XVC_CS_MAX_REFS];         /* (list, picture) -> index into refs; a
+                                             * re-used entry has its twin's              */
+  int32_t ref_poc[2][XVC_CS_MAX_REFS];
+  const xvcgpu_me_block *d_me[2][XVC_CS_MAX_REFS]; /* n_cus each, the same CUs in the same
+                                             * order: per-picture range, previous vector,
+                                             * predictor (re-used entries too: their
+                                             * predictor prices list 1's side)           */
+  xvcgpu_me_result *d_results[2][XVC_CS_MAX_REFS]; /* n_cus each; ignored for a re-used
+                                             * entry (may be NULL)                       */
+  uint32_t side_bits_uni[2];
+  uint32_t side_bits_bi;
+  xvcgpu_bi_block *d_bi_jobs;               /* n_cus * Rmax, Rmax = max(num_ref): job
+                                             * [i * Rmax + k] = CU i into picture k of its
+                                             * searched list                             */
+  xvcgpu_me_result *d_bi_results;           /* n_cus * Rmax                              */
+  uint8_t *d_bi_slots;                      /* 2 bytes per job: {searched, other} slot;
+                                             * XVC_FP_BI_NO_JOB first: no job            */
+  xvcgpu_fp_bi_refs_result *d_choice;       /* n_cus                                     */
+  xvcgpu_inter_block *d_inter;              /* 3 * n_cus: the CUs' prediction jobs Y, U, V */
+} xvcgpu_frame_pass_bi_refs_args;
+
 /* One job of xvcgpu_affine_me_batch: InterSearch::MotionEstAffine for one
  * (list, ref_idx) of a CU (inter_search.cc:664-749).  Vectors are {x, y} in
  * 1/16 pel; mvp / bootstrap / other_mv are MotionVector3 (top-left, top-right,

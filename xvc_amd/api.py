@@ -166,6 +166,34 @@ FP_BI_RESULT_DTYPE = np.dtype([("inter_dir", "<i4"), ("search_list", "<i4"),
                                ("mv", "<i4", (2, 2)), ("bi_mv", "<i4", (2,))])
 assert FP_BI_RESULT_DTYPE.itemsize == 48
 
+CS_MAX_REFS = 3           # XVC_CS_MAX_REFS: pictures per list
+FP_BI_MAX_REF_PICS = 6    # XVC_FP_BI_MAX_REF_PICS: distinct reference pictures of a call
+FP_BI_NO_JOB = 255        # XVC_FP_BI_NO_JOB
+
+
+class FramePassBiRefsArgs(C.Structure):
+    """xvcgpu_frame_pass_bi_refs_args (include/xvcgpu_types.h)"""
+    _fields_ = [("p", FramePassArgs), ("num_ref", C.c_int32 * 2),
+                ("same_poc_in_l0", C.c_int8 * CS_MAX_REFS), ("force_l1_mvd_zero", C.c_uint8),
+                ("n_refs", C.c_int32), ("refs", C.c_void_p * FP_BI_MAX_REF_PICS),
+                ("slot", (C.c_uint8 * CS_MAX_REFS) * 2), ("ref_poc", (C.c_int32 * CS_MAX_REFS) * 2),
+                ("d_me", (C.c_void_p * CS_MAX_REFS) * 2),
+                ("d_results", (C.c_void_p * CS_MAX_REFS) * 2),
+                ("side_bits_uni", C.c_uint32 * 2), ("side_bits_bi", C.c_uint32),
+                ("d_bi_jobs", C.c_void_p), ("d_bi_results", C.c_void_p),
+                ("d_bi_slots", C.c_void_p), ("d_choice", C.c_void_p), ("d_inter", C.c_void_p)]
+
+
+# xvcgpu_fp_bi_refs_result: what SearchMotion ends with for one CU of a B picture whose lists
+# name several pictures
+FP_BI_REFS_RESULT_DTYPE = np.dtype([
+    ("inter_dir", "<i4"), ("search_list", "<i4"), ("ref_idx", "<i4", (2,)),
+    ("mv", "<i4", (2, 2)), ("cost_list", "<u4", (2,)), ("cost_l1_unique", "<u4"),
+    ("cost_bi", "<u4"), ("cost", "<u4"), ("best_ref", "<i4", (2,)),
+    ("best_ref_l1_unique", "<i4"), ("cost_uni", "<u4", (2, CS_MAX_REFS)),
+    ("bi_cost", "<u4", (CS_MAX_REFS,)), ("bi_mv", "<i4", (CS_MAX_REFS, 2))])
+assert FP_BI_REFS_RESULT_DTYPE.itemsize == 124
+
 FP_ENCODE, FP_DEBLOCK_V, FP_DEBLOCK_H, FP_PAD, FP_SSD = 1, 2, 4, 8, 16
 # FramePassArgs.form: XVC_FP_FORM_* is the index (0: none; include/xvcgpu_types.h)
 FP_FORM_NAMES = (None, "recon_from_me", "fwd_from_me", "fwd_transform", "residual",
@@ -222,6 +250,8 @@ SYMBOLS = [
     "xvcgpu_me_search_planned", "xvcgpu_frame_pass_planned",
     "xvcgpu_fp_bi_uni_fold", "xvcgpu_fp_bi_choice", "xvcgpu_cu_info_from_choice",
     "xvcgpu_frame_pass_bi",
+    "xvcgpu_fp_bi_refs_uni_fold", "xvcgpu_fp_bi_refs_choice", "xvcgpu_cu_info_from_choice_refs",
+    "xvcgpu_bipred_search_refs_planned", "xvcgpu_frame_pass_bi_refs",
 ]
 
 _vp = C.c_void_p
@@ -433,6 +463,11 @@ def load_library(allow_missing=()):
         "xvcgpu_cu_info_from_choice": [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int,
                                        C.c_int, C.c_int, _vp],
         "xvcgpu_frame_pass_bi": [_vp, C.POINTER(FramePassBiArgs), _vp, _vp, C.c_int],
+        "xvcgpu_fp_bi_refs_uni_fold": [_vp, C.POINTER(FramePassBiRefsArgs)],
+        "xvcgpu_fp_bi_refs_choice": [_vp, C.POINTER(FramePassBiRefsArgs)],
+        "xvcgpu_cu_info_from_choice_refs": [_vp, C.POINTER(FramePassBiRefsArgs)],
+        "xvcgpu_bipred_search_refs_planned": [_vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp],
+        "xvcgpu_frame_pass_bi_refs": [_vp, C.POINTER(FramePassBiRefsArgs), _vp, C.c_int],
     }
     if "xvcgpu_me_plan_destroy" not in allow_missing or hasattr(lib, "xvcgpu_me_plan_destroy"):
         lib.xvcgpu_me_plan_destroy.restype = None

@@ -153,17 +153,20 @@ __device__ __forceinline__ void wg_lic_model(int bd, int comp, int bx, int by, i
 // kSadAcOnly[Fast] and the sub-pel stage with kSatdAcOnly (GetFullpelMetric /
 // GetSubpelMetric, inter_search.cc:1059-1076) - both on the int16 target; the
 // candidates' own predictions stay plain (GetSubpelDist: post_filter = false).
+// job_at: the job index where the caller forms it (k_fp_bi_refs.h: through a plan's list);
+// BI_JOB_BY_XCD: the body forms it from the workgroup index, as every instance here does.
+#define BI_JOB_BY_XCD (-2)
 template <int MS, bool LIC = false>
 __device__ __forceinline__ void
 bipred_search_body(const PlaneView &orig, const PlaneView &ref_other_arg,
                    const PlaneView &ref_search_arg, int bd, const xvcgpu_bi_block *jobs, int n,
                    xvcgpu_me_result *out, int max_launched, const PlaneView &rec,
                    const xvcgpu_mc_lic_block *nb, const RefTable *refs = nullptr,
-                   const uint8_t *slots = nullptr) {
+                   const uint8_t *slots = nullptr, int job_at = BI_JOB_BY_XCD) {
   constexpr int NW = BI_WAVES(MS);
   __shared__ BiShared<MS> s;
   __shared__ int s_scale, s_offset;
-  const int ji = xcd_job_index(blockIdx.x, n);
+  const int ji = job_at == BI_JOB_BY_XCD ? xcd_job_index(blockIdx.x, n) : job_at;
   if (ji < 0) return;
   // (the *_refs form: slots[2 * job] = the searched picture, [2 * job + 1] = the other)
   int slot_s = 0, slot_o = 0;

@@ -32,6 +32,7 @@
 #include "k_cu_state.h"
 #include "k_cs_engine.h"
 #include "k_fp_bi.h"
+#include "k_fp_bi_refs.h"
 #include "xvcgpu_internal.h"
 
 namespace {
@@ -3115,6 +3116,229 @@ xvcgpu_status xvcgpu_bipred_search_refs(xvcgpu_ctx *ctx, const xvcgpu_picture *o
 #undef BI_REFS
   CHECK_LAUNCH(ctx, "bipred_search_refs");
   return XVCGPU_OK;
+}
+
+xvcgpu_status xvcgpu_bipred_search_refs_planned(xvcgpu_ctx *ctx, const xvcgpu_picture *orig,
+                                                const xvcgpu_picture *const *refs, int n_refs,
+                                                const xvcgpu_me_plan *plan, int jobs_per_cu,
+                                                const xvcgpu_bi_block *d_jobs,
+                                                const uint8_t *d_slots,
+                                                xvcgpu_me_result *d_results) {
+  if (!ctx || !orig || !plan || jobs_per_cu < 1 || jobs_per_cu > XVC_CS_MAX_REFS ||
+      (plan->n && (!d_jobs || !d_slots || !d_results)))
+    return XVCGPU_INVALID_ARGUMENT;
+  RefTable t;
+  const xvcgpu_status st = ref_table_of(ctx, orig, refs, n_refs, &t);
+  if (st != XVCGPU_OK) return st;
+  const int *first = plan->first;
+  if (first[XVCGPU_ME_PLAN_UNSUPPORTED] != first[XVCGPU_ME_PLAN_LIC16])
+    return fail(ctx, XVCGPU_INVALID_ARGUMENT, "bipred_search_refs_planned: the plan holds LIC jobs");
+  if (plan->n == 0) return XVCGPU_OK;
+  // a class = a run of adjacent bins = a run of the plan's list
+#define BI_PLANNED(MS, FROM, TO)                                                             \
+  do {                                                                                       \
+    const int n_wg = (first[TO] - first[FROM]) * jobs_per_cu;                                \
+    if (n_wg > 0)                                                                            \
+      hipLaunchKernelGGL((bipred_search_refs_planned_kernel<MS>), dim3(n_wg),                \
+                         dim3(64 * BI_WAVES(MS)), 0, ctx->stream, orig->v.c[0], t, d_slots,  \
+                         orig->bd, d_jobs, plan->d_order + first[FROM], n_wg, jobs_per_cu,   \
+                         d_results, plan->max_launched);                                     \
+  } while (0)
+  BI_PLANNED(16, XVCGPU_ME_PLAN_16X16, XVCGPU_ME_PLAN_C32);
+  BI_PLANNED(32, XVCGPU_ME_PLAN_C32, XVCGPU_ME_PLAN_C64_TEAM);
+  BI_PLANNED(64, XVCGPU_ME_PLAN_C64_TEAM, XVCGPU_ME_PLAN_LIC16);
+#undef BI_PLANNED
+  const int bad = (first[XVCGPU_ME_PLAN_BINS] - first[XVCGPU_ME_PLAN_UNSUPPORTED]) * jobs_per_cu;
+  if (bad > 0)
+    hipLaunchKernelGGL(bipred_refs_planned_unsupported_kernel, dim3((bad + 255) / 256), dim3(256),
+                       0, ctx->stream, plan->d_order + first[XVCGPU_ME_PLAN_UNSUPPORTED], bad,
+                       jobs_per_cu, d_slots, n_refs, d_results);
+  CHECK_LAUNCH(ctx, "bipred_search_refs_planned");
+  return XVCGPU_OK;
+}
+
+/* ---- the frame pass of a B picture, several reference pictures per list (k_fp_bi_refs.h) ---- */
+// The tables of the args block checked (*what names the field of a refusal) and turned into
+// the kernels' form
+static bool fp_bi_refs_tables(const xvcgpu_frame_pass_bi_refs_args *b, FpBiRefsDev *t,
+                              const char **what) {
+#define FPR_NEED(cond, text) \
+  if (!(cond)) {             \
+    *what = text;            \
+    return false;            \
+  }
+  memset(t, 0, sizeof(*t));
+  for (int l = 0; l < 2; l++)
+    FPR_NEED(b->num_ref[l] >= 1 && b->num_ref[l] <= XVC_CS_MAX_REFS,
+             "num_ref must be 1 .. XVC_CS_MAX_REFS per list");
+  FPR_NEED(!b->force_l1_mvd_zero,
+           "force_l1_mvd_zero: pictures with only back references are out of scope");
+  FPR_NEED(b->n_refs >= 1 && b->n_refs <= XVC_FP_BI_MAX_REF_PICS,
+           "n_refs must be 1 .. XVC_FP_BI_MAX_REF_PICS");
+  for (int r = 0; r < b->num_ref[1]; r++) {
+    const int s = b->same_poc_in_l0[r];
+    FPR_NEED(s < b->num_ref[0], "same_poc_in_l0 names no picture of list 0");
+    if (s >= 0) {
+      FPR_NEED(b->slot[1][r] == b->slot[0][s], "slot of a re-used picture differs from its twin's");
+      FPR_NEED(b->ref_poc[1][r] == b->ref_poc[0][s],
+               "ref_poc of a re-used picture differs from its twin's");
+    }
+  }
+  for (int l = 0; l < 2; l++)
+    for (int r = 0; r < b->num_ref[l]; r++) {
+      const int same = l == 1 ? b->same_poc_in_l0[r] : -1;
+      FPR_NEED(b->slot[l][r] < b->n_refs, "slot is not below n_refs");
+      FPR_NEED(b->d_me[l][r], "d_me is missing for a picture of a list");
+      FPR_NEED(same >= 0 || b->d_results[l][r], "d_results is missing for a searched picture");
+      t->me[l][r] = b->d_me[l][r];
+      t->res[l][r] = same >= 0 ? b->d_results[0][same] : b->d_results[l][r];
+      t->slot[l][r] = b->slot[l][r];
+      t->ref_poc[l][r] = b->ref_poc[l][r];
+      if (l == 1) t->same[r] = same;
+    }
+  FPR_NEED(b->d_bi_jobs && b->d_bi_results && b->d_bi_slots && b->d_choice && b->d_inter,
+           "d_bi_jobs, d_bi_results, d_bi_slots, d_choice and d_inter");
+#undef FPR_NEED
+  t->num_ref[0] = b->num_ref[0];
+  t->num_ref[1] = b->num_ref[1];
+  t->side_uni[0] = b->side_bits_uni[0];
+  t->side_uni[1] = b->side_bits_uni[1];
+  t->side_bi = b->side_bits_bi;
+  t->rmax = b->num_ref[0] > b->num_ref[1] ? b->num_ref[0] : b->num_ref[1];
+  return true;
+}
+
+xvcgpu_status xvcgpu_fp_bi_refs_uni_fold(xvcgpu_ctx *ctx,
+                                         const xvcgpu_frame_pass_bi_refs_args *b) {
+  if (!ctx || !b || b->p.n_cus < 0) return XVCGPU_INVALID_ARGUMENT;
+  FpBiRefsDev t;
+  const char *what = nullptr;
+  if (!fp_bi_refs_tables(b, &t, &what)) return fail(ctx, XVCGPU_INVALID_ARGUMENT, what);
+  const int n = b->p.n_cus;
+  if (n == 0) return XVCGPU_OK;
+  hipLaunchKernelGGL(fp_bi_refs_uni_fold_kernel, dim3((n + 255) / 256), dim3(256), 0,
+                     ctx->stream, t, n, b->d_bi_jobs, b->d_bi_slots, b->d_choice);
+  CHECK_LAUNCH(ctx, "fp_bi_refs_uni_fold");
+  return XVCGPU_OK;
+}
+
+xvcgpu_status xvcgpu_fp_bi_refs_choice(xvcgpu_ctx *ctx,
+                                       const xvcgpu_frame_pass_bi_refs_args *b) {
+  if (!ctx || !b || b->p.n_cus < 0) return XVCGPU_INVALID_ARGUMENT;
+  FpBiRefsDev t;
+  const char *what = nullptr;
+  if (!fp_bi_refs_tables(b, &t, &what)) return fail(ctx, XVCGPU_INVALID_ARGUMENT, what);
+  const int n = b->p.n_cus;
+  if (n == 0) return XVCGPU_OK;
+  hipLaunchKernelGGL(fp_bi_refs_choice_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream,
+                     t, n, b->d_bi_results, b->d_choice, b->d_inter);
+  CHECK_LAUNCH(ctx, "fp_bi_refs_choice");
+  return XVCGPU_OK;
+}
+
+xvcgpu_status xvcgpu_cu_info_from_choice_refs(xvcgpu_ctx *ctx,
+                                              const xvcgpu_frame_pass_bi_refs_args *b) {
+  if (!ctx || !b || b->p.n_cus < 0) return XVCGPU_INVALID_ARGUMENT;
+  const xvcgpu_frame_pass_args *a = &b->p;
+  const int n = a->n_cus;
+  if (n && (!b->d_me[0][0] || !b->d_choice || !a->d_nnz || !a->d_cus_own))
+    return XVCGPU_INVALID_ARGUMENT;
+  if (n == 0) return XVCGPU_OK;
+  FpBiRefsPocs pocs;
+  memcpy(pocs.poc, b->ref_poc, sizeof(pocs.poc));
+  hipLaunchKernelGGL(cu_info_from_choice_refs_kernel, dim3((n + 255) / 256), dim3(256), 0,
+                     ctx->stream, b->d_me[0][0], b->d_choice, a->d_nnz, a->d_luma_tx_index, n,
+                     a->qp_y, a->qp_c, pocs, a->d_cus_own);
+  CHECK_LAUNCH(ctx, "cu_info_from_choice_refs");
+  return XVCGPU_OK;
+}
+
+xvcgpu_status xvcgpu_frame_pass_bi_refs(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_bi_refs_args *b,
+                                        const xvcgpu_me_plan *const plans[2][XVC_CS_MAX_REFS],
+                                        int phases) {
+  if (!ctx || !b || !b->p.rec) return XVCGPU_INVALID_ARGUMENT;
+  // the P pass's block with list 0's first picture in the fields the shared helpers read
+  xvcgpu_frame_pass_args pa = b->p;
+  const xvcgpu_frame_pass_args *a = &pa;
+  const int n = a->n_cus;
+  FpBiRefsDev t;
+  const xvcgpu_me_plan *plan0 = nullptr;
+#define FPB_NEED(cond, what) \
+  if (!(cond)) return fail(ctx, XVCGPU_INVALID_ARGUMENT, "frame_pass_bi_refs: " what)
+  FPB_NEED(n == a->n_cus_total && a->db_y_begin == 0 && a->db_y_end >= a->rec->h &&
+               a->dbh_y_end >= a->rec->h && a->ssd_y_begin == 0 && a->ssd_y_end >= a->rec->h,
+           "whole pictures only (no row shard)");
+  if ((phases & XVC_FP_ENCODE) && n > 0) {
+    FPB_NEED(a->form == XVC_FP_FORM_FWD_TRANSFORM || a->form == XVC_FP_FORM_RESIDUAL ||
+                 a->form == XVC_FP_FORM_RESIDUAL_RDOQ,
+             "the form must be one with a prediction picture: FWD_TRANSFORM, RESIDUAL or "
+             "RESIDUAL_RDOQ");
+    const char *what = nullptr;
+    if (!fp_bi_refs_tables(b, &t, &what)) {
+      char msg[200];
+      snprintf(msg, sizeof(msg), "frame_pass_bi_refs: %s", what);
+      return fail(ctx, XVCGPU_INVALID_ARGUMENT, msg);
+    }
+    FPB_NEED(a->orig, "orig");
+    for (int k = 0; k < b->n_refs; k++)
+      FPB_NEED(b->refs[k] && b->refs[k]->w == a->orig->w && b->refs[k]->h == a->orig->h &&
+                   b->refs[k]->bd == a->orig->bd,
+               "refs holds a missing picture or one not of orig's size and depth");
+    FPB_NEED(a->rec->w == a->orig->w && a->rec->h == a->orig->h && a->rec->bd == a->orig->bd,
+             "rec is not a picture of orig's size and depth");
+    int given = 0, searched = 0;
+    for (int l = 0; l < 2; l++)
+      for (int r = 0; r < b->num_ref[l]; r++) {
+        if (l == 1 && b->same_poc_in_l0[r] >= 0) continue;
+        searched++;
+        const xvcgpu_me_plan *p = plans ? plans[l][r] : nullptr;
+        if (!p) continue;
+        given++;
+        FPB_NEED(p->n == n && p->d_blocks == b->d_me[l][r], "a plan was not made from its d_me");
+        FPB_NEED(p->max_launched == me_class_of(a->max_block_size),
+                 "a plan was made for another max_block_size class");
+        if (!plan0) plan0 = p;
+        for (int k = 0; k <= XVCGPU_ME_PLAN_BINS + 1; k++)
+          FPB_NEED(p->first[k] == plan0->first[k], "the plans' bin counts differ");
+      }
+    FPB_NEED(given == 0 || given == searched, "plans for every searched picture or for none");
+    FPB_NEED(!plan0 || plan0->first[XVCGPU_ME_PLAN_UNSUPPORTED] == plan0->first[XVCGPU_ME_PLAN_LIC16],
+             "the plans hold LIC jobs");
+    pa.ref = b->refs[b->slot[0][0]];
+    pa.d_me = b->d_me[0][0];
+    pa.d_results = b->d_results[0][0];
+    pa.ref_poc = b->ref_poc[0][0];
+  }
+#undef FPB_NEED
+  FramePassForm r;
+  xvcgpu_status st = frame_pass_resolve(ctx, a, phases, plan0, &r);
+  if (st != XVCGPU_OK) return st;
+  xvcgpu_picture *const rec = r.fused_tail ? a->scratch_rec : a->rec;
+  if (r.form) {
+    for (int l = 0; l < 2 && st == XVCGPU_OK; l++)
+      for (int q = 0; q < b->num_ref[l] && st == XVCGPU_OK; q++) {
+        if (l == 1 && b->same_poc_in_l0[q] >= 0) continue;   // :536-542: list 0 searched it
+        st = fp_search(ctx, a, b->refs[b->slot[l][q]], b->d_me[l][q], b->d_results[l][q],
+                       plan0 ? plans[l][q] : nullptr);
+      }
+    if (st == XVCGPU_OK) st = xvcgpu_fp_bi_refs_uni_fold(ctx, b);
+    // SearchBiIterative's one step of every CU into every picture of its searched list
+    if (st == XVCGPU_OK && plan0)
+      st = xvcgpu_bipred_search_refs_planned(ctx, a->orig, b->refs, b->n_refs, plan0, t.rmax,
+                                             b->d_bi_jobs, b->d_bi_slots, b->d_bi_results);
+    for (int cls = 16; !plan0 && cls <= me_class_of(a->max_block_size) && st == XVCGPU_OK;
+         cls *= 2)
+      st = xvcgpu_bipred_search_refs(ctx, a->orig, b->refs, b->n_refs, b->d_bi_jobs,
+                                     b->d_bi_slots, n * t.rmax, b->d_bi_results, cls);
+    if (st == XVCGPU_OK) st = xvcgpu_fp_bi_refs_choice(ctx, b);
+    // (the prediction reads its `rec` for LIC jobs only: there are none)
+    if (st == XVCGPU_OK)
+      st = xvcgpu_inter_pred_batch(ctx, b->refs, b->n_refs, a->rec, a->pred, b->d_inter, 3 * n);
+    if (st == XVCGPU_OK) st = fp_residual(ctx, a, rec, r.form);
+    if (st == XVCGPU_OK) st = xvcgpu_cu_info_from_choice_refs(ctx, b);
+  }
+  if (st == XVCGPU_OK) st = fp_tail(ctx, a, phases, r.fused_tail, 1);
+  return st;
 }
 
 xvcgpu_status xvcgpu_mc_metric_batch_refs(xvcgpu_ctx *ctx, const xvcgpu_picture *orig,

@@ -455,5 +455,260 @@ class FramePassBi {
   std::unique_ptr<Picture> pred_;
 };
 
+// The frame pass of a B picture whose lists name up to XVC_CS_MAX_REFS reference pictures each
+// (the C++ twin of pipeline.BiRefsFramePass): SearchMotion as the reference configures itself
+// - one search per picture that list 0 has not searched already (inter_search.cc:536-542), the
+// SearchBiIterative step into every picture of the list that lost, the choice against the
+// best of the pictures only list 1 names (:247-257) - then CompressAndEvalCbf, the B picture's
+// DeblockPicture, PadBorder and the PSNR walk: one C call (xvcgpu_frame_pass_bi_refs).
+// QuantFast (form RESIDUAL), closed-form side bits 3 / 3 / 5.  The work arrays between the
+// launches are owned here, as FramePassBi owns its own.
+class FramePassBiRefs {
+ public:
+  // The picture's POC and its lists' POCs; what the pass needs beyond them is derived:
+  // same_poc_in_l0 (ReferencePictureLists::GetSamePocMappingFor), the table of distinct
+  // pictures and force_l1_mvd_zero (PictureData::DetermineForceBipredL1MvdZero), which is
+  // out of scope and refused.
+  struct RefLists {
+    int cur_poc;
+    std::vector<int> poc[2];
+  };
+
+  FramePassBiRefs(const Context &ctx, int width, int height, int bitdepth, int qp,
+                  const RefLists &lists, int cu = 16, int search_range = 96)
+      : ctx_(ctx), h_(height), bd_(bitdepth), qp_(qp), qp_c_(ChromaQp(qp)), plan_() {
+    std::vector<CuRect> parts;
+    for (int y = 0; y < height; y += cu)
+      for (int x = 0; x < width; x += cu) {
+        const CuRect p = {x, y, width - x < cu ? width - x : cu, height - y < cu ? height - y : cu};
+        parts.push_back(p);
+      }
+    Build(width, height, lists, parts, search_range, cu, false);
+  }
+  FramePassBiRefs(const Context &ctx, int width, int height, int bitdepth, int qp,
+                  const RefLists &lists, const std::vector<CuRect> &partition,
+                  int search_range = 96)
+      : ctx_(ctx), h_(height), bd_(bitdepth), qp_(qp), qp_c_(ChromaQp(qp)), plan_() {
+    CheckPartition(width, height, partition);
+    int side = 16;
+    for (size_t i = 0; i < partition.size(); i++) {
+      side = partition[i].w > side ? partition[i].w : side;
+      side = partition[i].h > side ? partition[i].h : side;
+    }
+    Build(width, height, lists, partition, search_range, side <= 16 ? 16 : (side <= 32 ? 32 : 64),
+          true);
+  }
+  ~FramePassBiRefs() { DestroyPlans(); }
+  FramePassBiRefs(const FramePassBiRefs &) = delete;
+  FramePassBiRefs &operator=(const FramePassBiRefs &) = delete;
+
+  // New search jobs of (list, picture): predictors, flags, lambda, range; the CUs stay.
+  void SetJobs(int list, int ref_idx, const std::vector<xvcgpu_me_block> &me) {
+    if (list < 0 || list > 1 || ref_idx < 0 || ref_idx >= num_ref_[list] ||
+        me.size() != static_cast<size_t>(n_cus_))
+      throw Error(XVCGPU_INVALID_ARGUMENT, "FramePassBiRefs::SetJobs: no such (list, picture)");
+    ctx_.Check(xvcgpu_memcpy_h2d(ctx_.get(), d_me_[list][ref_idx]->data(), me.data(),
+                                 me.size() * sizeof(xvcgpu_me_block)));
+  }
+
+  // Enqueues one picture (asynchronous): rec becomes the padded reconstruction.  pics[l][r]:
+  // the lists' pictures in the lists' order, the same object where they name the same POC.
+  void Run(const Picture &orig, const std::vector<const Picture *> pics[2], Picture *rec) {
+    xvcgpu_frame_pass_bi_refs_args b = xvcgpu_frame_pass_bi_refs_args();
+    xvcgpu_frame_pass_args &a = b.p;
+    a.orig = orig.get();
+    a.rec = rec->get();
+    a.n_cus = a.n_cus_total = n_cus_;
+    a.max_block_size = max_cu_;
+    a.qp_y = qp_;
+    a.qp_c = qp_c_;
+    a.d_nnz = d_nnz_->data();
+    a.d_cus_own = d_cus_->data();
+    a.d_cus = d_cus_->data();
+    a.d_cu_map = d_map_->data();
+    a.map_stride = map_stride_;
+    a.db_y_begin = 0;
+    a.db_y_end = a.dbh_y_end = h_;
+    a.ssd_y_begin = 0;
+    a.ssd_y_end = 1 << 30;
+    a.shift_bitdepth = bd_;
+    a.d_ssd = d_ssd_->data();
+    a.pred = pred_->get();
+    a.d_tx = d_tx_->data();
+    a.n_tx = 3 * n_cus_;
+    a.d_luma_tx_index = d_luma_->data();
+    a.form = XVC_FP_FORM_RESIDUAL;
+    b.n_refs = static_cast<int32_t>(distinct_.size());
+    b.force_l1_mvd_zero = 0;
+    const xvcgpu_me_plan *plans[2][XVC_CS_MAX_REFS] = {};
+    for (int l = 0; l < 2; l++) {
+      if (pics[l].size() != static_cast<size_t>(num_ref_[l]))
+        throw Error(XVCGPU_INVALID_ARGUMENT, "FramePassBiRefs::Run: one picture per list entry");
+      b.num_ref[l] = num_ref_[l];
+      for (int r = 0; r < num_ref_[l]; r++) {
+        const int k = slot_[l][r];
+        if (b.refs[k] && b.refs[k] != pics[l][r]->get())
+          throw Error(XVCGPU_INVALID_ARGUMENT,
+                      "FramePassBiRefs::Run: the lists name one POC with two pictures");
+        b.refs[k] = pics[l][r]->get();
+        b.slot[l][r] = static_cast<uint8_t>(k);
+        b.ref_poc[l][r] = poc_[l][r];
+        b.d_me[l][r] = d_me_[l][r]->data();
+        b.d_results[l][r] = d_res_[l][r] ? d_res_[l][r]->data() : nullptr;
+        plans[l][r] = plan_[l][r];
+      }
+    }
+    for (int r = 0; r < XVC_CS_MAX_REFS; r++)
+      b.same_poc_in_l0[r] = static_cast<int8_t>(r < num_ref_[1] ? same_[r] : -1);
+    b.side_bits_uni[0] = b.side_bits_uni[1] = 3;
+    b.side_bits_bi = 5;
+    b.d_bi_jobs = d_bi_jobs_->data();
+    b.d_bi_results = d_bi_res_->data();
+    b.d_bi_slots = d_bi_slots_->data();
+    b.d_choice = d_choice_->data();
+    b.d_inter = d_inter_->data();
+    ctx_.Check(xvcgpu_frame_pass_bi_refs(ctx_.get(), &b, plans,
+                                         XVC_FP_ENCODE | XVC_FP_DEBLOCK_V | XVC_FP_DEBLOCK_H |
+                                             XVC_FP_PAD | XVC_FP_SSD));
+  }
+
+  // SampleMetric::ComputePsnr parts of the last Run (synchronises).
+  void Ssd(uint64_t *ssd, uint64_t *samples) const {
+    std::vector<uint64_t> v = d_ssd_->ToHost();
+    *ssd = v[0];
+    *samples = v[1];
+  }
+  // what SearchMotion ended with per CU, and the CU records the filter read
+  std::vector<xvcgpu_fp_bi_refs_result> Choices() const { return d_choice_->ToHost(); }
+  std::vector<xvcgpu_cu_info> CuInfo() const { return d_cus_->ToHost(); }
+  int num_cus() const { return n_cus_; }
+  int same_poc_in_l0(int ref_idx) const { return same_[ref_idx]; }
+
+ private:
+  void DestroyPlans() {
+    for (int l = 0; l < 2; l++)
+      for (int r = 0; r < XVC_CS_MAX_REFS; r++)
+        if (plan_[l][r]) {
+          xvcgpu_me_plan_destroy(ctx_.get(), plan_[l][r]);
+          plan_[l][r] = nullptr;
+        }
+  }
+
+  void Build(int width, int height, const RefLists &lists, const std::vector<CuRect> &parts,
+             int search_range, int max_cu, bool planned) {
+    bool only_back = true;
+    for (int l = 0; l < 2; l++) {
+      num_ref_[l] = static_cast<int>(lists.poc[l].size());
+      if (num_ref_[l] < 1 || num_ref_[l] > XVC_CS_MAX_REFS)
+        throw Error(XVCGPU_INVALID_ARGUMENT, "FramePassBiRefs: 1 .. XVC_CS_MAX_REFS pictures per list");
+      for (int r = 0; r < num_ref_[l]; r++) {
+        const int poc = lists.poc[l][r];
+        poc_[l][r] = poc;
+        only_back = only_back && poc < lists.cur_poc;
+        size_t k = 0;
+        while (k < distinct_.size() && distinct_[k] != poc) k++;
+        if (k == distinct_.size()) distinct_.push_back(poc);
+        slot_[l][r] = static_cast<int>(k);
+      }
+    }
+    if (only_back)
+      throw Error(XVCGPU_INVALID_ARGUMENT,
+                  "FramePassBiRefs: a picture with only back references (force_l1_mvd_zero) is "
+                  "out of this pass's scope");
+    for (int r = 0; r < XVC_CS_MAX_REFS; r++) {
+      same_[r] = -1;
+      for (int q = num_ref_[0] - 1; r < num_ref_[1] && q >= 0; q--)
+        if (poc_[0][q] == poc_[1][r]) same_[r] = q;   // (the first list-0 index)
+    }
+    rmax_ = num_ref_[0] > num_ref_[1] ? num_ref_[0] : num_ref_[1];
+    map_stride_ = (width + 3) / 4;
+    max_cu_ = max_cu;
+    n_cus_ = static_cast<int>(parts.size());
+    std::vector<int32_t> map(static_cast<size_t>(map_stride_) * ((height + 3) / 4), -1);
+    std::vector<xvcgpu_me_block> me;
+    std::vector<xvcgpu_tx_block> tx;
+    std::vector<int32_t> luma;
+    for (size_t i = 0; i < parts.size(); i++) {
+      const CuRect &p = parts[i];
+      xvcgpu_me_block b = xvcgpu_me_block();
+      b.x = static_cast<int16_t>(p.x);
+      b.y = static_cast<int16_t>(p.y);
+      b.w = static_cast<uint8_t>(p.w);
+      b.h = static_cast<uint8_t>(p.h);
+      b.depth_nonzero = 1;
+      b.lambda16 = Lambda16(qp_);
+      b.search_range = search_range;
+      me.push_back(b);
+      for (int yy = p.y / 4; yy < (p.y + p.h) / 4; yy++)
+        for (int xx = p.x / 4; xx < (p.x + p.w) / 4; xx++)
+          map[static_cast<size_t>(yy) * map_stride_ + xx] = static_cast<int32_t>(i);
+      luma.push_back(static_cast<int32_t>(3 * i));
+      for (int c = 0; c < 3; c++) {   // Y U V per CU: block 3 * cu + comp
+        const int sh = c ? 1 : 0;
+        xvcgpu_tx_block t = xvcgpu_tx_block();
+        t.x = static_cast<int16_t>(p.x >> sh);
+        t.y = static_cast<int16_t>(p.y >> sh);
+        t.w = static_cast<uint8_t>(p.w >> sh);
+        t.h = static_cast<uint8_t>(p.h >> sh);
+        t.comp = static_cast<uint8_t>(c);
+        t.qp = static_cast<int8_t>(c ? qp_c_ : qp_);
+        tx.push_back(t);
+      }
+    }
+    const size_t n = me.size();
+    for (int l = 0; l < 2; l++)
+      for (int r = 0; r < num_ref_[l]; r++) {
+        d_me_[l][r].reset(new DeviceArray<xvcgpu_me_block>(ctx_, me));
+        if (l == 0 || same_[r] < 0) d_res_[l][r].reset(new DeviceArray<xvcgpu_me_result>(ctx_, n));
+      }
+    d_bi_jobs_.reset(new DeviceArray<xvcgpu_bi_block>(ctx_, n * rmax_));
+    d_bi_res_.reset(new DeviceArray<xvcgpu_me_result>(ctx_, n * rmax_));
+    d_bi_slots_.reset(new DeviceArray<uint8_t>(ctx_, 2 * n * rmax_));
+    d_choice_.reset(new DeviceArray<xvcgpu_fp_bi_refs_result>(ctx_, n));
+    d_inter_.reset(new DeviceArray<xvcgpu_inter_block>(ctx_, 3 * n));
+    d_map_.reset(new DeviceArray<int32_t>(ctx_, map));
+    d_tx_.reset(new DeviceArray<xvcgpu_tx_block>(ctx_, tx));
+    d_luma_.reset(new DeviceArray<int32_t>(ctx_, luma));
+    d_nnz_.reset(new DeviceArray<int32_t>(ctx_, 3 * n));
+    d_cus_.reset(new DeviceArray<xvcgpu_cu_info>(ctx_, n));
+    d_ssd_.reset(new DeviceArray<uint64_t>(ctx_, 2));
+    ctx_.Check(xvcgpu_memset(ctx_.get(), d_cus_->data(), 0, n * sizeof(xvcgpu_cu_info)));
+    pred_.reset(new Picture(ctx_, width, height, bd_));
+    if (!planned) return;
+    for (int l = 0; l < 2; l++)
+      for (int r = 0; r < num_ref_[l]; r++) {
+        if (!d_res_[l][r]) continue;   // a re-used picture is not searched
+        int32_t counts[XVCGPU_ME_PLAN_BINS] = {0};
+        xvcgpu_status st = xvcgpu_me_plan_create(ctx_.get(), d_me_[l][r]->data(), n_cus_, max_cu_,
+                                                 &plan_[l][r]);
+        if (st == XVCGPU_OK) st = xvcgpu_me_plan_counts(plan_[l][r], counts);
+        if (st != XVCGPU_OK || counts[XVCGPU_ME_PLAN_UNSUPPORTED] > 0) {
+          DestroyPlans();   // (no destructor behind a constructor that throws)
+          ctx_.Check(st);
+          throw Error(XVCGPU_INVALID_ARGUMENT,
+                      "partition: the motion search has no instance for some CUs (sides must be "
+                      "4, 8, 16, 32 or 64)");
+        }
+      }
+  }
+
+  const Context &ctx_;
+  int h_, bd_, qp_, qp_c_, n_cus_, map_stride_, max_cu_, rmax_;
+  int num_ref_[2], poc_[2][XVC_CS_MAX_REFS], slot_[2][XVC_CS_MAX_REFS], same_[XVC_CS_MAX_REFS];
+  std::vector<int> distinct_;
+  xvcgpu_me_plan *plan_[2][XVC_CS_MAX_REFS];
+  std::unique_ptr<DeviceArray<xvcgpu_me_block>> d_me_[2][XVC_CS_MAX_REFS];
+  std::unique_ptr<DeviceArray<xvcgpu_me_result>> d_res_[2][XVC_CS_MAX_REFS], d_bi_res_;
+  std::unique_ptr<DeviceArray<xvcgpu_bi_block>> d_bi_jobs_;
+  std::unique_ptr<DeviceArray<uint8_t>> d_bi_slots_;
+  std::unique_ptr<DeviceArray<xvcgpu_fp_bi_refs_result>> d_choice_;
+  std::unique_ptr<DeviceArray<xvcgpu_inter_block>> d_inter_;
+  std::unique_ptr<DeviceArray<int32_t>> d_map_, d_luma_, d_nnz_;
+  std::unique_ptr<DeviceArray<xvcgpu_tx_block>> d_tx_;
+  std::unique_ptr<DeviceArray<xvcgpu_cu_info>> d_cus_;
+  std::unique_ptr<DeviceArray<uint64_t>> d_ssd_;
+  std::unique_ptr<Picture> pred_;
+};
+
 }  // namespace xvc_gpu
 #endif  // XVC_AMD_HOST_XVC_FRAME_PASS_H_

@@ -1,0 +1,68 @@
+// xvc_frame_pass_bi_refs.cc -- C entry point (for ctypes / tests) of
+// xvc_gpu::FramePassBiRefs (xvc_frame_pass.h): the B pass with several reference pictures
+// per list over the 16-sample CU grid, on borrowed handles.
+#include <cstdint>
+#include <cstring>
+#include <memory>
+#include <vector>
+
+#include "xvc_frame_pass.h"
+
+extern "C" {
+
+// pocs[l * 3 + r], ref_pics[l * 3 + r] (NULL beyond num_ref[l]); blocks[(l * 3 + r) * n + i]:
+// the search jobs per (list, picture), n = the grid's CUs (NULL: the class's own jobs).
+// out_choice[n], out_cus[n], out_ssd[2] after the pass has run (synchronises).
+int xvc_host_frame_pass_bi_refs(xvcgpu_ctx *ctx, int width, int height, int bitdepth, int qp,
+                                int cur_poc, const int32_t *num_ref, const int32_t *pocs,
+                                xvcgpu_picture *orig, xvcgpu_picture *const *ref_pics,
+                                xvcgpu_picture *rec, const xvcgpu_me_block *blocks, int n,
+                                xvcgpu_fp_bi_refs_result *out_choice, xvcgpu_cu_info *out_cus,
+                                uint64_t *out_ssd) {
+  if (!ctx || !num_ref || !pocs || !orig || !ref_pics || !rec || !out_choice || !out_cus ||
+      !out_ssd)
+    return XVCGPU_INVALID_ARGUMENT;
+  try {
+    xvc_gpu::Context c(ctx);
+    xvc_gpu::FramePassBiRefs::RefLists lists;
+    lists.cur_poc = cur_poc;
+    for (int l = 0; l < 2; l++) {
+      if (num_ref[l] < 1 || num_ref[l] > XVC_CS_MAX_REFS) return XVCGPU_INVALID_ARGUMENT;
+      lists.poc[l].assign(pocs + XVC_CS_MAX_REFS * l, pocs + XVC_CS_MAX_REFS * l + num_ref[l]);
+    }
+    xvc_gpu::FramePassBiRefs pass(c, width, height, bitdepth, qp, lists);
+    if (pass.num_cus() != n) return XVCGPU_INVALID_ARGUMENT;
+    xvc_gpu::Picture o(c, orig), r(c, rec);
+    // one view per handle: the lists name a re-used picture by the same object
+    std::vector<std::unique_ptr<xvc_gpu::Picture>> views;
+    std::vector<const xvc_gpu::Picture *> pics[2];
+    for (int l = 0; l < 2; l++)
+      for (int q = 0; q < num_ref[l]; q++) {
+        xvcgpu_picture *h = ref_pics[XVC_CS_MAX_REFS * l + q];
+        if (!h) return XVCGPU_INVALID_ARGUMENT;
+        const xvc_gpu::Picture *view = nullptr;
+        for (size_t k = 0; k < views.size(); k++)
+          if (views[k]->get() == h) view = views[k].get();
+        if (!view) {
+          views.emplace_back(new xvc_gpu::Picture(c, h));
+          view = views.back().get();
+        }
+        pics[l].push_back(view);
+        if (blocks) {
+          const xvcgpu_me_block *b = blocks + static_cast<size_t>(XVC_CS_MAX_REFS * l + q) * n;
+          pass.SetJobs(l, q, std::vector<xvcgpu_me_block>(b, b + n));
+        }
+      }
+    pass.Run(o, pics, &r);
+    pass.Ssd(&out_ssd[0], &out_ssd[1]);
+    const std::vector<xvcgpu_fp_bi_refs_result> choice = pass.Choices();
+    const std::vector<xvcgpu_cu_info> cus = pass.CuInfo();
+    std::memcpy(out_choice, choice.data(), choice.size() * sizeof(choice[0]));
+    std::memcpy(out_cus, cus.data(), cus.size() * sizeof(cus[0]));
+    return XVCGPU_OK;
+  } catch (const xvc_gpu::Error &e) {
+    return e.status;
+  }
+}
+
+}  // extern "C"

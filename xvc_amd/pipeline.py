@@ -701,6 +701,225 @@ class BiFramePass:
         self.p.destroy()
 
 
+def ref_list_tables(cur_poc, ref_pocs):
+    """What a B picture's two POC lists say as xvcgpu_frame_pass_bi_refs wants it:
+    (same_poc_in_l0 per list-1 picture - the first list-0 index of the same POC, or -1,
+    ReferencePictureLists::GetSamePocMappingFor -, the distinct POCs in order of first
+    mention, slot[l][r] into them, force_l1_mvd_zero - every reference before the picture,
+    PictureData::DetermineForceBipredL1MvdZero)."""
+    l0, l1 = (list(int(v) for v in ref_pocs[l]) for l in range(2))
+    same = [l0.index(v) if v in l0 else -1 for v in l1]
+    distinct = []
+    for v in l0 + l1:
+        if v not in distinct:
+            distinct.append(v)
+    slot = [[distinct.index(v) for v in l] for l in (l0, l1)]
+    return same, distinct, slot, all(v < cur_poc for v in l0 + l1)
+
+
+class BiRefsFramePass:
+    """The frame pass of a B picture whose lists name 1 .. api.CS_MAX_REFS pictures each
+    (xvcgpu_frame_pass_bi_refs): one search per picture that list 0 has not searched
+    already, the SearchBiIterative step into every picture of the list that lost (by block
+    class, through the plan on a partition), the choice against the best unique list-1
+    picture, prediction from the chosen pictures, the residual pipeline and the B tail - one
+    C call, nothing read back.  BiFramePass's sibling: forms, contexts and the shared
+    FramePass state (self.p) as there.
+
+    ref_pocs = [[list 0's POCs], [list 1's]] with cur_poc give same_poc_in_l0, the slot
+    table and force_l1_mvd_zero (ref_list_tables); a picture with only back references is
+    refused here.  run(orig, refs, rec): refs = [[list 0's pictures], [list 1's]] in the
+    lists' order, the same object where the lists name the same POC.  me[l][r] / d_me[l][r]:
+    the search jobs per (list, picture), copies of the descriptors until set_jobs."""
+
+    def __init__(self, ctx, width, height, bitdepth=10, qp=32, cu=16, rdoq=False,
+                 rdoq_packed=None, keep_levels=False, partition=None, cur_poc=8,
+                 ref_pocs=((4,), (12,)), search_range=96, side_bits=(3, 3, 5)):
+        self.ctx = ctx
+        self.cur_poc, self.side_bits = cur_poc, tuple(side_bits)
+        self.ref_pocs = [list(ref_pocs[0]), list(ref_pocs[1])]
+        self.num_ref = [len(l) for l in self.ref_pocs]
+        if not all(1 <= k <= api.CS_MAX_REFS for k in self.num_ref):
+            raise ValueError("ref_pocs: 1 .. %d pictures per list" % api.CS_MAX_REFS)
+        self.same, self.distinct, self.slot, force = ref_list_tables(cur_poc, self.ref_pocs)
+        if force:
+            raise ValueError("ref_pocs %r lie all before POC %d: a picture with only back "
+                             "references (force_l1_mvd_zero) is out of this pass's scope"
+                             % (self.ref_pocs, cur_poc))
+        self.rmax = max(self.num_ref)
+        self.p = p = FramePass(ctx, width, height, bitdepth, qp, cu, search_range, None, True,
+                               keep_levels, rdoq, rdoq_packed, False, partition)
+        self.desc = d = p.desc
+        p.form = "fwd_transform" if p.rdoq_packed else ("residual_rdoq" if rdoq else "residual")
+        self.form = p.form
+        if rdoq:
+            d.rdoq_contexts = rdoq_init_contexts(qp, 0)
+            ctx.h2d(p.d_rdoq_ctx.ptr, d.rdoq_contexts)
+        n = max(1, d.n_cus)
+        self.searched = [[l == 0 or self.same[r] < 0 for r in range(self.num_ref[l])]
+                         for l in range(2)]
+        self.me = [[d.me.copy() for _ in range(self.num_ref[l])] for l in range(2)]
+        self.d_me = [[ctx.buffer(m) for m in self.me[l]] for l in range(2)]
+        self.d_res = [[ctx.alloc(api.MERES_DTYPE.itemsize * n) if s else None
+                       for s in self.searched[l]] for l in range(2)]
+        self.d_bi_jobs = ctx.alloc(api.BI_DTYPE.itemsize * n * self.rmax)
+        self.d_bi_res = ctx.alloc(api.MERES_DTYPE.itemsize * n * self.rmax)
+        self.d_bi_slots = ctx.alloc(2 * n * self.rmax)
+        self.d_choice = ctx.alloc(api.FP_BI_REFS_RESULT_DTYPE.itemsize * n)
+        self.d_inter = ctx.alloc(api.INTER_DTYPE.itemsize * 3 * n)
+        self.plans = [[None] * self.num_ref[l] for l in range(2)]
+        if p.plan is not None:
+            for l in range(2):
+                for r in range(self.num_ref[l]):
+                    if self.searched[l][r]:
+                        self.plans[l][r] = ctx.me_plan(self.d_me[l][r].ptr, d.n_cus, d.cu_size)
+
+    def set_jobs(self, me):
+        """New search jobs me[l][r] (predictors, flags, lambda, range; the shapes stay);
+        None keeps an entry."""
+        for l in range(2):
+            for r in range(self.num_ref[l]):
+                new, old = me[l][r], self.me[l][r]
+                if new is not None:
+                    assert all(np.array_equal(new[k], old[k]) for k in ("x", "y", "w", "h"))
+                    old[...] = new
+                    self.ctx.h2d(self.d_me[l][r].ptr, old)
+
+    def _distinct_pictures(self, refs):
+        pics = [None] * len(self.distinct)
+        for l in range(2):
+            assert len(refs[l]) == self.num_ref[l]
+            for r, pic in enumerate(refs[l]):
+                k = self.slot[l][r]
+                assert pics[k] is None or pics[k] is pic, \
+                    "the lists name POC %d with two different pictures" % self.distinct[k]
+                pics[k] = pic
+        return pics
+
+    def _call_args(self, orig, refs, rec):
+        a = api.FramePassBiRefsArgs()
+        a.p = self.p._call_args(orig, None, rec, 0)
+        pics = self._distinct_pictures(refs)
+        a.n_refs = len(pics)
+        for k, pic in enumerate(pics):
+            a.refs[k] = pic.h_pic if pic is not None else None
+        a.force_l1_mvd_zero = 0
+        for r in range(api.CS_MAX_REFS):
+            a.same_poc_in_l0[r] = self.same[r] if r < self.num_ref[1] else -1
+        for l in range(2):
+            a.num_ref[l] = self.num_ref[l]
+            for r in range(self.num_ref[l]):
+                a.slot[l][r], a.ref_poc[l][r] = self.slot[l][r], self.ref_pocs[l][r]
+                a.d_me[l][r] = self.d_me[l][r].ptr
+                a.d_results[l][r] = self.d_res[l][r].ptr if self.searched[l][r] else None
+        a.side_bits_uni[0], a.side_bits_uni[1], a.side_bits_bi = self.side_bits
+        a.d_bi_jobs, a.d_bi_results = self.d_bi_jobs.ptr, self.d_bi_res.ptr
+        a.d_bi_slots, a.d_choice, a.d_inter = self.d_bi_slots.ptr, self.d_choice.ptr, \
+            self.d_inter.ptr
+        return a
+
+    def plan_handles(self, use=True):
+        """plans[2][CS_MAX_REFS] as the C call takes it (use=False: all NULL)."""
+        h = ((C.c_void_p * api.CS_MAX_REFS) * 2)()
+        for l in range(2):
+            for r, plan in enumerate(self.plans[l]):
+                h[l][r] = plan.h if use and plan is not None else None
+        return h
+
+    def run(self, orig, refs, rec, fused_tail=True, planned=True):
+        """Enqueue one whole-picture B pass (asynchronous).  fused_tail=False: end with the
+        separate deblocking, padding and SSD launches also where the one launch applies;
+        planned=False: sized searches and whole-list class launches also on a partition."""
+        a = self._call_args(orig, refs, rec)
+        if not fused_tail:
+            a.p.scratch_rec = None
+        self.ctx._check(self.ctx.lib.xvcgpu_frame_pass_bi_refs(
+            self.ctx.h, C.byref(a), self.plan_handles(planned),
+            api.FP_ENCODE | api.FP_DEBLOCK_V | api.FP_DEBLOCK_H | api.FP_PAD | api.FP_SSD))
+
+    def kernel_steps(self, orig, refs, rec, fused_tail=None, planned=True):
+        """The launches of one pass as (name, callable) in issue order, each through its own
+        entry point: run in order they are the pass (per-launch timing, tests)."""
+        ctx, lib, p, d = self.ctx, self.ctx.lib, self.p, self.desc
+        fused_tail = p.fused_tail if fused_tail is None else fused_tail
+        n, chk = d.n_cus, ctx._check
+        a = self._call_args(orig, refs, rec)
+        pics = self._distinct_pictures(refs)
+        handles = (C.c_void_p * len(pics))(*[q.h_pic for q in pics])
+        out = p.scratch if fused_tail else rec
+        planned = planned and p.plan is not None
+        steps = []
+
+        def search(l, r):
+            pic, res = refs[l][r], self.d_res[l][r].ptr
+            if planned:
+                return lambda: ctx.me_search_planned(orig, pic, api.ME_FULLPEL | api.ME_SUBPEL,
+                                                     self.plans[l][r], res)
+            return lambda: ctx.me_search_dev(orig, pic, p.me_flags, self.d_me[l][r].ptr, n, res,
+                                             d.cu_size)
+
+        def refine(cls):
+            return lambda: chk(lib.xvcgpu_bipred_search_refs(
+                ctx.h, orig.h_pic, handles, len(pics), self.d_bi_jobs.ptr, self.d_bi_slots.ptr,
+                n * self.rmax, self.d_bi_res.ptr, cls))
+        for l in range(2):
+            for r in range(self.num_ref[l]):
+                if self.searched[l][r]:
+                    steps.append(("me_search_l%d_r%d" % (l, r), search(l, r)))
+        steps.append(("uni_fold", lambda: chk(lib.xvcgpu_fp_bi_refs_uni_fold(ctx.h, C.byref(a)))))
+        if planned:
+            first = next(q for q in self.plans[0] if q is not None)
+            steps.append(("bipred_planned", lambda: chk(lib.xvcgpu_bipred_search_refs_planned(
+                ctx.h, orig.h_pic, handles, len(pics), first.h, self.rmax, self.d_bi_jobs.ptr,
+                self.d_bi_slots.ptr, self.d_bi_res.ptr))))
+        else:
+            steps += [("bipred_c%d" % cls, refine(cls)) for cls in (16, 32, 64)
+                      if cls <= d.cu_size]
+        steps += [
+            ("choice", lambda: chk(lib.xvcgpu_fp_bi_refs_choice(ctx.h, C.byref(a)))),
+            ("inter_pred", lambda: chk(lib.xvcgpu_inter_pred_batch(
+                ctx.h, handles, len(pics), rec.h_pic, p.pred.h_pic, self.d_inter.ptr, 3 * n)))]
+        # the form's residual pipeline: the P pass's launches between its prediction and
+        # its CU records
+        steps += p._launches(orig, pics[0], rec, 0, fused_tail)[0][2:-1]
+        steps.append(("cu_info", lambda: chk(lib.xvcgpu_cu_info_from_choice_refs(
+            ctx.h, C.byref(a)))))
+        all_cus, stride = p.d_cus.ptr, d.cu_map.shape[1]
+        if fused_tail:
+            return steps + [("deblock_pad_ssd", lambda: ctx.deblock_pad_ssd_dev(
+                out, rec, orig, all_cus, d.n_cus_total, p.d_map.ptr, stride, 1, 0, 0, p.bd,
+                p.d_ssd.ptr))]
+        return steps + [
+            ("deblock", lambda: ctx.deblock_dev(rec, all_cus, d.n_cus_total, p.d_map.ptr,
+                                                stride, 1, 0, 0, 4)),
+            ("pad_border", lambda: ctx.pad_border(rec)),
+            ("picture_ssd", lambda: ctx.picture_ssd_dev(orig, rec, 0, p.bd, p.d_ssd.ptr))]
+
+    def results(self):
+        """(search results res[l][r] - None for a re-used picture -, nnz, cus, ssd, the
+        choice records, the refinement results [n_cus, Rmax], the slot bytes [n_cus, Rmax, 2])."""
+        d = self.desc
+        _, nnz, cus, ssd = self.p.results()
+        res = [[b.to_array(api.MERES_DTYPE, d.n_cus) if b is not None else None for b in row]
+               for row in self.d_res]
+        return (res, nnz, cus, ssd,
+                self.d_choice.to_array(api.FP_BI_REFS_RESULT_DTYPE, d.n_cus),
+                self.d_bi_res.to_array(api.MERES_DTYPE, d.n_cus * self.rmax).reshape(-1, self.rmax),
+                self.d_bi_slots.to_array(np.uint8, 2 * d.n_cus * self.rmax).reshape(-1, self.rmax, 2))
+
+    def destroy(self):
+        bufs = [self.d_bi_jobs, self.d_bi_res, self.d_bi_slots, self.d_choice, self.d_inter]
+        for l in range(2):
+            bufs += self.d_me[l] + [b for b in self.d_res[l] if b is not None]
+            for plan in self.plans[l]:
+                if plan is not None:
+                    plan.destroy()
+            self.plans[l] = [None] * self.num_ref[l]
+        for b in bufs:
+            b.free()
+        self.p.destroy()
+
+
 class PipelinedFramePass:
     """The frame pass issued on two queues so that kernels of one half of the
     picture run while kernels of the other half ramp up or drain (a launch is
