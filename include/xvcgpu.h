@@ -1234,74 +1234,15 @@ xvcgpu_status xvcgpu_me_search_planned(xvcgpu_ctx *ctx, const xvcgpu_picture *or
 xvcgpu_status xvcgpu_frame_pass_planned(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_args *a,
                                         const xvcgpu_me_plan *plan, int phases);
 
-/* ---- the frame pass of a B picture --------------------------------------- *
+/* ---- the frame pass of a B picture ---------------------------------------- *
  * InterSearch::SearchMotion for two lists (inter_search.cc:198-259) over a whole picture
  * without leaving the device, composed of launches that exist and three one-thread-per-CU
- * decision kernels between them (each with its own entry point below).  ENCODE runs
- *
- *   search of list 0 (p.ref, p.d_me -> p.d_results), search of list 1 (ref1, d_me_l1 ->
- *   d_results_l1)  ->  xvcgpu_fp_bi_uni_fold  ->  xvcgpu_bipred_search of the CUs that refine
- *   list 0 (d_bi_jobs[0] -> d_bi_results[0]) and of those that refine list 1  ->
- *   xvcgpu_fp_bi_choice  ->  xvcgpu_inter_pred_batch({p.ref, ref1} -> p.pred, d_inter)  ->
- *   the residual pipeline of p.form  ->  xvcgpu_cu_info_from_choice
- *
- * and the phases behind it are xvcgpu_frame_pass's with the deblocking filter's
- * pic_is_bipred = 1 (the fused tail under the same conditions).  Scope: one reference
- * picture per list, one refinement iteration, translational motion (no LIC, no affine), a
- * job's mvp standing for both AMVP entries of its list (start and final index 0), the
- * closed-form side bits of the args, whole pictures (n_cus == n_cus_total, all rows).
- * p.form: FWD_TRANSFORM, RESIDUAL or RESIDUAL_RDOQ (RECON_FROM_ME and FWD_FROM_ME predict
- * from one list inside their kernel).  plan_l0 / plan_l1: both (made from p.d_me and from
- * d_me_l1, checked as xvcgpu_frame_pass_planned checks its plan) or both NULL.  Anything
- * else is XVCGPU_INVALID_ARGUMENT with a message, before the first launch.  Everything runs
- * on the context's stream; nothing synchronises, nothing allocates.
- *
- * xvcgpu_fp_bi_uni_fold: per CU and list cost_l = subpel_dist + (((side_bits_l + 1 +
- * GetMvdBits(mvp, mv, fullpel ? 2 : 0)) * lambda16) >> 16) (SearchRefIdx); the refined list
- * is the one that lost (cost_0 <= cost_1 ? 1 : 0) and gets its job in d_bi_jobs_l<that> -
- * blk the list's search job, other_mv the winner's vector, boot_mv its own -, the other
- * array a width-0 job at that index (answered with the unsupported record, never read).
- * d_choice[i]: search_list and cost_uni, the rest zero.  A CU with an
- * XVCGPU_ME_UNSUPPORTED result in either list: the record all ones, width-0 jobs in both.
- * xvcgpu_fp_bi_choice: cost_bi = refined subpel_dist + (((side_bits_bi + 2 + mvd bits of
- * both lists) * lambda16) >> 16), the searched list with its refined vector, the other with
- * its uni-directional one; bi on cost_bi <= both, else list 0 on cost_0 <= cost_1
- * (ChooseUniOrBi); completes d_choice[i] (read for search_list and cost_uni) and writes the
- * CU's prediction jobs d_inter[3 i + comp]: ref[l] = l or -1, mv[l][0], flags 0.
- * xvcgpu_cu_info_from_choice: xvcgpu_cu_info_from_me for two lists - ref_idx0 0 or -1,
- * ref_poc[l] the list's POC or -1, the four corners the list's vector (an unused list
- * zero), cbf_luma from d_nnz[d_luma_tx_index[i]]. */
-xvcgpu_status xvcgpu_fp_bi_uni_fold(xvcgpu_ctx *ctx, const xvcgpu_me_block *d_me_l0,
-                                    const xvcgpu_me_block *d_me_l1,
-                                    const xvcgpu_me_result *d_results_l0,
-                                    const xvcgpu_me_result *d_results_l1, int n,
-                                    uint32_t side_bits_l0, uint32_t side_bits_l1,
-                                    xvcgpu_bi_block *d_bi_jobs_l0, xvcgpu_bi_block *d_bi_jobs_l1,
-                                    xvcgpu_fp_bi_result *d_choice);
-xvcgpu_status xvcgpu_fp_bi_choice(xvcgpu_ctx *ctx, const xvcgpu_me_block *d_me_l0,
-                                  const xvcgpu_me_block *d_me_l1,
-                                  const xvcgpu_me_result *d_results_l0,
-                                  const xvcgpu_me_result *d_results_l1,
-                                  const xvcgpu_me_result *d_bi_results_l0,
-                                  const xvcgpu_me_result *d_bi_results_l1, int n,
-                                  uint32_t side_bits_bi, xvcgpu_fp_bi_result *d_choice,
-                                  xvcgpu_inter_block *d_inter);
-xvcgpu_status xvcgpu_cu_info_from_choice(xvcgpu_ctx *ctx, const xvcgpu_me_block *d_blocks,
-                                         const xvcgpu_fp_bi_result *d_choice,
-                                         const int32_t *d_nnz, const int32_t *d_luma_tx_index,
-                                         int n, int qp_y, int qp_c, int ref_poc_l0,
-                                         int ref_poc_l1, xvcgpu_cu_info *d_cus);
-xvcgpu_status xvcgpu_frame_pass_bi(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_bi_args *a,
-                                   const xvcgpu_me_plan *plan_l0, const xvcgpu_me_plan *plan_l1,
-                                   int phases);
-
-/* ---- the frame pass of a B picture, several reference pictures per list ---- *
- * xvcgpu_frame_pass_bi with num_ref[l] = 1 .. XVC_CS_MAX_REFS pictures per list as the
- * reference encoder codes a B picture: inside a sub-GOP the lists name the same pictures in
- * opposite order, SearchRefIdx then re-uses list 0's result for list 1
- * (same_poc_in_l0[r] >= 0, inter_search.cc:536-542) and the final choice is made against
- * the best of the pictures only list 1 names (cost_l1_unique, :247-257).  ENCODE runs, on
- * the context's stream, without synchronising or allocating:
+ * decision kernels between them (each with its own entry point below), with num_ref[l] = 1
+ * .. XVC_CS_MAX_REFS pictures per list as the reference encoder codes a B picture: inside a
+ * sub-GOP the lists name the same pictures in opposite order, SearchRefIdx then re-uses
+ * list 0's result for list 1 (same_poc_in_l0[r] >= 0, :536-542) and the final choice is made
+ * against the best of the pictures only list 1 names (cost_l1_unique, :247-257).  ENCODE
+ * runs, on the context's stream, without synchronising or allocating:
  *
  *   1  one search per (l, r) that is not re-used (d_me[l][r] on refs[slot[l][r]] ->
  *      d_results[l][r]), sized or through plans[l][r]
@@ -1315,7 +1256,10 @@ xvcgpu_status xvcgpu_frame_pass_bi(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_bi_a
  *   6  the residual pipeline of p.form
  *   7  xvcgpu_cu_info_from_choice_refs
  *
- * and the phases behind it are xvcgpu_frame_pass's with pic_is_bipred = 1.  Scope: one
+ * and the phases behind it are xvcgpu_frame_pass's with the deblocking filter's
+ * pic_is_bipred = 1 (the fused tail under the same conditions).  One picture per list is
+ * num_ref = {1, 1}, same_poc_in_l0[0] = -1, n_refs = 2, slot = {{0}, {1}}: Rmax = 1, one
+ * refinement job per CU, every slot byte a job, RefIdxBits 0.  Scope: one
  * refinement iteration, translational motion (no LIC, no affine), a job's mvp standing for
  * both AMVP entries of its (list, picture), the caller's closed-form side bits (3 / 3 / 5)
  * to which the device adds RefIdxBits(num_ref, r) = num_ref <= 1 ? 0 : r + 1 - (r == num_ref
@@ -1348,8 +1292,9 @@ xvcgpu_status xvcgpu_frame_pass_bi(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_bi_a
  * both, else list 0 on cost_l0 <= cost_l1_unique, else the best unique list-1 state; writes
  * the record and the CU's prediction jobs d_inter[3 i + comp] with ref[l] = the table slot of
  * the chosen picture, or -1.
- * xvcgpu_cu_info_from_choice_refs: xvcgpu_cu_info_from_choice with ref_idx0 = the chosen
- * list-0 index or -1 and ref_poc[l] = the chosen picture's POC or -1. */
+ * xvcgpu_cu_info_from_choice_refs: xvcgpu_cu_info_from_me for two lists - ref_idx0 = the
+ * chosen list-0 index or -1, ref_poc[l] = the chosen picture's POC or -1, the four corners
+ * the list's vector (an unused list zero), cbf_luma from d_nnz[d_luma_tx_index[i]]. */
 xvcgpu_status xvcgpu_fp_bi_refs_uni_fold(xvcgpu_ctx *ctx,
                                          const xvcgpu_frame_pass_bi_refs_args *a);
 xvcgpu_status xvcgpu_fp_bi_refs_choice(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_bi_refs_args *a);

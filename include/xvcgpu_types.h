@@ -605,43 +605,9 @@ typedef struct xvcgpu_frame_pass_args {
 } xvcgpu_frame_pass_args;
 
 /* What InterSearch::SearchMotion (inter_search.cc:198-259) ends with for one CU of a B
- * picture with one reference picture per list (xvcgpu_frame_pass_bi), and what shows why:
- * the lists' uni-directional costs, the list SearchBiIterative refined (the one that lost
- * the uni-directional comparison), the refined vector and the bi-directional cost.  A CU
- * whose search has no kernel instance (XVCGPU_ME_UNSUPPORTED): every byte 0xff. */
-typedef struct xvcgpu_fp_bi_result {
-  int32_t inter_dir;      /* 0 L0, 1 L1, 2 bi                                   */
-  int32_t search_list;    /* the refined list                                   */
-  uint32_t cost_uni[2];   /* SearchRefIdx's cost per list                       */
-  uint32_t cost_bi;       /* SearchBiIterative's cost after the one iteration   */
-  uint32_t cost;          /* the chosen state's                                 */
-  int32_t mv[2][2];       /* [list][x, y], 1/16 pel; the unused list is zero    */
-  int32_t bi_mv[2];       /* the refined vector of search_list                  */
-} xvcgpu_fp_bi_result;
-
-/* xvcgpu_frame_pass_bi: the frame pass of a B picture.  p is the P pass's block with
- * p.ref, p.d_me, p.d_results and p.ref_poc meaning list 0; the fields below add list 1,
- * the closed-form side bits (GetInterPredBits without predictor index and vector
- * difference: 3, 3 and 5 with fast_inter_pred_bits) and the work arrays between the
- * launches, all allocated by the caller. */
-typedef struct xvcgpu_frame_pass_bi_args {
-  xvcgpu_frame_pass_args p;
-  const struct xvcgpu_picture *ref1;
-  const xvcgpu_me_block *d_me_l1;   /* list 1's search jobs: the CUs of p.d_me      */
-  xvcgpu_me_result *d_results_l1;
-  int32_t ref_poc_l1;
-  uint32_t side_bits_uni[2];
-  uint32_t side_bits_bi;
-  xvcgpu_bi_block *d_bi_jobs[2];    /* n_cus each: the refinement jobs by searched
-                                     * list (a width-0 job where the CU refines the
-                                     * other list)                                  */
-  xvcgpu_me_result *d_bi_results[2];/* n_cus each                                   */
-  xvcgpu_fp_bi_result *d_choice;    /* n_cus                                        */
-  xvcgpu_inter_block *d_inter;      /* 3 * n_cus: the CUs' prediction jobs Y, U, V  */
-} xvcgpu_frame_pass_bi_args;
-
-/* What InterSearch::SearchMotion ends with for one CU of a B picture with several reference
- * pictures per list (xvcgpu_frame_pass_bi_refs), and what shows why.  Unused entries
+ * picture (xvcgpu_frame_pass_bi_refs), and what shows why: the uni-directional costs per
+ * (list, picture) and per list, the list SearchBiIterative refined (the one that lost the
+ * uni-directional comparison), the refined vectors and the bi-directional cost.  Unused entries
  * (r >= num_ref[l], k >= num_ref[search_list], no unique list-1 picture) hold UINT32_MAX as
  * a cost, -1 as an index and 0 as a vector.  A CU whose search has no kernel instance
  * (XVCGPU_ME_UNSUPPORTED): every byte 0xff. */
@@ -661,10 +627,12 @@ typedef struct xvcgpu_fp_bi_refs_result {
   int32_t bi_mv[XVC_CS_MAX_REFS][2];     /* the refined vector into picture k            */
 } xvcgpu_fp_bi_refs_result;
 
-/* xvcgpu_frame_pass_bi_refs: the frame pass of a B picture whose lists name up to
+/* xvcgpu_frame_pass_bi_refs: the frame pass of a B picture whose lists name 1 to
  * XVC_CS_MAX_REFS pictures each.  p is the P pass's block; p.ref, p.d_me, p.d_results and
- * p.ref_poc are ignored (the tables below say them per list and picture).  All arrays are
- * allocated by the caller. */
+ * p.ref_poc are ignored (the tables below say them per list and picture).  side_bits_*: the
+ * closed-form side bits (GetInterPredBits without reference index, predictor index and
+ * vector difference: 3, 3 and 5 with fast_inter_pred_bits).  All arrays, the work arrays
+ * between the launches included, are allocated by the caller. */
 #define XVC_FP_BI_MAX_REF_PICS 6   /* distinct reference pictures of a call */
 #define XVC_FP_BI_NO_JOB 255       /* first slot byte of a refinement job nobody runs */
 typedef struct xvcgpu_frame_pass_bi_refs_args {

@@ -1,25 +1,28 @@
-"""The expected frame pass of a B picture whose lists name several reference pictures
-(xvcgpu_frame_pass_bi_refs, pipeline.BiRefsFramePass), composed of the oracle's pinned
-pieces as tests/bi_pass_model.py composes the pass with one picture per list: per searched
-(list, picture) xo.tz_search + xo.subpel_search, xo.bipred_search per refinement job,
-xo.mc_block / xo.mc_bipred_block from the chosen pictures, the residual pipeline,
-xo.deblock(bipred=1), xo.pad_border, xo.picture_ssd - and the two folds of
-InterSearch::SearchMotion (uni_fold, choice_fold) in Python integers, worded as
-include/xvcgpu.h words them.  Its SearchMotion half is pinned to the reference's own member
-function by tests/test_bi_refs_pass_model.py.
+"""The expected frame pass of a B picture (xvcgpu_frame_pass_bi_refs,
+pipeline.BiRefsFramePass), composed in numpy / ctypes from the oracle's pinned pieces
+(tests/oracle_lib.py): per searched (list, picture) xo.tz_search + xo.subpel_search,
+xo.bipred_search per refinement job, xo.mc_block / xo.mc_bipred_block from the chosen
+pictures, the residual pipeline per transform block, xo.deblock(bipred=1), xo.pad_border,
+xo.picture_ssd - and the two folds of InterSearch::SearchMotion (inter_search.cc:198-259;
+uni_fold, choice_fold) in Python integers, worded as include/xvcgpu.h words them.  Its
+SearchMotion half is pinned to the reference's own member function by
+tests/test_bi_refs_pass_model.py.
 
-Also the reference picture sets the tests share (SETS, make_refs).
+Also the inputs (INPUTS, partition_128, descriptors) and the reference picture sets (SETS,
+make_refs) the B-pass tests share.
 
 TEST INFRASTRUCTURE."""
 import ctypes as C
 
 import numpy as np
 
-import bi_pass_model as bm
 import helpers
 import oracle_lib as ol
 
-BL, BC = bm.BL, bm.BC
+BL, BC = 128, 64          # luma / chroma borders of the padded planes
+LAMBDA16, QP = 498000, 32
+SIDE_BITS = (3, 3, 5)     # fast_inter_pred_bits: uni L0, uni L1, bi
+SEARCH_RANGE = 128        # the descriptors' range (jobs() gives each picture its own)
 CUR_POC = 8
 MAX_REFS = 3
 NO_JOB = 255
@@ -28,7 +31,7 @@ NONE = 0xffffffff
 SETS = {"A": ((4, 0), (12, 16)),        # four distinct pictures
         "B": ((4, 12), (12, 4)),        # both list-1 entries re-used: L1 is never chosen
         "C": ((4, 0, 16), (16, 12)),    # Rmax 3, a no-job slot in list 1, one entry re-used
-        "D": ((4,), (12,))}             # one picture per list: xvcgpu_frame_pass_bi's case
+        "D": ((4,), (12,))}             # one picture per list: Rmax 1, every slot a job
 # luma displacement (rows, columns; even, so that chroma moves by half) per POC; 12 and 16
 # cost the same vector bits
 SHIFT = {0: (4, -6), 4: (2, -2), 12: (-2, 4), 16: (2, -4)}
@@ -44,6 +47,66 @@ CHOICE_DTYPE = np.dtype([
     ("cost_bi", "<u4"), ("cost", "<u4"), ("best_ref", "<i4", (2,)),
     ("best_ref_l1_unique", "<i4"), ("cost_uni", "<u4", (2, MAX_REFS)),
     ("bi_cost", "<u4", (MAX_REFS,)), ("bi_mv", "<i4", (MAX_REFS, 2))])
+
+
+def partition_128():
+    """The 128x128 partition of 111 CUs: every search and refinement class, a side of 4."""
+    p = [(0, 0, 64, 64), (64, 0, 32, 32), (96, 0, 32, 32), (64, 32, 32, 16), (64, 48, 32, 16),
+         (96, 32, 16, 32), (112, 32, 16, 32)]
+    p += [(x, y, 16, 16) for y in (64, 80) for x in range(0, 128, 16)]
+    p += [(x, y, 8, 8) for y in (96, 104) for x in range(0, 128, 8)]
+    p += [(x, y, 8, 4) for y in (112, 116) for x in range(0, 64, 8)]
+    p += [(x, 120, 8, 8) for x in range(0, 64, 8)]
+    p += [(x, y, 4, 8) for y in (112, 120) for x in range(64, 128, 4)]
+    assert len(p) == 111
+    return np.array(p, np.int32)
+
+
+# name -> (width, height, bit depth, partition or None for the 16-sample grid)
+INPUTS = {"grid10": (104, 72, 10, None), "grid8": (104, 72, 8, None),
+          "part10": (128, 128, 10, partition_128)}
+
+
+def _original(rng, bd, pw, ph, border):
+    """One component's padded original: between two textured pictures, the first displaced
+    on the left quarter, the second displaced on the right quarter, their mean between,
+    plus noise."""
+    _, ref0 = helpers.make_pics(rng, bd, pw, ph, border, (0, 0))
+    _, ref1 = helpers.make_pics(rng, bd, pw, ph, border, (0, 0))
+    a = np.roll(ref0, (2, -5), (0, 1)).astype(np.int32)
+    b = np.roll(ref1, (-3, 6), (0, 1)).astype(np.int32)
+    x = np.arange(a.shape[1])[None, :] - border
+    orig = np.where(x < pw // 4, a, np.where(x >= 3 * pw // 4, b, (a + b + 1) // 2))
+    orig = np.clip(orig + rng.integers(-2, 3, a.shape), 0, (1 << bd) - 1).astype(np.uint16)
+    return np.ascontiguousarray(orig)
+
+
+def descriptors(name, rdoq=False):
+    """pipeline.FrameDescriptors of the input as BiRefsFramePass builds them (the B
+    picture's contexts for RDOQ), with the tests' lambda."""
+    from xvc_amd import pipeline
+    pw, ph, bd, part = INPUTS[name]
+    d = pipeline.FrameDescriptors(pw, ph, QP, search_range=SEARCH_RANGE, rdoq=rdoq, bitdepth=bd,
+                                  partition=part() if part else None)
+    d.me["lambda16"] = LAMBDA16
+    if rdoq:
+        d.rdoq_contexts = pipeline.rdoq_init_contexts(QP, 0)
+    return d
+
+
+def eg_bits(v):
+    """GetNumExpGolombBits (inter_search.cc:1179-1188)"""
+    u = ((-v) << 1) + 1 if v <= 0 else v << 1
+    n = 1
+    while u != 1:
+        u >>= 1
+        n += 2
+    return n
+
+
+def mvd_bits(b, mv):
+    sh = 2 + (2 if int(b["fullpel_mv"]) & 1 else 0)
+    return eg_bits((mv[0] - int(b["mvp_x"])) >> sh) + eg_bits((mv[1] - int(b["mvp_y"])) >> sh)
 
 
 def tables(lists):
@@ -62,7 +125,10 @@ def make_refs(name):
     """(pw, ph, bd, partition, orig, {poc: [Y, U, V] padded planes}): every reference is the
     input's original with grain of GRAIN's strength, displaced by SHIFT[poc], so that
     different pictures and all directions win in different CUs."""
-    pw, ph, bd, part, orig, _, _ = bm.make_input(name)
+    pw, ph, bd, part = INPUTS[name]
+    rng = np.random.default_rng(7700 + bd)
+    orig = [_original(rng, bd, pw >> (c > 0), ph >> (c > 0), BC if c else BL) for c in range(3)]
+    part = part() if part else None
     rng = np.random.default_rng(9100 + bd)
     shared = [rng.integers(-64, 65, p.shape) for p in orig]
     refs = {}
@@ -106,7 +172,7 @@ def _cost(dist, bits, lambda16):
     return (dist + ((bits * lambda16) >> 16)) & NONE
 
 
-def uni_fold(lists, me, res, side_bits=bm.SIDE_BITS):
+def uni_fold(lists, me, res, side_bits=SIDE_BITS):
     """xvcgpu_fp_bi_refs_uni_fold.  me[l][r]: the jobs; res[l][r]: the search results, None
     for a re-used list-1 picture.  Returns (choice with the fold's fields, jobs [n, Rmax],
     slot bytes [n, Rmax, 2]); a job nobody writes stays zero."""
@@ -126,7 +192,7 @@ def uni_fold(lists, me, res, side_bits=bm.SIDE_BITS):
                 q, b = eff[l][r][i], me[l][r][i]
                 bad = bad or int(q["subpel_dist"]) == NONE
                 mv = (int(q["mv_x"]), int(q["mv_y"]))
-                bits = side_bits[l] + ref_idx_bits(num_ref[l], r) + 1 + bm.mvd_bits(b, mv)
+                bits = side_bits[l] + ref_idx_bits(num_ref[l], r) + 1 + mvd_bits(b, mv)
                 cost = _cost(int(q["subpel_dist"]), bits, int(b["lambda16"]))
                 c["cost_uni"][l][r] = cost
                 if cost < best_cost[l]:
@@ -150,7 +216,7 @@ def uni_fold(lists, me, res, side_bits=bm.SIDE_BITS):
     return choice, jobs, slots
 
 
-def choice_fold(lists, me, res, bi_res, choice, side_bits=bm.SIDE_BITS):
+def choice_fold(lists, me, res, bi_res, choice, side_bits=SIDE_BITS):
     """xvcgpu_fp_bi_refs_choice: completes a copy of uni_fold's records from the refinement
     results bi_res [n, Rmax].  Returns (choice, the prediction jobs as (x, y, w, h, ref[2],
     mv[2][2]) per CU)."""
@@ -173,7 +239,7 @@ def choice_fold(lists, me, res, bi_res, choice, side_bits=bm.SIDE_BITS):
         def uni_mv(l, r):
             return (int(eff[l][r][i]["mv_x"]), int(eff[l][r][i]["mv_y"]))
         bits_o = side_bits[2] + ref_idx_bits(num_ref[o], best[o]) + 1 + \
-            bm.mvd_bits(me[o][best[o]][i], uni_mv(o, best[o]))
+            mvd_bits(me[o][best[o]][i], uni_mv(o, best[o]))
         cost_bi, best_k, best_mv = NONE, -1, (0, 0)
         c["bi_cost"], c["bi_mv"] = NONE, 0
         for k in range(num_ref[s]):
@@ -182,7 +248,7 @@ def choice_fold(lists, me, res, bi_res, choice, side_bits=bm.SIDE_BITS):
             cost = NONE
             if int(r["subpel_dist"]) != NONE:
                 cost = _cost(int(r["subpel_dist"]),
-                             bits_o + ref_idx_bits(num_ref[s], k) + 1 + bm.mvd_bits(b, mv),
+                             bits_o + ref_idx_bits(num_ref[s], k) + 1 + mvd_bits(b, mv),
                              int(b["lambda16"]))
             c["bi_cost"][k], c["bi_mv"][k] = cost, mv
             if cost < cost_bi:
@@ -230,7 +296,7 @@ def uni_search(xo, key, bd, pw, ph, orig_y, ref_y, me):
     return res
 
 
-def search_motion(xo, bd, pw, ph, orig_y, refs, lists, me, side_bits=bm.SIDE_BITS, key=None):
+def search_motion(xo, bd, pw, ph, orig_y, refs, lists, me, side_bits=SIDE_BITS, key=None):
     """SearchMotion for every CU.  refs: {poc: planes}; me[l][r]: the jobs.  Returns (res[l][r]
     - None where re-used -, the refinement results [n, Rmax] with zeros where there is no job,
     the slot bytes, the choice records, the prediction jobs)."""
@@ -265,7 +331,7 @@ def _ptr(a):
 
 
 def frame_pass(xo, desc, bd, orig, refs, lists, searched):
-    """The whole pass over desc (bm.descriptors()); searched: search_motion's answer for its
+    """The whole pass over desc (descriptors()); searched: search_motion's answer for its
     jobs.  Returns (padded rec planes, res, nnz, cus, (ssd, samples), choice, bi, slots,
     the prediction picture's planes, the levels per transform block)."""
     pw, ph = desc.w, desc.h

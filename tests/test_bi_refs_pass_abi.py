@@ -1,8 +1,6 @@
-"""CPU-side checks of the boundary of the B pass with several reference pictures per list:
-the entry points exported by the built library, the two new structs as the C compiler lays
-them out against their ctypes / numpy mirrors in xvc_amd/api.py, the existing B-pass block
-unchanged beside them, and xvc_gpu::FramePassBiRefs against the public headers with plain
-g++."""
+"""CPU-side checks of the B pass's boundary: the entry points exported by the built library,
+the two structs as the C compiler lays them out against their ctypes / numpy mirrors in
+xvc_amd/api.py, and xvc_gpu::FramePassBiRefs against the public headers with plain g++."""
 import ctypes as C
 import os
 import subprocess
@@ -33,7 +31,7 @@ def test_entry_points_are_exported():
 def test_struct_layouts_match_header(tmp_path):
     from xvc_amd import api
     what = ["sizeof(xvcgpu_frame_pass_bi_refs_args)", "sizeof(xvcgpu_fp_bi_refs_result)",
-            "sizeof(xvcgpu_frame_pass_bi_args)", "sizeof(xvcgpu_frame_pass_args)",
+            "sizeof(xvcgpu_frame_pass_args)",
             "(size_t)XVC_CS_MAX_REFS", "(size_t)XVC_FP_BI_MAX_REF_PICS",
             "(size_t)XVC_FP_BI_NO_JOB"] + \
         ["offsetof(xvcgpu_frame_pass_bi_refs_args, %s)" % f for f in _ARGS_FIELDS] + \
@@ -45,14 +43,12 @@ def test_struct_layouts_match_header(tmp_path):
     subprocess.check_call(["gcc", "-std=c99", "-I", INC, str(src), "-o", exe])
     out = [int(v) for v in subprocess.check_output([exe]).decode().split()]
     A, R = api.FramePassBiRefsArgs, api.FP_BI_REFS_RESULT_DTYPE
-    assert out == [C.sizeof(A), R.itemsize, C.sizeof(api.FramePassBiArgs),
+    assert out == [C.sizeof(A), R.itemsize,
                    C.sizeof(api.FramePassArgs), api.CS_MAX_REFS, api.FP_BI_MAX_REF_PICS,
                    api.FP_BI_NO_JOB] + [getattr(A, f).offset for f in _ARGS_FIELDS] + \
         [R.fields[f][1] for f in _RESULT_FIELDS]
-    # the block embeds the P pass's, unchanged, at its start; the one-picture B block is
-    # what it was: the P block and 88 bytes behind it
+    # the block embeds the P pass's, unchanged, at its start
     assert A.p.offset == 0 and A.p.size == C.sizeof(api.FramePassArgs) == 240
-    assert C.sizeof(api.FramePassBiArgs) == 240 + 88 and api.FP_BI_RESULT_DTYPE.itemsize == 48
     assert R.itemsize == 124 and R == rm.CHOICE_DTYPE
     assert (api.CS_MAX_REFS, api.FP_BI_NO_JOB) == (rm.MAX_REFS, rm.NO_JOB)
 

@@ -1,19 +1,17 @@
-"""The model of the B pass with several reference pictures per list
-(tests/bi_refs_pass_model.py) against the reference: its SearchMotion half - the searches
+"""The model of the B pass (tests/bi_refs_pass_model.py) against the reference: its SearchMotion half - the searches
 per picture, the re-use of list 0's results, the SearchBiIterative step into every picture,
 the folds and the choice against the best unique list-1 picture - must equal
 InterSearch::SearchMotion (xr_search_motion_multi of oracle/_ref) CU for CU on the inputs
 and picture sets the GPU tests run, so that the device pass is pinned to the reference
 through the model.  No neighbours: every AMVP list is zero, as the jobs' predictors are.
 
-The coverage the GPU tests rely on is checked here too (and printed: DESIGN section 10
+The coverage the GPU tests rely on is checked here too (and printed: DESIGN section 9
 states the counts)."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
-import bi_pass_model as bm
 import bi_refs_pass_model as rm
 import oracle_lib as ol
 
@@ -30,7 +28,7 @@ def reference(name, which):
     pw, ph, bd, _, orig, refs = rm.make_refs(name)
     lists = rm.SETS[which]
     num_ref, _, distinct, slot = rm.tables(lists)
-    desc = bm.descriptors(name)
+    desc = rm.descriptors(name)
     planes = [refs[p][0] for p in distinct]
     ptrs = (C.c_void_p * len(planes))(*[p[rm.BL:, rm.BL:].ctypes.data for p in planes])
     strides = np.array([p.strides[0] // 2 for p in planes], np.int64)
@@ -44,7 +42,7 @@ def reference(name, which):
     exp = np.zeros((desc.n_cus, 80), np.int64)
     for i, b in enumerate(desc.me):
         xr.xr_search_motion_multi(bd, int(b["x"]), int(b["y"]), int(b["w"]), int(b["h"]), 0,
-                                  bm.LAMBDA16, 1, pw, ph, o.ctypes.data,
+                                  rm.LAMBDA16, 1, pw, ph, o.ctypes.data,
                                   orig[0].strides[0] // 2, len(planes), ptrs,
                                   strides.ctypes.data, pocs.ctypes.data, rm.CUR_POC,
                                   nr.ctypes.data, ref_pic.ctypes.data, nb.ctypes.data,
@@ -56,12 +54,12 @@ def model(name, which):
     xo = ol.Lib("xo")
     pw, ph, bd, _, orig, refs = rm.make_refs(name)
     lists = rm.SETS[which]
-    desc = bm.descriptors(name)
+    desc = rm.descriptors(name)
     return desc, rm.search_motion(xo, bd, pw, ph, orig[0], refs, lists, rm.jobs(desc, lists),
                                   key=name)
 
 
-@pytest.mark.parametrize("which", ["A", "B", "C"])
+@pytest.mark.parametrize("which", ["A", "B", "C", "D"])
 @pytest.mark.parametrize("name", ["grid10", "grid8", "part10"])
 def test_search_motion_half_equals_reference(name, which):
     lists = rm.SETS[which]
@@ -98,7 +96,7 @@ def test_search_motion_half_equals_reference(name, which):
 def test_coverage_of_the_picture_sets():
     """What the seeds were chosen for; the GPU tests compare against this model on these
     inputs, so what is not chosen here is not tested there."""
-    for which in ("A", "B", "C"):
+    for which in ("A", "B", "C", "D"):
         total = np.zeros(3, int)
         idx_gt0 = [0, 0]
         l1_best_reused_chosen_unique = 0
@@ -121,6 +119,9 @@ def test_coverage_of_the_picture_sets():
             if which == "B":
                 assert dirs[1] == 0 and (choice["cost_l1_unique"] == rm.NONE).all()
                 assert (slots[:, :, 0] != rm.NO_JOB).all()
+            if which == "D":        # one picture per list: every direction, every slot a job
+                assert (dirs >= 4).all(), (which, name, dirs)
+                assert (slots != rm.NO_JOB).all()
             if which == "C":        # list 1's third slot is never a job
                 s1 = choice["search_list"] == 1
                 assert s1.any() and (slots[s1, 2, 0] == rm.NO_JOB).all()

@@ -1,21 +1,21 @@
-"""The frame pass of a B picture with several reference pictures per list on the GPU
-(xvcgpu_frame_pass_bi_refs, pipeline.BiRefsFramePass): the three decision kernels alone on
-hand-made inputs, the whole pass bit-exact against the model composed of the oracle's pieces
+"""The frame pass of a B picture on the GPU (xvcgpu_frame_pass_bi_refs,
+pipeline.BiRefsFramePass): the three decision kernels alone on hand-made inputs, the whole
+pass bit-exact against the model composed of the oracle's pieces
 (tests/bi_refs_pass_model.py, whose SearchMotion half tests/test_bi_refs_pass_model.py pins
-to the reference), one picture per list against xvcgpu_frame_pass_bi, the planned refinement
-against the whole-list class launches, the refusals, the C++ class and the host control."""
+to the reference) from one to three pictures per list, the one call against its parts, the
+planned refinement against the whole-list class launches, the refusals, the P pass beside it
+on one context, the C++ class and the host controls."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
-import bi_pass_model as bm
 import bi_refs_pass_model as rm
 import oracle_lib as ol
 
 pytestmark = pytest.mark.gpu
 
-BL = bm.BL
+BL = rm.BL
 ALL = 31    # FP_ENCODE | FP_DEBLOCK_V | FP_DEBLOCK_H | FP_PAD | FP_SSD
 NONE = rm.NONE
 
@@ -48,7 +48,7 @@ def expected(xo, name, which, rdoq):
     if (name, which, rdoq) not in _expected:
         pw, ph, bd, _, orig, refs = model_input(name)
         lists = rm.SETS[which]
-        desc = bm.descriptors(name, rdoq)
+        desc = rm.descriptors(name, rdoq)
         if (name, which) not in _searched:
             _searched[name, which] = rm.search_motion(xo, bd, pw, ph, orig[0], refs, lists,
                                                       rm.jobs(desc, lists), key=name)
@@ -73,12 +73,12 @@ class Scene:
             self.by_poc[poc].upload(refs[poc], BL)
         self.refs = [[self.by_poc[poc] for poc in lists[l]] for l in range(2)]
         self.fp = pipeline.BiRefsFramePass(
-            ctx, pw, ph, bd, bm.QP, rdoq=form != "residual", rdoq_packed=form == "fwd_transform",
-            partition=part, cur_poc=rm.CUR_POC, ref_pocs=lists, search_range=bm.SEARCH_RANGE,
-            side_bits=bm.SIDE_BITS)
+            ctx, pw, ph, bd, rm.QP, rdoq=form != "residual", rdoq_packed=form == "fwd_transform",
+            partition=part, cur_poc=rm.CUR_POC, ref_pocs=lists, search_range=rm.SEARCH_RANGE,
+            side_bits=rm.SIDE_BITS)
         assert self.fp.form == form
         base = self.fp.desc.me.copy()
-        base["lambda16"] = bm.LAMBDA16
+        base["lambda16"] = rm.LAMBDA16
         self.me = [[base.copy() for _ in lists[l]] for l in range(2)]
         for l in range(2):
             for r, poc in enumerate(lists[l]):
@@ -173,7 +173,7 @@ class Folds:
                 a.d_me[l][r] = self.buf(me[l][r]).ptr
                 if res[l][r] is not None:
                     a.d_results[l][r] = self.buf(res[l][r]).ptr
-        a.side_bits_uni[0], a.side_bits_uni[1], a.side_bits_bi = bm.SIDE_BITS
+        a.side_bits_uni[0], a.side_bits_uni[1], a.side_bits_bi = rm.SIDE_BITS
         self.jobs = self.poisoned(api.BI_DTYPE.itemsize * n * rmax)
         self.bi = self.poisoned(api.MERES_DTYPE.itemsize * n * rmax)
         self.slots = self.poisoned(2 * n * rmax)
@@ -343,13 +343,19 @@ def test_decision_kernels_on_hand_made_inputs(gpu):
 
 
 # ---- the whole pass ----------------------------------------------------------------------
-@pytest.mark.parametrize("which", ["A", "B", "C"])
-@pytest.mark.parametrize("name,form", [
-    ("grid10", "residual"), ("grid10", "fwd_transform"), ("grid8", "residual"),
-    ("grid8", "fwd_transform"), ("part10", "residual"), ("part10", "fwd_transform")])
+_FORMS = [("grid10", "residual"), ("grid10", "fwd_transform"), ("grid8", "residual"),
+          ("grid8", "fwd_transform"), ("part10", "residual"), ("part10", "fwd_transform")]
+
+
+@pytest.mark.parametrize("name,form,which", [
+    (name, form, which) for which in "ABCD" for name, form in _FORMS] + [
+    ("grid10", "residual_rdoq", "D")])
 def test_whole_pass_equals_model(gpu, xo, name, form, which):
     api, ctx = gpu
     exp = expected(xo, name, which, form != "residual")
+    if which == "D":        # every direction, also through MC and the filter
+        dirs = np.bincount(exp[5]["inter_dir"], minlength=3)
+        assert (dirs >= 4).all(), dirs
     s = Scene(ctx, name, which, form)
     try:
         fused = s.fp.p.fused_tail
@@ -357,7 +363,16 @@ def test_whole_pass_equals_model(gpu, xo, name, form, which):
         planned = name == "part10"
         assert all((p is not None) == (planned and s.fp.searched[l][r])
                    for l in range(2) for r, p in enumerate(s.fp.plans[l]))
-        assert_pass_equal(s.run(), exp, "one call", s)
+        if planned and which == "D":    # every search and refinement class is in the plan
+            counts = dict(zip(api.ME_PLAN_BIN_NAMES, s.fp.plans[1][0].counts.tolist()))
+            assert all(counts[k] > 0 for k in ("16x16", "8x8", "other16", "c32")) and \
+                counts["c64_team"] + counts["c64_wave"] > 0 and not counts["unsupported"], counts
+        got = s.run()
+        assert_pass_equal(got, exp, "one call", s)
+        if which == "D":        # one job per CU: its answer is the record's refined vector
+            choice, bi = got[0][4], got[0][5]
+            assert np.array_equal(np.stack([bi[:, 0]["mv_x"], bi[:, 0]["mv_y"]], 1),
+                                  choice["bi_mv"][:, 0])
         if planned:
             # the same blocks without plans: sized searches, whole-list class launches (the
             # 16 launch answers the larger classes with the unsupported record first)
@@ -401,47 +416,6 @@ def test_one_call_equals_its_parts(gpu):
         finally:
             a.destroy()
             b.destroy()
-
-
-def test_one_picture_per_list_equals_frame_pass_bi(gpu):
-    """Set D through the new entry point against xvcgpu_frame_pass_bi on the same pictures
-    and jobs: vectors, costs, pictures and CU records."""
-    from xvc_amd import pipeline
-    api, ctx = gpu
-    for name, form in (("grid10", "fwd_transform"), ("part10", "residual")):
-        s = Scene(ctx, name, "D", form)
-        pw, ph, bd = s.size
-        part = model_input(name)[3]
-        old = pipeline.BiFramePass(
-            ctx, pw, ph, bd, bm.QP, rdoq=form != "residual", rdoq_packed=form == "fwd_transform",
-            partition=part, ref_pocs=(4, 12), search_range=bm.SEARCH_RANGE,
-            side_bits=bm.SIDE_BITS)
-        Rec = ctx.picture(pw, ph, bd)
-        try:
-            old.set_jobs(s.me[0][0], s.me[1][0])
-            old.run(s.O, s.refs[0][0], s.refs[1][0], Rec)
-            ctx.sync()
-            (o_res, o_nnz, o_cus, o_ssd, o_choice), o_rec = old.results(), Rec.download(BL)
-            (res, nnz, cus, ssd, choice, bi, slots), rec = s.run()
-            for l in range(2):
-                assert not len(differing(res[l][0], o_res[l]))
-            for f in ("inter_dir", "search_list", "cost_bi", "cost", "mv"):
-                assert np.array_equal(choice[f], o_choice[f]), f
-            assert np.array_equal(choice["cost_list"], o_choice["cost_uni"])
-            assert np.array_equal(choice["cost_l1_unique"], o_choice["cost_uni"][:, 1])
-            assert np.array_equal(choice["bi_mv"][:, 0], o_choice["bi_mv"])
-            assert np.array_equal(bi[:, 0]["mv_x"], o_choice["bi_mv"][:, 0])
-            used = [np.isin(choice["inter_dir"], (2, l)) for l in range(2)]
-            for l in range(2):
-                assert np.array_equal(choice["ref_idx"][:, l], np.where(used[l], 0, -1))
-            assert len(set(choice["inter_dir"].tolist())) == 3
-            assert np.array_equal(nnz, o_nnz) and not len(differing(cus, o_cus))
-            assert all(np.array_equal(x, y) for x, y in zip(rec, o_rec))
-            assert ssd.tolist() == o_ssd.tolist()
-        finally:
-            old.destroy()
-            Rec.destroy()
-            s.destroy()
 
 
 @pytest.mark.parametrize("lists", [((4, 0), (12,)), rm.SETS["C"]], ids=["rmax2", "rmax3"])
@@ -602,6 +576,81 @@ def test_refusals_enqueue_nothing(gpu):
         p.destroy()
 
 
+def test_refusals_enqueue_nothing_one_picture_per_list(gpu):
+    """Set D, one plan per list: the forms that predict from one list inside their kernel
+    (the P pass runs both on this grid), a missing list-1 picture, a plan for one list only
+    and the lists' plans swapped are refused before anything is written."""
+    api, ctx = gpu
+    g, p = Scene(ctx, "grid10", "D"), Scene(ctx, "part10", "D")
+    try:
+        for s, name in ((g, "grid10"), (p, "part10")):
+            s.Rec.upload([np.full_like(q, 0x0123) for q in model_input(name)[4]], BL)
+        bufs = _poison(ctx, g.fp)
+
+        def form(v):
+            def change(a):
+                a.p.form = v
+            return change
+
+        def no_ref1(a):
+            a.refs[1] = None
+        _refused(api, ctx, g, bufs, form(api.FP_FORM_NAMES.index("recon_from_me")), "form")
+        _refused(api, ctx, g, bufs, form(api.FP_FORM_NAMES.index("fwd_from_me")), "form")
+        _refused(api, ctx, g, bufs, no_ref1, "refs")
+        bufs = _poison(ctx, p.fp)
+        fp = p.fp
+
+        def handles(l0, l1):
+            h = fp.plan_handles(False)
+            h[0][0] = l0.h if l0 is not None else None
+            h[1][0] = l1.h if l1 is not None else None
+            return h
+        p0, p1 = fp.plans[0][0], fp.plans[1][0]
+        same = lambda a: None       # noqa: E731
+        _refused(api, ctx, p, bufs, same, "plans for every searched picture", handles(p0, None))
+        _refused(api, ctx, p, bufs, same, "plans for every searched picture", handles(None, p1))
+        _refused(api, ctx, p, bufs, same, "not made from its d_me", handles(p1, p0))
+        # and the same blocks run when nothing is wrong with them
+        assert int(p.run()[0][4]["inter_dir"].max()) == 2
+    finally:
+        g.destroy()
+        p.destroy()
+
+
+def test_p_pass_untouched_beside_the_b_pass(gpu):
+    """A FramePass on list 0 of the same input answers the same before and after a
+    BiRefsFramePass ran on its context: no scratch or context state leaks between them."""
+    from xvc_amd import pipeline
+    api, ctx = gpu
+    s = Scene(ctx, "grid10", "D", "fwd_transform")
+    pw, ph, bd = s.size
+    P = ctx.picture(pw, ph, bd)
+    passes = [pipeline.FramePass(ctx, pw, ph, bd, rm.QP),
+              pipeline.FramePass(ctx, pw, ph, bd, rm.QP, rdoq=True)]
+    try:
+        def run_p():
+            out = []
+            for fp in passes:
+                fp.run(s.O, s.refs[0][0], P)
+                ctx.sync()
+                out.append((fp.results(), P.download(BL)))
+            return out
+        before = run_p()
+        b1 = s.run()
+        after = run_p()
+        for (ra, pa), (rb, pb) in zip(before, after):
+            assert all(not len(differing(x, y)) for x, y in zip(ra, rb))
+            assert all(np.array_equal(x, y) for x, y in zip(pa, pb))
+        assert before[0][0][0]["subpel_dist"].any()
+        # ... and the B pass the same after the P passes
+        assert_pass_equal(s.run(), as_expected(*b1), "B pass again")
+    finally:
+        for fp in passes:
+            fp.destroy()
+        P.destroy()
+        s.destroy()
+
+
 # ---- the host layers ---------------------------------------------------------------------
 def test_host_class_equals_python_pass(gpu):
     """xvc_gpu::FramePassBiRefs (through xvc_host_frame_pass_bi_refs) on set A equals
@@ -629,7 +678,7 @@ def test_host_class_equals_python_pass(gpu):
         h_cus = np.zeros(n, api.CU_DTYPE)
         h_ssd = np.zeros(2, np.uint64)
         assert L.xvc_host_frame_pass_bi_refs(
-            ctx.h, pw, ph, bd, bm.QP, rm.CUR_POC, num_ref.ctypes.data, pocs.ctypes.data,
+            ctx.h, pw, ph, bd, rm.QP, rm.CUR_POC, num_ref.ctypes.data, pocs.ctypes.data,
             s.O.h_pic, pics, Rec.h_pic, blocks.ctypes.data, n, h_choice.ctypes.data,
             h_cus.ctypes.data, h_ssd.ctypes.data) == 0
         assert not len(differing(h_choice, choice)) and not len(differing(h_cus, cus))
@@ -692,6 +741,54 @@ def test_search_motion_half_equals_host_control(gpu):
                 else:
                     assert int(c["ref_idx"][l]) == -1 and not c["mv"][l].any()
             assert got == want, (i, got, want)
+        assert len(set(choice["inter_dir"].tolist())) >= 2
+    finally:
+        s.destroy()
+
+
+def test_folds_with_predictors_equal_host_control(gpu):
+    """One picture per list (set D), random per-list predictors and full-pel CUs: the choice
+    records against xvc_host_search_motion_batch (pinned to the reference by
+    test_gpu_host_inter_search.py) on the same jobs with AMVP pairs {mvp, mvp}."""
+    from xvc_amd import decoder
+    api, ctx = gpu
+    L = decoder.load_host_library()
+    L.xvc_host_search_motion_batch.argtypes = [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 3 + \
+        [C.c_int, C.c_void_p]
+    s = Scene(ctx, "grid10", "D")
+    try:
+        n = s.fp.desc.n_cus
+        rng = np.random.default_rng(31)
+        blocks = np.zeros((2, n), api.ME_DTYPE)
+        fullpel = (rng.integers(0, 6, n) == 0).astype(np.uint8)
+        for l in range(2):
+            blocks[l] = s.me[l][0]
+            blocks[l]["mvp_x"] = rng.integers(-160, 161, n)
+            blocks[l]["mvp_y"] = rng.integers(-160, 161, n)
+            blocks[l]["fullpel_mv"] = fullpel
+        assert fullpel.any() and not fullpel.all()
+        s.fp.set_jobs([[blocks[0]], [blocks[1]]])
+        (_, _, _, _, choice, _, _), _ = s.run()
+        mvp = np.zeros((2, n, 4), np.int32)
+        for l in range(2):
+            mvp[l, :, 0] = mvp[l, :, 2] = blocks[l]["mvp_x"]
+            mvp[l, :, 1] = mvp[l, :, 3] = blocks[l]["mvp_y"]
+        side_uni = np.zeros((2, n), np.uint32)
+        side_uni[0], side_uni[1] = rm.SIDE_BITS[0], rm.SIDE_BITS[1]
+        side_bi = np.full(n, rm.SIDE_BITS[2], np.uint32)
+        out = np.zeros((n, 18), np.int64)
+        bl = np.ascontiguousarray(blocks)
+        assert L.xvc_host_search_motion_batch(
+            ctx.h, s.O.h_pic, s.refs[0][0].h_pic, s.refs[1][0].h_pic, bl.ctypes.data, n,
+            mvp.ctypes.data, side_uni.ctypes.data, side_bi.ctypes.data, 1, out.ctypes.data) == 0
+        for i in range(n):
+            q, c = [int(v) for v in out[i]], choice[i]
+            d = q[0]
+            want_mv = [[q[1 + 2 * l], q[2 + 2 * l]] if d in (2, l) else [0, 0] for l in range(2)]
+            got = (int(c["inter_dir"]), c["mv"].tolist(), int(c["cost"]), c["cost_list"].tolist(),
+                   int(c["cost_bi"]))
+            assert got == (d, want_mv, q[7], [q[8], q[12]], q[16]), (i, got, q)
+            assert q[5] == q[6] == 0 and q[17] == 1     # predictor index 0, one step
         assert len(set(choice["inter_dir"].tolist())) >= 2
     finally:
         s.destroy()

@@ -1,20 +1,18 @@
 #!/usr/bin/env python3
-"""Times the frame pass of a B picture with several reference pictures per list
-(pipeline.BiRefsFramePass, xvcgpu_frame_pass_bi_refs) at 1080p, 10 bit, QP 32, packed RDOQ -
-on the 16-sample grid and on one real partition (`c1` picture 1) - for the picture sets
-D (L0 {4}, L1 {12}), B (L0 {4, 12}, L1 {12, 4}) and A (L0 {4, 0}, L1 {12, 16}) around POC 8,
-per pass and per launch (profiles/bi_refs_frame_pass_time.txt is a run of it).
+"""Times the frame pass of a B picture (pipeline.BiRefsFramePass,
+xvcgpu_frame_pass_bi_refs) at 1080p, 10 bit, QP 32, packed RDOQ - on the 16-sample grid and
+on one real partition (`c1` picture 1) - for the picture sets D (L0 {4}, L1 {12}), B (L0
+{4, 12}, L1 {12, 4}) and A (L0 {4, 0}, L1 {12, 16}) around POC 8, per pass and per launch.
+profiles/bi_refs_frame_pass_time.txt is a run of an earlier version, which also timed the
+retired one-reference pass beside set D: give --out another name to keep that record.
 
     python tools/time_bi_refs_pass.py [--out profiles/bi_refs_frame_pass_time.txt]
                                       [--repeats 30] [--warmup 5] [--inner 8]
 
-Two comparisons, both in this process with the passes taking turns round by round:
-set D through the new entry point against xvcgpu_frame_pass_bi on the same pictures (the
-new pass runs its refinement as one launch of n jobs instead of two of n), and on the
-partition the planned refinement against the whole-list launches per class.  Device events
-around `inner` back-to-back calls, divided by inner; `warmup` untimed rounds, then `repeats`
-timed ones: median and inter-quartile range, in microseconds.  A launch is timed alone,
-after the launches before it ran once untimed.  There is no target."""
+On the partition the planned refinement is timed against the whole-list launches per class.
+Device events around `inner` back-to-back calls, divided by inner; `warmup` untimed rounds,
+then `repeats` timed ones: median and inter-quartile range, in microseconds.  A launch is
+timed alone, after the launches before it ran once untimed.  There is no target."""
 import argparse
 import os
 import sys
@@ -24,12 +22,46 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-
-from time_bi_pass import per_launch, timed  # noqa: E402
 
 CUR_POC = 8
 SETS = (("D", ((4,), (12,))), ("B", ((4, 12), (12, 4))), ("A", ((4, 0), (12, 16))))
+
+
+def stats(us):
+    q1, med, q3 = np.percentile(np.asarray(us, float), [25, 50, 75])
+    return float(med), float(q3 - q1)
+
+
+def timed_round(ctx, fn, inner):
+    ctx.timer_begin()
+    for _ in range(inner):
+        fn()
+    return ctx.timer_end() * 1000.0 / inner
+
+
+def timed(ctx, fns, a):
+    """Median and IQR per callable of fns, the callables taking turns round by round."""
+    for _ in range(a.warmup):
+        for fn in fns:
+            for _ in range(a.inner):
+                fn()
+    ctx.sync()
+    out = [[] for _ in fns]
+    for _ in range(a.repeats):
+        for k, fn in enumerate(fns):
+            out[k].append(timed_round(ctx, fn, a.inner))
+    return [stats(o) for o in out]
+
+
+def per_launch(ctx, steps_of, a):
+    """(name, median, iqr) per launch of steps_of() (a fresh list of (name, callable))."""
+    rows = []
+    for k, (name, _) in enumerate(steps_of()):
+        for _, fn in steps_of()[:k]:
+            fn()
+        (med, iqr), = timed(ctx, [steps_of()[k][1]], a)
+        rows.append((name, med, iqr))
+    return rows
 
 
 def main():
@@ -53,8 +85,7 @@ def main():
                     for c, p in enumerate(clip.frame(k))], 128)
         if poc != CUR_POC:
             by_poc[poc] = pic
-    lines = ["B frame pass with several reference pictures per list, %dx%d, %d bit, QP %d, "
-             "packed RDOQ" % (w, h, bd, qp),
+    lines = ["B frame pass, %dx%d, %d bit, QP %d, packed RDOQ" % (w, h, bd, qp),
              "device events, inner %d, warm-up %d, repeats %d: median (IQR) in us"
              % (a.inner, a.warmup, a.repeats), ""]
     for name, parts in (("grid 16x16", None), ("partition c1 picture 1", luma_partition("c1", 1))):
@@ -62,12 +93,7 @@ def main():
             refs = [[by_poc[p] for p in lists[l]] for l in range(2)]
             fr = pipeline.BiRefsFramePass(ctx, w, h, bd, qp, rdoq=True, partition=parts,
                                           cur_poc=CUR_POC, ref_pocs=lists)
-            fns, old = [lambda: fr.run(O, refs, Rec)], None
-            if which == "D":    # the one-picture pass on the same pictures, turn by turn
-                old = pipeline.BiFramePass(ctx, w, h, bd, qp, rdoq=True, partition=parts,
-                                           ref_pocs=(4, 12))
-                fns.append(lambda: old.run(O, by_poc[4], by_poc[12], Rec))
-            meds = timed(ctx, fns, a)
+            meds = timed(ctx, [lambda: fr.run(O, refs, Rec)], a)
             ctx.sync()
             choice = fr.results()[4]
             dirs = np.bincount(choice["inter_dir"], minlength=3)
@@ -78,12 +104,6 @@ def main():
                          (choice["ref_idx"][:, 1] > 0).sum()),
                       "  xvcgpu_frame_pass_bi_refs, one call  form %-14s fused tail %-5s "
                       "%9.1f (%.1f)" % (fr.form, bool(fr.p.fused_tail), meds[0][0], meds[0][1])]
-            if old is not None:
-                lines += ["  xvcgpu_frame_pass_bi, one call       form %-14s fused tail %-5s "
-                          "%9.1f (%.1f)" % (old.form, bool(old.p.fused_tail), meds[1][0],
-                                            meds[1][1]),
-                          "  new / old %.3f (difference %.1f us, the old pass's IQR %.1f us)"
-                          % (meds[0][0] / meds[1][0], meds[0][0] - meds[1][0], meds[1][1])]
             rows = per_launch(ctx, lambda: fr.kernel_steps(O, refs, Rec), a)
             lines.append("  per launch (sum %.1f)" % sum(r[1] for r in rows))
             lines += ["    %-18s %9.1f (%.1f)" % r for r in rows]
@@ -94,12 +114,6 @@ def main():
                 lines.append("  the refinement as whole-list launches per class (sum %.1f)"
                              % sum(r[1] for r in rows))
                 lines += ["    %-18s %9.1f (%.1f)" % r for r in rows]
-            if old is not None:
-                rows = per_launch(ctx, lambda: old.kernel_steps(O, by_poc[4], by_poc[12], Rec), a)
-                lines.append("  xvcgpu_frame_pass_bi per launch (sum %.1f)"
-                             % sum(r[1] for r in rows))
-                lines += ["    %-18s %9.1f (%.1f)" % r for r in rows]
-                old.destroy()
             lines.append("")
             fr.destroy()
     for p in [O, Rec] + list(by_poc.values()):

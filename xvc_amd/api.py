@@ -151,21 +151,6 @@ class FramePassArgs(C.Structure):
                 ("form", C.c_int32)]
 
 
-class FramePassBiArgs(C.Structure):
-    """xvcgpu_frame_pass_bi_args (include/xvcgpu_types.h)"""
-    _fields_ = [("p", FramePassArgs), ("ref1", C.c_void_p), ("d_me_l1", C.c_void_p),
-                ("d_results_l1", C.c_void_p), ("ref_poc_l1", C.c_int32),
-                ("side_bits_uni", C.c_uint32 * 2), ("side_bits_bi", C.c_uint32),
-                ("d_bi_jobs", C.c_void_p * 2), ("d_bi_results", C.c_void_p * 2),
-                ("d_choice", C.c_void_p), ("d_inter", C.c_void_p)]
-
-
-# xvcgpu_fp_bi_result: what SearchMotion ends with for one CU of a B picture
-FP_BI_RESULT_DTYPE = np.dtype([("inter_dir", "<i4"), ("search_list", "<i4"),
-                               ("cost_uni", "<u4", (2,)), ("cost_bi", "<u4"), ("cost", "<u4"),
-                               ("mv", "<i4", (2, 2)), ("bi_mv", "<i4", (2,))])
-assert FP_BI_RESULT_DTYPE.itemsize == 48
-
 CS_MAX_REFS = 3           # XVC_CS_MAX_REFS: pictures per list
 FP_BI_MAX_REF_PICS = 6    # XVC_FP_BI_MAX_REF_PICS: distinct reference pictures of a call
 FP_BI_NO_JOB = 255        # XVC_FP_BI_NO_JOB
@@ -184,8 +169,7 @@ class FramePassBiRefsArgs(C.Structure):
                 ("d_bi_slots", C.c_void_p), ("d_choice", C.c_void_p), ("d_inter", C.c_void_p)]
 
 
-# xvcgpu_fp_bi_refs_result: what SearchMotion ends with for one CU of a B picture whose lists
-# name several pictures
+# xvcgpu_fp_bi_refs_result: what SearchMotion ends with for one CU of a B picture
 FP_BI_REFS_RESULT_DTYPE = np.dtype([
     ("inter_dir", "<i4"), ("search_list", "<i4"), ("ref_idx", "<i4", (2,)),
     ("mv", "<i4", (2, 2)), ("cost_list", "<u4", (2,)), ("cost_l1_unique", "<u4"),
@@ -248,8 +232,6 @@ SYMBOLS = [
     "xvcgpu_fwd_from_me", "xvcgpu_output_bytes", "xvcgpu_picture_convert_to",
     "xvcgpu_me_plan_create", "xvcgpu_me_plan_counts", "xvcgpu_me_plan_destroy",
     "xvcgpu_me_search_planned", "xvcgpu_frame_pass_planned",
-    "xvcgpu_fp_bi_uni_fold", "xvcgpu_fp_bi_choice", "xvcgpu_cu_info_from_choice",
-    "xvcgpu_frame_pass_bi",
     "xvcgpu_fp_bi_refs_uni_fold", "xvcgpu_fp_bi_refs_choice", "xvcgpu_cu_info_from_choice_refs",
     "xvcgpu_bipred_search_refs_planned", "xvcgpu_frame_pass_bi_refs",
 ]
@@ -457,12 +439,6 @@ def load_library(allow_missing=()):
         "xvcgpu_me_plan_counts": [_vp, C.POINTER(C.c_int32)],
         "xvcgpu_me_search_planned": [_vp, _vp, _vp, C.c_int, _vp, _vp],
         "xvcgpu_frame_pass_planned": [_vp, C.POINTER(FramePassArgs), _vp, C.c_int],
-        "xvcgpu_fp_bi_uni_fold": [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_uint32, C.c_uint32, _vp,
-                                  _vp, _vp],
-        "xvcgpu_fp_bi_choice": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_uint32, _vp, _vp],
-        "xvcgpu_cu_info_from_choice": [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int,
-                                       C.c_int, C.c_int, _vp],
-        "xvcgpu_frame_pass_bi": [_vp, C.POINTER(FramePassBiArgs), _vp, _vp, C.c_int],
         "xvcgpu_fp_bi_refs_uni_fold": [_vp, C.POINTER(FramePassBiRefsArgs)],
         "xvcgpu_fp_bi_refs_choice": [_vp, C.POINTER(FramePassBiRefsArgs)],
         "xvcgpu_cu_info_from_choice_refs": [_vp, C.POINTER(FramePassBiRefsArgs)],

@@ -7,11 +7,12 @@
 // Host twin: xvc_gpu::InterSearch::SearchMotionMultiBatch (host/xvc_gpu_ops.h), which reads
 // every search result back to decide the next step.
 //
-// The folds: one thread per CU, 256-thread workgroups, plain loads and stores, as k_fp_bi.h;
-// a job's single mvp stands for both AMVP entries of its (list, picture).  A list-1 picture
-// that list 0 names too (same_poc_in_l0 >= 0) is not searched: SearchRefIdx takes list 0's
-// distortion and vector (:536-542) and prices them with list 1's own predictor and index;
-// the final choice compares against the best of the pictures only list 1 names
+// The folds: one thread per CU, 256-thread workgroups, plain loads and stores.  A job's
+// single mvp stands for both AMVP entries of its (list, picture): the start index and
+// EvalFinalMvpIdx's answer are both 0 and GetMvpBits(0, 2) = 1 is the constant in the prices.
+// A list-1 picture that list 0 names too (same_poc_in_l0 >= 0) is not searched: SearchRefIdx
+// takes list 0's distortion and vector (:536-542) and prices them with list 1's own predictor
+// and index; the final choice compares against the best of the pictures only list 1 names
 // (cost_l1_unique, :247-257).
 //
 // The refinement jobs lie by CU: job [i * Rmax + k] is CU i's step into picture k of its
@@ -37,9 +38,20 @@
 #ifndef XVCGPU_K_FP_BI_REFS_H_
 #define XVCGPU_K_FP_BI_REFS_H_
 
+#include "dev_common.h"
 #include "k_bipred.h"
-#include "k_fp_bi.h"
 #include "k_me_plan.h"
+#include "xvcgpu_internal.h"
+
+// dist + ((bits * lambda) >> 16) (SearchRefIdx :560-566, SearchBiIterative :418-424)
+__device__ __forceinline__ uint32_t fp_bi_cost(uint32_t dist, uint32_t bits, uint32_t lambda16) {
+  return dist + (uint32_t)(((uint64_t)bits * lambda16) >> 16);
+}
+
+// GetMvdBits of a list's vector against the job's predictor
+__device__ __forceinline__ uint32_t fp_bi_mvd_bits(const xvcgpu_me_block &b, int mx, int my) {
+  return d_mvd_bits(b.mvp_x, b.mvp_y, mx, my, (b.fullpel_mv & XVC_ME_FULLPEL_MV) ? 2 : 0);
+}
 
 // The pass's tables as the kernels read them.  res[1][r] of a re-used picture points at
 // list 0's results of its twin (the host resolves it: the kernels read one array per entry).
@@ -283,9 +295,10 @@ struct FpBiRefsPocs {
   int poc[2][XVC_CS_MAX_REFS];
 };
 
-// cu_info_from_choice_kernel (k_fp_bi.h) with the chosen pictures: ref_idx0 the chosen list-0
-// index, or -1; ref_poc[l] the chosen picture's POC, or -1; the vectors as there.
-// grid: ceil(n / 256); block: 256.
+// cu_info_from_me_kernel (k_misc.h) for two lists: the deblocking records as the decoder
+// fills them for a B picture (host/xvc_picture_decoder.cc:220-230) - ref_idx0 the chosen
+// list-0 index, or -1 where list 0 is unused; ref_poc[l] the chosen picture's POC, or -1; all
+// four corners the list's vector, an unused list zero.  grid: ceil(n / 256); block: 256.
 __global__ void __launch_bounds__(256)
 cu_info_from_choice_refs_kernel(const xvcgpu_me_block *blocks,
                                 const xvcgpu_fp_bi_refs_result *choice, const int32_t *nnz,

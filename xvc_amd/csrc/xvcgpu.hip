@@ -31,7 +31,6 @@
 #include "k_intra_waves.h"
 #include "k_cu_state.h"
 #include "k_cs_engine.h"
-#include "k_fp_bi.h"
 #include "k_fp_bi_refs.h"
 #include "xvcgpu_internal.h"
 
@@ -1345,61 +1344,6 @@ xvcgpu_status xvcgpu_cu_info_from_me(xvcgpu_ctx *ctx,
                      ctx->stream, d_blocks, d_results, d_nnz, d_luma_tx_index, n,
                      qp_y, qp_c, ref_poc, d_cus);
   CHECK_LAUNCH(ctx, "cu_info_from_me");
-  return XVCGPU_OK;
-}
-
-/* ---- SearchMotion's decisions for a B picture (k_fp_bi.h) ---- */
-xvcgpu_status xvcgpu_fp_bi_uni_fold(xvcgpu_ctx *ctx, const xvcgpu_me_block *d_me_l0,
-                                    const xvcgpu_me_block *d_me_l1,
-                                    const xvcgpu_me_result *d_results_l0,
-                                    const xvcgpu_me_result *d_results_l1, int n,
-                                    uint32_t side_bits_l0, uint32_t side_bits_l1,
-                                    xvcgpu_bi_block *d_bi_jobs_l0, xvcgpu_bi_block *d_bi_jobs_l1,
-                                    xvcgpu_fp_bi_result *d_choice) {
-  if (!ctx || n < 0 ||
-      (n && (!d_me_l0 || !d_me_l1 || !d_results_l0 || !d_results_l1 || !d_bi_jobs_l0 ||
-             !d_bi_jobs_l1 || !d_choice)))
-    return XVCGPU_INVALID_ARGUMENT;
-  if (n == 0) return XVCGPU_OK;
-  hipLaunchKernelGGL(fp_bi_uni_fold_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream,
-                     d_me_l0, d_me_l1, d_results_l0, d_results_l1, n, side_bits_l0, side_bits_l1,
-                     d_bi_jobs_l0, d_bi_jobs_l1, d_choice);
-  CHECK_LAUNCH(ctx, "fp_bi_uni_fold");
-  return XVCGPU_OK;
-}
-
-xvcgpu_status xvcgpu_fp_bi_choice(xvcgpu_ctx *ctx, const xvcgpu_me_block *d_me_l0,
-                                  const xvcgpu_me_block *d_me_l1,
-                                  const xvcgpu_me_result *d_results_l0,
-                                  const xvcgpu_me_result *d_results_l1,
-                                  const xvcgpu_me_result *d_bi_results_l0,
-                                  const xvcgpu_me_result *d_bi_results_l1, int n,
-                                  uint32_t side_bits_bi, xvcgpu_fp_bi_result *d_choice,
-                                  xvcgpu_inter_block *d_inter) {
-  if (!ctx || n < 0 ||
-      (n && (!d_me_l0 || !d_me_l1 || !d_results_l0 || !d_results_l1 || !d_bi_results_l0 ||
-             !d_bi_results_l1 || !d_choice || !d_inter)))
-    return XVCGPU_INVALID_ARGUMENT;
-  if (n == 0) return XVCGPU_OK;
-  hipLaunchKernelGGL(fp_bi_choice_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream,
-                     d_me_l0, d_me_l1, d_results_l0, d_results_l1, d_bi_results_l0,
-                     d_bi_results_l1, n, side_bits_bi, d_choice, d_inter);
-  CHECK_LAUNCH(ctx, "fp_bi_choice");
-  return XVCGPU_OK;
-}
-
-xvcgpu_status xvcgpu_cu_info_from_choice(xvcgpu_ctx *ctx, const xvcgpu_me_block *d_blocks,
-                                         const xvcgpu_fp_bi_result *d_choice,
-                                         const int32_t *d_nnz, const int32_t *d_luma_tx_index,
-                                         int n, int qp_y, int qp_c, int ref_poc_l0,
-                                         int ref_poc_l1, xvcgpu_cu_info *d_cus) {
-  if (!ctx || n < 0 || (n && (!d_blocks || !d_choice || !d_nnz || !d_cus)))
-    return XVCGPU_INVALID_ARGUMENT;
-  if (n == 0) return XVCGPU_OK;
-  hipLaunchKernelGGL(cu_info_from_choice_kernel, dim3((n + 255) / 256), dim3(256), 0,
-                     ctx->stream, d_blocks, d_choice, d_nnz, d_luma_tx_index, n, qp_y, qp_c,
-                     ref_poc_l0, ref_poc_l1, d_cus);
-  CHECK_LAUNCH(ctx, "cu_info_from_choice");
   return XVCGPU_OK;
 }
 
@@ -2727,78 +2671,6 @@ xvcgpu_status xvcgpu_frame_pass_planned(xvcgpu_ctx *ctx, const xvcgpu_frame_pass
   return frame_pass_impl(ctx, a, phases, plan);
 }
 
-xvcgpu_status xvcgpu_frame_pass_bi(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_bi_args *b,
-                                   const xvcgpu_me_plan *plan_l0, const xvcgpu_me_plan *plan_l1,
-                                   int phases) {
-  if (!ctx || !b || !b->p.rec) return XVCGPU_INVALID_ARGUMENT;
-  const xvcgpu_frame_pass_args *a = &b->p;
-  const int n = a->n_cus;
-#define FPB_NEED(cond, what) \
-  if (!(cond)) return fail(ctx, XVCGPU_INVALID_ARGUMENT, "frame_pass_bi: " what)
-  FPB_NEED(n == a->n_cus_total && a->db_y_begin == 0 && a->db_y_end >= a->rec->h &&
-               a->dbh_y_end >= a->rec->h && a->ssd_y_begin == 0 && a->ssd_y_end >= a->rec->h,
-           "whole pictures only (no row shard)");
-  if ((phases & XVC_FP_ENCODE) && n > 0) {
-    FPB_NEED(a->form == XVC_FP_FORM_FWD_TRANSFORM || a->form == XVC_FP_FORM_RESIDUAL ||
-                 a->form == XVC_FP_FORM_RESIDUAL_RDOQ,
-             "the form must be one with a prediction picture: FWD_TRANSFORM, RESIDUAL or "
-             "RESIDUAL_RDOQ");
-    FPB_NEED(a->orig && b->ref1 && b->d_me_l1 && b->d_results_l1,
-             "orig, ref1, d_me_l1 and d_results_l1");
-    FPB_NEED(b->ref1->w == a->orig->w && b->ref1->h == a->orig->h && b->ref1->bd == a->orig->bd,
-             "ref1 is not a picture of orig's size");
-    FPB_NEED(b->d_bi_jobs[0] && b->d_bi_jobs[1] && b->d_bi_results[0] && b->d_bi_results[1] &&
-                 b->d_choice && b->d_inter,
-             "d_bi_jobs, d_bi_results, d_choice and d_inter");
-    FPB_NEED(!plan_l0 == !plan_l1, "both plans or neither");
-    if (plan_l0) {
-      FPB_NEED(plan_l0->n == n && plan_l0->d_blocks == a->d_me,
-               "plan_l0 was not made from p.d_me");
-      FPB_NEED(plan_l1->n == n && plan_l1->d_blocks == b->d_me_l1,
-               "plan_l1 was not made from d_me_l1");
-      FPB_NEED(plan_l0->max_launched == me_class_of(a->max_block_size) &&
-                   plan_l1->max_launched == plan_l0->max_launched,
-               "a plan was made for another max_block_size class");
-    }
-  }
-#undef FPB_NEED
-  FramePassForm r;
-  xvcgpu_status st = frame_pass_resolve(ctx, a, phases, plan_l0, &r);
-  if (st != XVCGPU_OK) return st;
-  if (plan_l1 && plan_l1->n_small() > 0) r.fused_tail = false;
-  xvcgpu_picture *const rec = r.fused_tail ? a->scratch_rec : a->rec;
-  if (r.form) {
-    st = fp_search(ctx, a, a->ref, a->d_me, a->d_results, plan_l0);
-    if (st == XVCGPU_OK) st = fp_search(ctx, a, b->ref1, b->d_me_l1, b->d_results_l1, plan_l1);
-    if (st == XVCGPU_OK)
-      st = xvcgpu_fp_bi_uni_fold(ctx, a->d_me, b->d_me_l1, a->d_results, b->d_results_l1, n,
-                                 b->side_bits_uni[0], b->side_bits_uni[1], b->d_bi_jobs[0],
-                                 b->d_bi_jobs[1], b->d_choice);
-    // SearchBiIterative's one step, the CUs that refine list 0, then those that refine list 1
-    if (st == XVCGPU_OK)
-      st = xvcgpu_bipred_search(ctx, a->orig, b->ref1, a->ref, b->d_bi_jobs[0], n,
-                                b->d_bi_results[0], a->max_block_size);
-    if (st == XVCGPU_OK)
-      st = xvcgpu_bipred_search(ctx, a->orig, a->ref, b->ref1, b->d_bi_jobs[1], n,
-                                b->d_bi_results[1], a->max_block_size);
-    if (st == XVCGPU_OK)
-      st = xvcgpu_fp_bi_choice(ctx, a->d_me, b->d_me_l1, a->d_results, b->d_results_l1,
-                               b->d_bi_results[0], b->d_bi_results[1], n, b->side_bits_bi,
-                               b->d_choice, b->d_inter);
-    if (st == XVCGPU_OK) {
-      // (the prediction reads its `rec` for LIC jobs only: there are none)
-      const xvcgpu_picture *refs[2] = {a->ref, b->ref1};
-      st = xvcgpu_inter_pred_batch(ctx, refs, 2, a->rec, a->pred, b->d_inter, 3 * n);
-    }
-    if (st == XVCGPU_OK) st = fp_residual(ctx, a, rec, r.form);
-    if (st == XVCGPU_OK)
-      st = xvcgpu_cu_info_from_choice(ctx, a->d_me, b->d_choice, a->d_nnz, a->d_luma_tx_index, n,
-                                      a->qp_y, a->qp_c, a->ref_poc, b->ref_poc_l1, a->d_cus_own);
-  }
-  if (st == XVCGPU_OK) st = fp_tail(ctx, a, phases, r.fused_tail, 1);
-  return st;
-}
-
 /* ---- several pictures per call: every kernel launched once for all of them ---- */
 // Picture by picture.  The batched form runs everything on ctxs[0]'s stream; so that a
 // caller sees ONE ordering rule either way, a picture whose context has another stream is
@@ -3157,7 +3029,7 @@ xvcgpu_status xvcgpu_bipred_search_refs_planned(xvcgpu_ctx *ctx, const xvcgpu_pi
   return XVCGPU_OK;
 }
 
-/* ---- the frame pass of a B picture, several reference pictures per list (k_fp_bi_refs.h) ---- */
+/* ---- the frame pass of a B picture (k_fp_bi_refs.h) ---- */
 // The tables of the args block checked (*what names the field of a refusal) and turned into
 // the kernels' form
 static bool fp_bi_refs_tables(const xvcgpu_frame_pass_bi_refs_args *b, FpBiRefsDev *t,

@@ -271,198 +271,18 @@ class FramePass {
   std::unique_ptr<DeviceArray<uint64_t>> d_ssd_;
 };
 
-// The frame pass of a B picture (the C++ twin of pipeline.BiFramePass): for every CU
-// InterSearch::SearchMotion over two lists with one reference picture each
-// (inter_search.cc:198-259: both searches, the SearchBiIterative step, :392-433, the choice,
-// :247-257), CompressAndEvalCbf of the chosen prediction, DeblockPicture of a B picture,
-// PadBorder and the PSNR walk - one C call (xvcgpu_frame_pass_bi), nothing read back in
-// between.  QuantFast (form RESIDUAL); closed-form side bits (fast_inter_pred_bits: 3, 3, 5);
-// the CUs are the cu x cu grid or, with a partition, a caller's CUs of any mix of sizes
-// (searched through one plan per list).
-class FramePassBi {
- public:
-  FramePassBi(const Context &ctx, int width, int height, int bitdepth, int qp, int cu = 16,
-              int search_range = 96)
-      : ctx_(ctx), h_(height), bd_(bitdepth), qp_(qp), qp_c_(ChromaQp(qp)), plan_() {
-    std::vector<CuRect> parts;
-    for (int y = 0; y < height; y += cu)
-      for (int x = 0; x < width; x += cu) {
-        const CuRect p = {x, y, width - x < cu ? width - x : cu, height - y < cu ? height - y : cu};
-        parts.push_back(p);
-      }
-    Build(width, height, parts, search_range, cu, false);
-  }
-  FramePassBi(const Context &ctx, int width, int height, int bitdepth, int qp,
-              const std::vector<CuRect> &partition, int search_range = 96)
-      : ctx_(ctx), h_(height), bd_(bitdepth), qp_(qp), qp_c_(ChromaQp(qp)), plan_() {
-    CheckPartition(width, height, partition);
-    int side = 16;
-    for (size_t i = 0; i < partition.size(); i++) {
-      side = partition[i].w > side ? partition[i].w : side;
-      side = partition[i].h > side ? partition[i].h : side;
-    }
-    Build(width, height, partition, search_range, side <= 16 ? 16 : (side <= 32 ? 32 : 64), true);
-  }
-  ~FramePassBi() {
-    for (int l = 0; l < 2; l++)
-      if (plan_[l]) xvcgpu_me_plan_destroy(ctx_.get(), plan_[l]);
-  }
-  FramePassBi(const FramePassBi &) = delete;
-  FramePassBi &operator=(const FramePassBi &) = delete;
-
-  // Enqueues one picture (asynchronous): rec becomes the padded reconstruction.
-  void Run(const Picture &orig, const Picture &ref0, const Picture &ref1, Picture *rec,
-           int ref_poc0 = 0, int ref_poc1 = 2) {
-    xvcgpu_frame_pass_bi_args b = xvcgpu_frame_pass_bi_args();
-    xvcgpu_frame_pass_args &a = b.p;
-    a.orig = orig.get();
-    a.ref = ref0.get();
-    a.rec = rec->get();
-    a.d_me = d_me_[0]->data();
-    a.d_results = d_res_[0]->data();
-    a.n_cus = a.n_cus_total = n_cus_;
-    a.max_block_size = max_cu_;
-    a.qp_y = qp_;
-    a.qp_c = qp_c_;
-    a.ref_poc = ref_poc0;
-    a.d_nnz = d_nnz_->data();
-    a.d_cus_own = d_cus_->data();
-    a.d_cus = d_cus_->data();
-    a.d_cu_map = d_map_->data();
-    a.map_stride = map_stride_;
-    a.db_y_begin = 0;
-    a.db_y_end = a.dbh_y_end = h_;
-    a.ssd_y_begin = 0;
-    a.ssd_y_end = 1 << 30;
-    a.shift_bitdepth = bd_;
-    a.d_ssd = d_ssd_->data();
-    a.pred = pred_->get();
-    a.d_tx = d_tx_->data();
-    a.n_tx = 3 * n_cus_;
-    a.d_luma_tx_index = d_luma_->data();
-    a.form = XVC_FP_FORM_RESIDUAL;
-    b.ref1 = ref1.get();
-    b.d_me_l1 = d_me_[1]->data();
-    b.d_results_l1 = d_res_[1]->data();
-    b.ref_poc_l1 = ref_poc1;
-    b.side_bits_uni[0] = b.side_bits_uni[1] = 3;
-    b.side_bits_bi = 5;
-    for (int l = 0; l < 2; l++) {
-      b.d_bi_jobs[l] = d_bi_jobs_[l]->data();
-      b.d_bi_results[l] = d_bi_res_[l]->data();
-    }
-    b.d_choice = d_choice_->data();
-    b.d_inter = d_inter_->data();
-    ctx_.Check(xvcgpu_frame_pass_bi(ctx_.get(), &b, plan_[0], plan_[1],
-                                    XVC_FP_ENCODE | XVC_FP_DEBLOCK_V | XVC_FP_DEBLOCK_H |
-                                        XVC_FP_PAD | XVC_FP_SSD));
-  }
-
-  // SampleMetric::ComputePsnr parts of the last Run (synchronises).
-  void Ssd(uint64_t *ssd, uint64_t *samples) const {
-    std::vector<uint64_t> v = d_ssd_->ToHost();
-    *ssd = v[0];
-    *samples = v[1];
-  }
-  // what SearchMotion ended with per CU, and the lists' uni-directional searches
-  std::vector<xvcgpu_fp_bi_result> Choices() const { return d_choice_->ToHost(); }
-  std::vector<xvcgpu_me_result> MotionVectors(int list) const { return d_res_[list]->ToHost(); }
-  int num_cus() const { return n_cus_; }
-
- private:
-  void Build(int width, int height, const std::vector<CuRect> &parts, int search_range,
-             int max_cu, bool planned) {
-    map_stride_ = (width + 3) / 4;
-    max_cu_ = max_cu;
-    n_cus_ = static_cast<int>(parts.size());
-    std::vector<int32_t> map(static_cast<size_t>(map_stride_) * ((height + 3) / 4), -1);
-    std::vector<xvcgpu_me_block> me;
-    std::vector<xvcgpu_tx_block> tx;
-    std::vector<int32_t> luma;
-    for (size_t i = 0; i < parts.size(); i++) {
-      const CuRect &p = parts[i];
-      xvcgpu_me_block b = xvcgpu_me_block();
-      b.x = static_cast<int16_t>(p.x);
-      b.y = static_cast<int16_t>(p.y);
-      b.w = static_cast<uint8_t>(p.w);
-      b.h = static_cast<uint8_t>(p.h);
-      b.depth_nonzero = 1;
-      b.lambda16 = Lambda16(qp_);
-      b.search_range = search_range;
-      me.push_back(b);
-      for (int yy = p.y / 4; yy < (p.y + p.h) / 4; yy++)
-        for (int xx = p.x / 4; xx < (p.x + p.w) / 4; xx++)
-          map[static_cast<size_t>(yy) * map_stride_ + xx] = static_cast<int32_t>(i);
-      luma.push_back(static_cast<int32_t>(3 * i));
-      for (int c = 0; c < 3; c++) {   // Y U V per CU: block 3 * cu + comp
-        const int sh = c ? 1 : 0;
-        xvcgpu_tx_block t = xvcgpu_tx_block();
-        t.x = static_cast<int16_t>(p.x >> sh);
-        t.y = static_cast<int16_t>(p.y >> sh);
-        t.w = static_cast<uint8_t>(p.w >> sh);
-        t.h = static_cast<uint8_t>(p.h >> sh);
-        t.comp = static_cast<uint8_t>(c);
-        t.qp = static_cast<int8_t>(c ? qp_c_ : qp_);
-        tx.push_back(t);
-      }
-    }
-    const size_t n = me.size();
-    for (int l = 0; l < 2; l++) {   // list 1's jobs: list 0's until a caller has predictors
-      d_me_[l].reset(new DeviceArray<xvcgpu_me_block>(ctx_, me));
-      d_res_[l].reset(new DeviceArray<xvcgpu_me_result>(ctx_, n));
-      d_bi_jobs_[l].reset(new DeviceArray<xvcgpu_bi_block>(ctx_, n));
-      d_bi_res_[l].reset(new DeviceArray<xvcgpu_me_result>(ctx_, n));
-    }
-    d_choice_.reset(new DeviceArray<xvcgpu_fp_bi_result>(ctx_, n));
-    d_inter_.reset(new DeviceArray<xvcgpu_inter_block>(ctx_, 3 * n));
-    d_map_.reset(new DeviceArray<int32_t>(ctx_, map));
-    d_tx_.reset(new DeviceArray<xvcgpu_tx_block>(ctx_, tx));
-    d_luma_.reset(new DeviceArray<int32_t>(ctx_, luma));
-    d_nnz_.reset(new DeviceArray<int32_t>(ctx_, 3 * n));
-    d_cus_.reset(new DeviceArray<xvcgpu_cu_info>(ctx_, n));
-    d_ssd_.reset(new DeviceArray<uint64_t>(ctx_, 2));
-    ctx_.Check(xvcgpu_memset(ctx_.get(), d_cus_->data(), 0, n * sizeof(xvcgpu_cu_info)));
-    pred_.reset(new Picture(ctx_, width, height, bd_));
-    if (!planned) return;
-    for (int l = 0; l < 2; l++) {
-      int32_t counts[XVCGPU_ME_PLAN_BINS] = {0};
-      xvcgpu_status st =
-          xvcgpu_me_plan_create(ctx_.get(), d_me_[l]->data(), n_cus_, max_cu_, &plan_[l]);
-      if (st == XVCGPU_OK) st = xvcgpu_me_plan_counts(plan_[l], counts);
-      if (st != XVCGPU_OK || counts[XVCGPU_ME_PLAN_UNSUPPORTED] > 0) {
-        for (int k = 0; k < 2; k++)   // (no destructor behind a constructor that throws)
-          if (plan_[k]) xvcgpu_me_plan_destroy(ctx_.get(), plan_[k]);
-        ctx_.Check(st);
-        throw Error(XVCGPU_INVALID_ARGUMENT,
-                    "partition: the motion search has no instance for some CUs (sides must be "
-                    "4, 8, 16, 32 or 64)");
-      }
-    }
-  }
-
-  const Context &ctx_;
-  int h_, bd_, qp_, qp_c_, n_cus_, map_stride_, max_cu_;
-  xvcgpu_me_plan *plan_[2];
-  std::unique_ptr<DeviceArray<xvcgpu_me_block>> d_me_[2];
-  std::unique_ptr<DeviceArray<xvcgpu_me_result>> d_res_[2], d_bi_res_[2];
-  std::unique_ptr<DeviceArray<xvcgpu_bi_block>> d_bi_jobs_[2];
-  std::unique_ptr<DeviceArray<xvcgpu_fp_bi_result>> d_choice_;
-  std::unique_ptr<DeviceArray<xvcgpu_inter_block>> d_inter_;
-  std::unique_ptr<DeviceArray<int32_t>> d_map_, d_luma_, d_nnz_;
-  std::unique_ptr<DeviceArray<xvcgpu_tx_block>> d_tx_;
-  std::unique_ptr<DeviceArray<xvcgpu_cu_info>> d_cus_;
-  std::unique_ptr<DeviceArray<uint64_t>> d_ssd_;
-  std::unique_ptr<Picture> pred_;
-};
-
-// The frame pass of a B picture whose lists name up to XVC_CS_MAX_REFS reference pictures each
-// (the C++ twin of pipeline.BiRefsFramePass): SearchMotion as the reference configures itself
+// The frame pass of a B picture whose lists name 1 to XVC_CS_MAX_REFS reference pictures each
+// (the C++ twin of pipeline.BiRefsFramePass): for every CU InterSearch::SearchMotion over two
+// lists (inter_search.cc:198-259; the SearchBiIterative step :392-433) as the reference
+// configures itself
 // - one search per picture that list 0 has not searched already (inter_search.cc:536-542), the
 // SearchBiIterative step into every picture of the list that lost, the choice against the
 // best of the pictures only list 1 names (:247-257) - then CompressAndEvalCbf, the B picture's
 // DeblockPicture, PadBorder and the PSNR walk: one C call (xvcgpu_frame_pass_bi_refs).
-// QuantFast (form RESIDUAL), closed-form side bits 3 / 3 / 5.  The work arrays between the
-// launches are owned here, as FramePassBi owns its own.
+// Nothing is read back in between.  QuantFast (form RESIDUAL), closed-form side bits
+// (fast_inter_pred_bits: 3 / 3 / 5).  The CUs are the cu x cu grid or, with a partition, a
+// caller's CUs of any mix of sizes (searched through one plan per searched picture).  The work
+// arrays between the launches are owned here.
 class FramePassBiRefs {
  public:
   // The picture's POC and its lists' POCs; what the pass needs beyond them is derived:

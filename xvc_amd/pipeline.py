@@ -560,147 +560,6 @@ class FramePass:
             self.scratch = None
 
 
-class BiFramePass:
-    """The frame pass of a B picture (xvcgpu_frame_pass_bi): both lists searched, the
-    SearchBiIterative step, the choice between L0, L1 and bi per CU, bi-directional
-    prediction, the residual pipeline and the tail with the filter's B-picture word - one
-    C call, nothing read back in between.  One reference picture per list (ref_pocs), one
-    refinement iteration, closed-form side bits (side_bits = uni L0, uni L1, bi).
-
-    The forms are those with a prediction picture: `residual`, `residual_rdoq`, or
-    `fwd_transform` for packed RDOQ; the quantiser's contexts are those of a B picture
-    (rdoq_init_contexts(qp, 0)).  The state every list shares - descriptors, transform
-    blocks, CU records, scratch - is a FramePass's (self.p, list 0's jobs in p.d_me);
-    me_l1 / d_me_l1 are list 1's jobs, a copy until set_jobs gives the lists their own
-    predictors."""
-
-    def __init__(self, ctx, width, height, bitdepth=10, qp=32, cu=16, rdoq=False,
-                 rdoq_packed=None, keep_levels=False, partition=None, ref_pocs=(0, 2),
-                 search_range=96, side_bits=(3, 3, 5)):
-        self.ctx = ctx
-        self.ref_pocs, self.side_bits = tuple(ref_pocs), tuple(side_bits)
-        self.p = p = FramePass(ctx, width, height, bitdepth, qp, cu, search_range, None, True,
-                               keep_levels, rdoq, rdoq_packed, False, partition)
-        self.desc = d = p.desc
-        p.form = "fwd_transform" if p.rdoq_packed else ("residual_rdoq" if rdoq else "residual")
-        self.form = p.form
-        if rdoq:
-            d.rdoq_contexts = rdoq_init_contexts(qp, 0)
-            ctx.h2d(p.d_rdoq_ctx.ptr, d.rdoq_contexts)
-        n = max(1, d.n_cus)
-        self.me_l1 = d.me.copy()
-        self.d_me_l1 = ctx.buffer(self.me_l1)
-        self.d_res_l1 = ctx.alloc(api.MERES_DTYPE.itemsize * n)
-        self.d_bi_jobs = [ctx.alloc(api.BI_DTYPE.itemsize * n) for _ in range(2)]
-        self.d_bi_res = [ctx.alloc(api.MERES_DTYPE.itemsize * n) for _ in range(2)]
-        self.d_choice = ctx.alloc(api.FP_BI_RESULT_DTYPE.itemsize * n)
-        self.d_inter = ctx.alloc(api.INTER_DTYPE.itemsize * 3 * n)
-        self.plan_l1 = None
-        if p.plan is not None:
-            self.plan_l1 = ctx.me_plan(self.d_me_l1.ptr, d.n_cus, d.cu_size)
-
-    def set_jobs(self, me_l0=None, me_l1=None):
-        """New search jobs per list (predictors, flags, lambda; the shapes stay)."""
-        for new, old, buf in ((me_l0, self.desc.me, self.p.d_me),
-                              (me_l1, self.me_l1, self.d_me_l1)):
-            if new is not None:
-                assert all(np.array_equal(new[k], old[k]) for k in ("x", "y", "w", "h"))
-                old[...] = new
-                self.ctx.h2d(buf.ptr, old)
-
-    def _call_args(self, orig, ref0, ref1, rec):
-        a = api.FramePassBiArgs()
-        a.p = self.p._call_args(orig, ref0, rec, self.ref_pocs[0])
-        a.ref1 = ref1.h_pic if ref1 is not None else None
-        a.d_me_l1, a.d_results_l1 = self.d_me_l1.ptr, self.d_res_l1.ptr
-        a.ref_poc_l1 = self.ref_pocs[1]
-        a.side_bits_uni[0], a.side_bits_uni[1], a.side_bits_bi = self.side_bits
-        for l in range(2):
-            a.d_bi_jobs[l], a.d_bi_results[l] = self.d_bi_jobs[l].ptr, self.d_bi_res[l].ptr
-        a.d_choice, a.d_inter = self.d_choice.ptr, self.d_inter.ptr
-        return a
-
-    def run(self, orig, ref0, ref1, rec, fused_tail=True):
-        """Enqueue one whole-picture B pass (asynchronous).  fused_tail=False: end with the
-        separate deblocking, padding and SSD launches also where the one launch applies."""
-        a = self._call_args(orig, ref0, ref1, rec)
-        if not fused_tail:
-            a.p.scratch_rec = None
-        self.ctx._check(self.ctx.lib.xvcgpu_frame_pass_bi(
-            self.ctx.h, C.byref(a), self.p.plan.h if self.p.plan is not None else None,
-            self.plan_l1.h if self.plan_l1 is not None else None,
-            api.FP_ENCODE | api.FP_DEBLOCK_V | api.FP_DEBLOCK_H | api.FP_PAD | api.FP_SSD))
-
-    def kernel_steps(self, orig, ref0, ref1, rec, fused_tail=None):
-        """The launches of one B pass as (name, callable) in issue order, each through its
-        own entry point: run in order they are the pass (per-launch timing, tests)."""
-        ctx, lib, p, d = self.ctx, self.ctx.lib, self.p, self.desc
-        fused_tail = p.fused_tail if fused_tail is None else fused_tail
-        n, chk = d.n_cus, ctx._check
-        me = (p.d_me.ptr, self.d_me_l1.ptr)
-        res = (p.d_res.ptr, self.d_res_l1.ptr)
-        refs = (ref0, ref1)
-        plans = (p.plan, self.plan_l1)
-        out = p.scratch if fused_tail else rec
-
-        def search(l):
-            if plans[l] is not None:
-                return lambda: ctx.me_search_planned(orig, refs[l], api.ME_FULLPEL | api.ME_SUBPEL,
-                                                     plans[l], res[l])
-            return lambda: ctx.me_search_dev(orig, refs[l], p.me_flags, me[l], n, res[l],
-                                             d.cu_size)
-
-        def refine(l):
-            return lambda: ctx.bipred_search_dev(orig, refs[1 - l], refs[l],
-                                                 self.d_bi_jobs[l].ptr, n, self.d_bi_res[l].ptr,
-                                                 d.cu_size)
-        handles = (C.c_void_p * 2)(ref0.h_pic, ref1.h_pic)
-        steps = [
-            ("me_search_l0", search(0)), ("me_search_l1", search(1)),
-            ("uni_fold", lambda: chk(lib.xvcgpu_fp_bi_uni_fold(
-                ctx.h, me[0], me[1], res[0], res[1], n, self.side_bits[0], self.side_bits[1],
-                self.d_bi_jobs[0].ptr, self.d_bi_jobs[1].ptr, self.d_choice.ptr))),
-            ("bipred_l0", refine(0)), ("bipred_l1", refine(1)),
-            ("choice", lambda: chk(lib.xvcgpu_fp_bi_choice(
-                ctx.h, me[0], me[1], res[0], res[1], self.d_bi_res[0].ptr, self.d_bi_res[1].ptr,
-                n, self.side_bits[2], self.d_choice.ptr, self.d_inter.ptr))),
-            ("inter_pred", lambda: chk(lib.xvcgpu_inter_pred_batch(
-                ctx.h, handles, 2, rec.h_pic, p.pred.h_pic, self.d_inter.ptr, 3 * n)))]
-        # the form's residual pipeline: the P pass's launches between its prediction and
-        # its CU records
-        steps += p._launches(orig, ref0, rec, self.ref_pocs[0], fused_tail)[0][2:-1]
-        steps.append(("cu_info", lambda: chk(lib.xvcgpu_cu_info_from_choice(
-            ctx.h, me[0], self.d_choice.ptr, p.d_nnz.ptr, p.d_luma_idx.ptr, n, d.qp, d.qp_c,
-            self.ref_pocs[0], self.ref_pocs[1], p.d_cus_own))))
-        all_cus, stride = p.d_cus.ptr, d.cu_map.shape[1]
-        if fused_tail:
-            return steps + [("deblock_pad_ssd", lambda: ctx.deblock_pad_ssd_dev(
-                out, rec, orig, all_cus, d.n_cus_total, p.d_map.ptr, stride, 1, 0, 0, p.bd,
-                p.d_ssd.ptr))]
-        return steps + [
-            ("deblock", lambda: ctx.deblock_dev(rec, all_cus, d.n_cus_total, p.d_map.ptr,
-                                                stride, 1, 0, 0, 4)),
-            ("pad_border", lambda: ctx.pad_border(rec)),
-            ("picture_ssd", lambda: ctx.picture_ssd_dev(orig, rec, 0, p.bd, p.d_ssd.ptr))]
-
-    def results(self):
-        """FramePass.results() - the search results being a pair, list 0's and list 1's -
-        and the choice records."""
-        d = self.desc
-        res0, nnz, cus, ssd = self.p.results()
-        return ((res0, self.d_res_l1.to_array(api.MERES_DTYPE, d.n_cus)), nnz, cus, ssd,
-                self.d_choice.to_array(api.FP_BI_RESULT_DTYPE, d.n_cus))
-
-    def destroy(self):
-        for b in [self.d_me_l1, self.d_res_l1, self.d_choice, self.d_inter] + self.d_bi_jobs + \
-                self.d_bi_res:
-            b.free()
-        if self.plan_l1 is not None:
-            self.plan_l1.destroy()
-            self.plan_l1 = None
-        self.p.destroy()
-
-
 def ref_list_tables(cur_poc, ref_pocs):
     """What a B picture's two POC lists say as xvcgpu_frame_pass_bi_refs wants it:
     (same_poc_in_l0 per list-1 picture - the first list-0 index of the same POC, or -1,
@@ -723,8 +582,13 @@ class BiRefsFramePass:
     already, the SearchBiIterative step into every picture of the list that lost (by block
     class, through the plan on a partition), the choice against the best unique list-1
     picture, prediction from the chosen pictures, the residual pipeline and the B tail - one
-    C call, nothing read back.  BiFramePass's sibling: forms, contexts and the shared
-    FramePass state (self.p) as there.
+    C call, nothing read back in between.  One refinement iteration, closed-form side bits
+    (side_bits = uni L0, uni L1, bi).
+
+    The forms are those with a prediction picture: `residual`, `residual_rdoq`, or
+    `fwd_transform` for packed RDOQ; the quantiser's contexts are those of a B picture
+    (rdoq_init_contexts(qp, 0)).  The state every (list, picture) shares - descriptors,
+    transform blocks, CU records, scratch - is a FramePass's (self.p).
 
     ref_pocs = [[list 0's POCs], [list 1's]] with cur_poc give same_poc_in_l0, the slot
     table and force_l1_mvd_zero (ref_list_tables); a picture with only back references is
