@@ -29,6 +29,15 @@ __device__ __forceinline__ T group_sum(T v) {
   return v;
 }
 
+// Orders LDS traffic between the lanes of ONE wave (jobs never share data
+// across waves, so no workgroup barrier is ever needed): LDS requests of a
+// wave are serviced in issue order; this only stops compiler reordering and
+// drains outstanding LDS returns.
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
 // for (i = first; i < n; i += STEP) body(i) over the lanes of a wave, first < STEP.  N > 0:
 // n is the constant N - the trips are unrolled and carry no compare, mask update or branch
 // (a bound test only in a last, partial trip); N == 0: the loop as written, n at run time.

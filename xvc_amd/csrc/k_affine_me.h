@@ -60,37 +60,26 @@ __device__ __forceinline__ void affine_me_mc(int bd, int bx, int by, int w, int 
     // plain MC: the wave's slab as a block of its own
     const int rows = affine_slab_rows(w, h);
     if (wave * rows < h) {
-      const uint16_t *r = pr.p + (ptrdiff_t)(by + wave * rows + (mv[0][1] >> 4)) * pr.stride + bx +
-                          (mv[0][0] >> 4);
-      wave_interp_block<false>(bd, w, rows, mv[0][0] & 15, mv[0][1] & 15, r, pr.stride,
-                               s.tmp + wave * (rows * 64 * 11 / 4), s.pred + wave * rows * w);
+      // (McBlock clips the clipped vector once more: no change)
+      const McBlock m(bx, by, w, rows, 0, mv[0][0], mv[0][1], pr, pr.w, pr.h, wave * rows);
+      mc_filter_block<false, McWave>(bd, m.cw, m.ch, m.fx, m.fy, m.ref, m.rs,
+                                     s.tmp + wave * (rows * 64 * 11 / 4),
+                                     McSampleDense{s.pred + wave * rows * w});
     }
     __syncthreads();
     return;
   }
   // All sub-blocks at once (they are 4x4 ... 16x16: one at a time would leave
   // most of a wave idle): the arithmetic per sample is MotionCompUniPred's
-  // (wave_interp_block), with the sub-block's own phase.
+  // (mc_filter_block, k_interp.h), with the sub-block's own phase.
   const int sbw = d_affine_subblock(mv[0][0], mv[0][1], mv[1][0], mv[1][1], w, 0);
   const int sbh = d_affine_subblock(mv[0][0], mv[0][1], mv[2][0], mv[2][1], h, 0);
   const int nsx = w / sbw, nsy = h / sbh, n_sub = nsx * nsy;
   const int lsw = 31 - __clz(sbw), lsh = 31 - __clz(sbh), lnx = 31 - __clz(nsx);
   const int T = 64 * NW, tid = threadIdx.x;
   {
-    const int mv_max_x = (pr.w - bx + 8 - 1) * 16, mv_min_x = (-64 - bx - 8 + 1) * 16;
-    const int mv_max_y = (pr.h - by + 8 - 1) * 16, mv_min_y = (-64 - by - 8 + 1) * 16;
-    const int dhx = ((mv[1][0] - mv[0][0]) * 256) / w;
-    const int dhy = ((mv[1][1] - mv[0][1]) * 256) / w;
-    const int dvx = -dhy, dvy = dhx;
-    for (int k = tid; k < n_sub; k += T) {
-      const int iy = k >> lnx, ix = k & (nsx - 1);
-      const int hor_x = mv[0][0] * 256 + dvx * sbh * iy + dhx * sbw * ix;
-      const int hor_y = mv[0][1] * 256 + dvy * sbh * iy + dhy * sbw * ix;
-      const int mx = (hor_x + dhx * (sbw >> 1) + dvx * (sbh >> 1)) >> 8;
-      const int my = (hor_y + dhy * (sbw >> 1) + dvy * (sbh >> 1)) >> 8;
-      s.sbmv[k][0] = d_clip3(mx, mv_min_x, mv_max_x);
-      s.sbmv[k][1] = d_clip3(my, mv_min_y, mv_max_y);
-    }
+    const AffineSubMv field(mv, w, sbw, sbh, bx, by, pr.w, pr.h);
+    for (int k = tid; k < n_sub; k += T) field.at(k & (nsx - 1), k >> lnx, s.sbmv[k][0], s.sbmv[k][1]);
   }
   __syncthreads();
   const int rows = sbh + 7;  // intermediate rows of a sub-block

@@ -21,9 +21,10 @@
 #include "dev_common.h"
 #include "dev_tables.h"
 #include "k_interp.h"
+#include "k_lic.h"
 #include "k_me.h"
+#include "k_me2.h"
 #include "k_metric.h"
-#include "k_recon.h"
 #include "xvcgpu_internal.h"
 
 // Waves per workgroup (= job).  The 64 class holds 17 KB of interpolation scratch per wave.
@@ -53,9 +54,8 @@ struct __attribute__((aligned(16))) BiShared {
 __device__ __forceinline__ void bi_mc_luma(int bd, const xvcgpu_me_block &b,
                                            const PlaneView &pr, int mx, int my,
                                            int16_t *tmp, uint16_t *pred) {
-  d_clip_mv(b.x, b.y, pr.w, pr.h, mx, my);
-  const uint16_t *r = pr.p + (ptrdiff_t)(b.y + (my >> 4)) * pr.stride + b.x + (mx >> 4);
-  wave_interp_block<false>(bd, b.w, b.h, mx & 15, my & 15, r, pr.stride, tmp, pred);
+  const McBlock m(b.x, b.y, b.w, b.h, 0, mx, my, pr, pr.w, pr.h);
+  mc_filter_block<false, McWave>(bd, m.cw, m.ch, m.fx, m.fy, m.ref, m.rs, tmp, McSampleDense{pred});
 }
 
 // The same by the waves of a workgroup: wave k the rows [k * h / n, (k + 1) * h / n) of the
@@ -67,82 +67,9 @@ __device__ __forceinline__ void bi_mc_luma_slabs(int bd, const xvcgpu_me_block &
   const int n = (b.h >> 2) < nw ? (b.h >> 2) : nw;
   if (wave >= n) return;
   const int rows = b.h / n, row0 = wave * rows;
-  d_clip_mv(b.x, b.y, pr.w, pr.h, mx, my);
-  const uint16_t *r = pr.p + (ptrdiff_t)(b.y + (my >> 4) + row0) * pr.stride + b.x + (mx >> 4);
-  wave_interp_block<false>(bd, b.w, rows, mx & 15, my & 15, r, pr.stride, tmp, pred + row0 * b.w);
-}
-
-// DeriveLicParams (inter_prediction.cc:1577-1663) by the first wave of the
-// workgroup; scale / offset are left in *s_scale / *s_offset (LDS) and are
-// visible after the next __syncthreads().  mx, my: the CU's clipped vector.
-__device__ __forceinline__ void wg_lic_model(int bd, int comp, int bx, int by, int bw, int bh,
-                                             int mx, int my, int neighbors, int above_x,
-                                             int above_y, int left_x, int left_y, int pic_w,
-                                             int pic_h, const PlaneView &pr, const PlaneView &pc,
-                                             int *s_scale, int *s_offset) {
-  if (threadIdx.x >= 64) return;
-  const int lane = threadIdx.x;
-  const int cs = comp ? 1 : 0, shift = 4 + cs;
-  const int cx = bx >> cs, cy = by >> cs, cw = bw >> cs, ch = bh >> cs;
-  const bool has_above = neighbors & XVC_LIC_HAS_ABOVE, has_left = neighbors & XVC_LIC_HAS_LEFT;
-  const int full_x = (mx + (1 << (shift - 1))) >> shift, full_y = (my + (1 << (shift - 1))) >> shift;
-  const int step = (cw < ch ? cw : ch) > 8 ? 2 : 1;
-  const int dx = step * (cw / ch > 1 ? cw / ch : 1), dy = step * (ch / cw > 1 ? ch / cw : 1);
-  const int na = has_above ? cw / dx : 0, nl = has_left ? ch / dy : 0;
-  const int nbr = na + nl;
-  const uint16_t *rb = pr.p + (ptrdiff_t)cy * pr.stride + cx;
-  const uint16_t *sb = pc.p + (ptrdiff_t)cy * pc.stride + cx;
-  int sx = 0, sy = 0, sxx = 0, sxy = 0;
-  for (int i = lane; i < nbr; i += 64) {
-    int a, d;
-    if (i < na) {
-      int vx = full_x, vy = full_y;
-      d_clip_mv(above_x, above_y, pic_w, pic_h, vx, vy);
-      a = rb[(ptrdiff_t)(vy - 1) * pr.stride + vx + i * dx];
-      d = sb[-(ptrdiff_t)pc.stride + i * dx];
-    } else {
-      int vx = full_x, vy = full_y;
-      d_clip_mv(left_x, left_y, pic_w, pic_h, vx, vy);
-      const int yy = (i - na) * dy;
-      a = rb[(ptrdiff_t)(vy + yy) * pr.stride + vx - 1];
-      d = sb[(ptrdiff_t)yy * pc.stride - 1];
-    }
-    sx += a; sy += d; sxx += a * a; sxy += a * d;
-  }
-  sx = group_sum<64>(sx);
-  sy = group_sum<64>(sy);
-  sxx = group_sum<64>(sxx);
-  sxy = group_sum<64>(sxy);
-  if (lane != 0) return;
-  int scale = 32, offset = 0;
-  if (nbr > 0) {
-    int size_shift = 1;
-    while ((1 << size_shift) < nbr) size_shift++;
-    int base_shift = bd + size_shift - 15;
-    base_shift = base_shift < 0 ? 0 : base_shift;
-    const int avg_x = sx >> base_shift, avg_y = sy >> base_shift;
-    const int xx_offset = sxx >> 7;
-    const int avg_xy = ((sxy + xx_offset) >> (2 * base_shift)) << size_shift;
-    const int avg_xx = ((sxx + xx_offset) >> (2 * base_shift)) << size_shift;
-    const int vxy = avg_xy - avg_x * avg_y, vxx = avg_xx - avg_x * avg_x;
-    const int msb = vxx == 0 ? 0 : 32 - __clz(d_abs(vxx));
-    int shift_xx = msb - 6;
-    shift_xx = shift_xx < 0 ? 0 : shift_xx;
-    int shift_xy = shift_xx - 12;
-    shift_xy = shift_xy < 0 ? 0 : shift_xy;
-    const int total_shift = 15 - 5 + shift_xx - shift_xy;
-    const int vxy_s = vxy >> shift_xy;
-    const int vxx_s = d_clip3(vxx >> shift_xx, 0, 63);
-    if (vxx_s != 0) {
-      const int vxx_scaled = ((1 << 15) + (vxx_s / 2)) / vxx_s;
-      const int sc = (int)((long long)vxy_s * vxx_scaled) >> total_shift;
-      scale = d_clip3(sc, 0, 128);
-      const int off = (sy - ((scale * sx) >> 5) + (1 << (size_shift - 1))) >> size_shift;
-      offset = d_clip3(off, -(1 << (bd - 1)), (1 << (bd - 1)) - 1);
-    }
-  }
-  *s_scale = scale;
-  *s_offset = offset;
+  const McBlock m(b.x, b.y, b.w, rows, 0, mx, my, pr, pr.w, pr.h, row0);
+  mc_filter_block<false, McWave>(bd, m.cw, m.ch, m.fx, m.fy, m.ref, m.rs, tmp,
+                                 McSampleDense{pred + row0 * b.w});
 }
 
 // LIC = true: the CU tries local illumination compensation (cu.GetUseLic()).  The
@@ -340,59 +267,6 @@ bipred_search_refs_kernel(PlaneView orig, RefTable refs, const uint8_t *slots, i
                                 nullptr, &refs, slots);
 }
 
-// MotionCompUniPred -> int16 (14-bit, offset removed) by the workgroup
-// (inter_prediction.cc:1156-1172; FilterCopyBipred :1462-1473; shift/offset
-// rules inter_prediction.h:218-254).  tmp: w * (h + N - 1); dst stride w.
-// Contains __syncthreads(): call uniformly.
-template <bool CHROMA>
-__device__ __forceinline__ void wg_interp_block_bipred(int bd, int w, int h, int fx,
-                                                       int fy, const uint16_t *ref,
-                                                       int rs, int16_t *tmp,
-                                                       int16_t *dst) {
-  constexpr int N = CHROMA ? 4 : 8;
-  constexpr int BACK = N / 2 - 1;
-  const int tid = threadIdx.x, nt = blockDim.x;
-  const int lw = 31 - __clz(w);
-  const int16_t *fh = CHROMA ? kChromaTaps[fx] : kLumaTaps[fx];
-  const int16_t *fv = CHROMA ? kChromaTaps[fy] : kLumaTaps[fy];
-  const int head = 14 - bd;
-  const int sh1 = 6 - head, off1 = -(8192 << sh1);  // Sample -> int16
-  if (fx == 0 && fy == 0) {
-    for (int i = tid; i < w * h; i += nt) {
-      const int16_t v = (int16_t)(ref[(ptrdiff_t)(i >> lw) * rs + (i & (w - 1))] << head);
-      dst[i] = (int16_t)(v - (int16_t)8192);
-    }
-    return;
-  }
-  if (fy == 0 || fx == 0) {
-    const int16_t *f = fy == 0 ? fh : fv;
-    const ptrdiff_t step = fy == 0 ? 1 : rs;
-    for (int i = tid; i < w * h; i += nt) {
-      const uint16_t *s = ref + (ptrdiff_t)(i >> lw) * rs + (i & (w - 1)) - BACK * step;
-      int sum = 0;
-#pragma unroll
-      for (int k = 0; k < N; k++) sum += (int)s[k * step] * f[k];
-      dst[i] = (int16_t)((sum + off1) >> sh1);
-    }
-    return;
-  }
-  for (int i = tid; i < w * (h + N - 1); i += nt) {
-    const uint16_t *s = ref + (ptrdiff_t)((i >> lw) - BACK) * rs + (i & (w - 1)) - BACK;
-    int sum = 0;
-#pragma unroll
-    for (int k = 0; k < N; k++) sum += (int)s[k] * fh[k];
-    tmp[i] = (int16_t)((sum + off1) >> sh1);
-  }
-  __syncthreads();
-  for (int i = tid; i < w * h; i += nt) {  // int16 -> int16: shift 6, offset 0
-    const int16_t *s = tmp + i;
-    int sum = 0;
-#pragma unroll
-    for (int k = 0; k < N; k++) sum += (int)s[k * w] * fv[k];
-    dst[i] = (int16_t)(sum >> 6);
-  }
-}
-
 // grid: n; block: 256.  ref0 / ref1 are the list-0 / list-1 pictures.
 __global__ void __launch_bounds__(256)
 mc_bipred_kernel(PicView ref0, PicView ref1, PicView pred,
@@ -403,32 +277,17 @@ mc_bipred_kernel(PicView ref0, PicView ref1, PicView pred,
   if (bi >= n) return;
   const xvcgpu_mc_bi_block b = blocks[bi];
   const int bd = ref0.bd;
-  const int cs = b.comp ? 1 : 0, shift = 4 + cs;
-  const int cx = b.x >> cs, cy = b.y >> cs, cw = b.w >> cs, ch = b.h >> cs;
-  for (int l = 0; l < 2; l++) {
-    int mx = l ? b.mv1_x : b.mv0_x, my = l ? b.mv1_y : b.mv0_y;
-    const PlaneView pr = l ? ref1.c[b.comp] : ref0.c[b.comp];
-    d_clip_mv(b.x, b.y, ref0.c[0].w, ref0.c[0].h, mx, my);
-    const int fx = mx & ((1 << shift) - 1), fy = my & ((1 << shift) - 1);
-    const uint16_t *r = pr.p + (ptrdiff_t)(cy + (my >> shift)) * pr.stride + cx + (mx >> shift);
-    __syncthreads();  // tmp reuse
-    if (b.comp)
-      wg_interp_block_bipred<true>(bd, cw, ch, fx, fy, r, pr.stride, tmp, p[l]);
-    else
-      wg_interp_block_bipred<false>(bd, cw, ch, fx, fy, r, pr.stride, tmp, p[l]);
-  }
+  const McBlock m0(b.x, b.y, b.w, b.h, b.comp, b.mv0_x, b.mv0_y, ref0.c[b.comp], ref0.c[0].w,
+                   ref0.c[0].h);
+  const McBlock m1(b.x, b.y, b.w, b.h, b.comp, b.mv1_x, b.mv1_y, ref1.c[b.comp], ref0.c[0].w,
+                   ref0.c[0].h);
+  mc_filter<McWorkgroup>(bd, b.comp, m0, tmp, McInt14Dense{p[0]});
+  __syncthreads();  // tmp reuse
+  mc_filter<McWorkgroup>(bd, b.comp, m1, tmp, McInt14Dense{p[1]});
   __syncthreads();
-  // AddAvgBi (inter_prediction.cc:1545-1547)
-  const int head = 14 - bd;
-  const int sh = (head > 2 ? head : 2) + 1;
-  const int off = (1 << (sh - 1)) + 2 * 8192;
-  const int smax = (1 << bd) - 1;
   const PlaneView pd = pred.c[b.comp];
-  uint16_t *dst = pd.p + (ptrdiff_t)cy * pd.stride + cx;
-  const int lw = 31 - __clz(cw);
-  for (int i = threadIdx.x; i < cw * ch; i += 256)
-    dst[(ptrdiff_t)(i >> lw) * pd.stride + (i & (cw - 1))] =
-        d_clip_bd(((int)p[0][i] + (int)p[1][i] + off) >> sh, smax);
+  wg_add_avg_bi(bd, m0.cw, m0.ch, p[0], p[1], pd.p + (ptrdiff_t)m0.cy * pd.stride + m0.cx,
+                pd.stride);
 }
 
 // I3 (affine half): MotionCompAffine -> Sample (inter_prediction.cc:1044-1136).
@@ -443,6 +302,30 @@ __device__ __forceinline__ int d_affine_subblock(int rx, int ry, int mx, int my,
   while (size % sb) sb--;
   return (sb > 4 ? sb : 4) >> scale;
 }
+
+// The vector of sub-block (ix, iy) of MotionCompAffine's field (:1103-1133: the
+// reference's running sums in closed form).  mv: the control vectors after
+// ClipMv; cw: the width the field is spread over; sbw x sbh: the sub-block;
+// (x, y): the CU's luma position, which with the picture size bounds the result.
+struct AffineSubMv {
+  int hor_x0, hor_y0, dhx, dhy, sbw, sbh, min_x, max_x, min_y, max_y;
+  __device__ __forceinline__ AffineSubMv(const int (*mv)[2], int cw, int sbw_, int sbh_, int x,
+                                         int y, int pic_w, int pic_h)
+      : sbw(sbw_), sbh(sbh_) {
+    dhx = ((mv[1][0] - mv[0][0]) * 256) / cw;  // C division
+    dhy = ((mv[1][1] - mv[0][1]) * 256) / cw;
+    const int dvx = -dhy, dvy = dhx;
+    hor_x0 = mv[0][0] * 256 + dhx * (sbw >> 1) + dvx * (sbh >> 1);
+    hor_y0 = mv[0][1] * 256 + dhy * (sbw >> 1) + dvy * (sbh >> 1);
+    max_x = (pic_w - x + 8 - 1) * 16, min_x = (-64 - x - 8 + 1) * 16;
+    max_y = (pic_h - y + 8 - 1) * 16, min_y = (-64 - y - 8 + 1) * 16;
+  }
+  __device__ __forceinline__ void at(int ix, int iy, int &mx, int &my) const {
+    const int dvx = -dhy, dvy = dhx;
+    mx = d_clip3((hor_x0 + dvx * sbh * iy + dhx * sbw * ix) >> 8, min_x, max_x);
+    my = d_clip3((hor_y0 + dvy * sbh * iy + dhy * sbw * ix) >> 8, min_y, max_y);
+  }
+};
 
 __global__ void __launch_bounds__(256)
 mc_affine_kernel(PicView ref, PicView pred, const xvcgpu_mc_affine_block *blocks, int n) {
@@ -470,45 +353,32 @@ mc_affine_kernel(PicView ref, PicView pred, const xvcgpu_mc_affine_block *blocks
   const PlaneView pr = ref.c[comp], pd = pred.c[comp];
   uint16_t *out = pd.p + (ptrdiff_t)cy * pd.stride + cx;
   if (mv[0][0] == mv[1][0] && mv[0][1] == mv[1][1]) {
-    const uint16_t *r =
-        pr.p + (ptrdiff_t)(cy + (mv[0][1] >> shift)) * pr.stride + cx + (mv[0][0] >> shift);
-    if (comp)
-      wg_interp_block<true>(bd, cw, ch, mv[0][0] & mask, mv[0][1] & mask, r, pr.stride,
-                            sh.whole, out, pd.stride);
-    else
-      wg_interp_block<false>(bd, cw, ch, mv[0][0] & mask, mv[0][1] & mask, r, pr.stride,
-                             sh.whole, out, pd.stride);
+    // (McBlock clips the clipped vector once more: no change)
+    const McBlock m(b.x, b.y, b.w, b.h, comp, mv[0][0], mv[0][1], pr, pic_w, pic_h);
+    mc_filter<McWorkgroup>(bd, comp, m, sh.whole, McSampleStrided{out, pd.stride});
     return;
   }
   const int sbw = d_affine_subblock(mv[0][0], mv[0][1], mv[1][0], mv[1][1], cw, cs);
   const int sbh = d_affine_subblock(mv[0][0], mv[0][1], mv[2][0], mv[2][1], ch, cs);
-  const int mv_max_x = (pic_w - b.x + 8 - 1) * 16, mv_min_x = (-64 - b.x - 8 + 1) * 16;
-  const int mv_max_y = (pic_h - b.y + 8 - 1) * 16, mv_min_y = (-64 - b.y - 8 + 1) * 16;
-  const int dhx = ((mv[1][0] - mv[0][0]) * 256) / cw;  // C division
-  const int dhy = ((mv[1][1] - mv[0][1]) * 256) / cw;
-  const int dvx = -dhy, dvy = dhx;
+  const AffineSubMv field(mv, cw, sbw, sbh, b.x, b.y, pic_w, pic_h);
   const int nsx = cw / sbw, nsy = ch / sbh;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int lsw = 31 - __clz(sbw);
   for (int k = wave; k < nsx * nsy; k += 4) {
     const int iy = k / nsx, ix = k - iy * nsx;
-    // the reference's running sums, in closed form
-    const int hor_x = mv[0][0] * 256 + dvx * sbh * iy + dhx * sbw * ix;
-    const int hor_y = mv[0][1] * 256 + dvy * sbh * iy + dhy * sbw * ix;
-    int mx = (hor_x + dhx * (sbw >> 1) + dvx * (sbh >> 1)) >> 8;
-    int my = (hor_y + dhy * (sbw >> 1) + dvy * (sbh >> 1)) >> 8;
-    mx = d_clip3(mx, mv_min_x, mv_max_x);
-    my = d_clip3(my, mv_min_y, mv_max_y);
+    int mx, my;
+    field.at(ix, iy, mx, my);
     const int sx = ix * sbw, sy = iy * sbh;
     const uint16_t *r =
         pr.p + (ptrdiff_t)(cy + sy + (my >> shift)) * pr.stride + cx + sx + (mx >> shift);
     wave_sync();  // previous sub-block of this wave copied out
+    const McSampleDense to_lds{sh.wv[wave].dst};
     if (comp)
-      wave_interp_block<true>(bd, sbw, sbh, mx & mask, my & mask, r, pr.stride,
-                              sh.wv[wave].tmp, sh.wv[wave].dst);
+      mc_filter_block<true, McWave>(bd, sbw, sbh, mx & mask, my & mask, r, pr.stride,
+                                    sh.wv[wave].tmp, to_lds);
     else
-      wave_interp_block<false>(bd, sbw, sbh, mx & mask, my & mask, r, pr.stride,
-                               sh.wv[wave].tmp, sh.wv[wave].dst);
+      mc_filter_block<false, McWave>(bd, sbw, sbh, mx & mask, my & mask, r, pr.stride,
+                                     sh.wv[wave].tmp, to_lds);
     wave_sync();
     uint16_t *o = out + (ptrdiff_t)sy * pd.stride + sx;
     for (int i = lane; i < sbw * sbh; i += 64)

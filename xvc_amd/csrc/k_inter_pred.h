@@ -7,8 +7,8 @@
 // pictures of the batch come as a table indexed by the job's per-list slot, so
 // one launch covers all reference pictures of both lists.
 //
-// Translational lists use the workgroup filters (k_interp.h, k_bipred.h:
-// separable, intermediate in LDS).  Affine lists give every thread one output
+// Translational lists use the workgroup's separable filter (k_interp.h:
+// intermediate in LDS).  Affine lists give every thread one output
 // sample with its sub-block's own vector and filter phase and evaluate the two
 // filter stages directly (d_interp_point: identical rounding, stage by stage);
 // a one-4x4-sub-block-at-a-time walk would leave 15/16 of the workgroup idle.
@@ -19,6 +19,7 @@
 #include "dev_tables.h"
 #include "k_bipred.h"
 #include "k_interp.h"
+#include "k_lic.h"
 #include "xvcgpu_internal.h"
 
 // One output sample of MotionCompUniPred at full-pel pointer `s` (the sample's
@@ -84,30 +85,17 @@ __device__ __forceinline__ void wg_affine_block(int bd, int comp, int bx, int by
     sbw = d_affine_subblock(mv[0][0], mv[0][1], mv[1][0], mv[1][1], cw, cs);
     sbh = d_affine_subblock(mv[0][0], mv[0][1], mv[2][0], mv[2][1], ch, cs);
   }
-  const int mv_max_x = (pic_w - bx + 8 - 1) * 16, mv_min_x = (-64 - bx - 8 + 1) * 16;
-  const int mv_max_y = (pic_h - by + 8 - 1) * 16, mv_min_y = (-64 - by - 8 + 1) * 16;
-  const int dhx = ((mv[1][0] - mv[0][0]) * 256) / cw;  // C division
-  const int dhy = ((mv[1][1] - mv[0][1]) * 256) / cw;
-  const int dvx = -dhy, dvy = dhx;
+  const AffineSubMv field(mv, cw, sbw, sbh, bx, by, pic_w, pic_h);
   for (int i = threadIdx.x; i < cw * ch; i += blockDim.x) {
     const int y = i >> lw, x = i & (cw - 1);
     int mx = mv[0][0], my = mv[0][1];
-    if (!plain) {
-      const int ix = x / sbw, iy = y / sbh;
-      // the reference's running sums in closed form (:1103-1133)
-      const int hor_x = mv[0][0] * 256 + dvx * sbh * iy + dhx * sbw * ix;
-      const int hor_y = mv[0][1] * 256 + dvy * sbh * iy + dhy * sbw * ix;
-      mx = d_clip3((hor_x + dhx * (sbw >> 1) + dvx * (sbh >> 1)) >> 8, mv_min_x, mv_max_x);
-      my = d_clip3((hor_y + dhy * (sbw >> 1) + dvy * (sbh >> 1)) >> 8, mv_min_y, mv_max_y);
-    }
+    if (!plain) field.at(x / sbw, y / sbh, mx, my);
     const uint16_t *s = pr.p + (ptrdiff_t)(cy + y + (my >> shift)) * pr.stride + cx + x + (mx >> shift);
     const int v = comp ? d_interp_point<true, BIPRED>(bd, mx & mask, my & mask, s, pr.stride)
                        : d_interp_point<false, BIPRED>(bd, mx & mask, my & mask, s, pr.stride);
     out[y * os + x] = (uint16_t)v;
   }
 }
-
-// (wg_lic_model: k_bipred.h)
 
 // grid: n; block: 256.
 __device__ __forceinline__ void
@@ -122,7 +110,7 @@ inter_pred_body(const RefTable &refs, const PicView &rec, const PicView &pred,
   if (bi_ >= n) return;
   const xvcgpu_inter_block &b = blocks[bi_];
   const int bd = pred.bd, comp = b.comp;
-  const int cs = comp ? 1 : 0, shift = 4 + cs, mask = (1 << shift) - 1;
+  const int cs = comp ? 1 : 0;
   const int cx = b.x >> cs, cy = b.y >> cs, cw = b.w >> cs, ch = b.h >> cs;
   const bool affine = b.flags & XVC_INTER_AFFINE;
   const bool lic = (b.flags & XVC_INTER_LIC) && !affine;
@@ -145,14 +133,9 @@ inter_pred_body(const RefTable &refs, const PicView &rec, const PicView &pred,
         wg_affine_block<true>(bd, comp, b.x, b.y, b.w, b.h, mvl, pic_w, pic_h, pr,
                               reinterpret_cast<uint16_t *>(p16[l]), cw);
       } else {
-        int mx = mvl[0][0], my = mvl[0][1];
-        d_clip_mv(b.x, b.y, pic_w, pic_h, mx, my);
-        const uint16_t *r = pr.p + (ptrdiff_t)(cy + (my >> shift)) * pr.stride + cx + (mx >> shift);
+        const McBlock m(b.x, b.y, b.w, b.h, comp, mvl[0][0], mvl[0][1], pr, pic_w, pic_h);
         __syncthreads();  // tmp reuse
-        if (comp)
-          wg_interp_block_bipred<true>(bd, cw, ch, mx & mask, my & mask, r, pr.stride, tmp, p16[l]);
-        else
-          wg_interp_block_bipred<false>(bd, cw, ch, mx & mask, my & mask, r, pr.stride, tmp, p16[l]);
+        mc_filter<McWorkgroup>(bd, comp, m, tmp, McInt14Dense{p16[l]});
       }
       continue;
     }
@@ -164,16 +147,11 @@ inter_pred_body(const RefTable &refs, const PicView &rec, const PicView &pred,
       wg_affine_block<false>(bd, comp, b.x, b.y, b.w, b.h, mvl, pic_w, pic_h, pr, dst, ds);
       continue;
     }
-    int mx = mvl[0][0], my = mvl[0][1];
-    d_clip_mv(b.x, b.y, pic_w, pic_h, mx, my);
-    const uint16_t *r = pr.p + (ptrdiff_t)(cy + (my >> shift)) * pr.stride + cx + (mx >> shift);
+    const McBlock m(b.x, b.y, b.w, b.h, comp, mvl[0][0], mvl[0][1], pr, pic_w, pic_h);
     __syncthreads();  // tmp / smp reuse
-    if (comp)
-      wg_interp_block<true>(bd, cw, ch, mx & mask, my & mask, r, pr.stride, tmp, dst, ds);
-    else
-      wg_interp_block<false>(bd, cw, ch, mx & mask, my & mask, r, pr.stride, tmp, dst, ds);
+    mc_filter<McWorkgroup>(bd, comp, m, tmp, McSampleStrided{dst, ds});
     if (!lic) continue;
-    wg_lic_model(bd, comp, b.x, b.y, b.w, b.h, mx, my, b.neighbors, b.above_x, b.above_y,
+    wg_lic_model(bd, comp, b.x, b.y, b.w, b.h, m.mx, m.my, b.neighbors, b.above_x, b.above_y,
                  b.left_x, b.left_y, pic_w, pic_h, pr, rec.c[comp], &s_scale, &s_offset);
     __syncthreads();  // model visible; prediction stores ordered before the reads below
     const int scale = s_scale, offset = s_offset;
@@ -188,12 +166,7 @@ inter_pred_body(const RefTable &refs, const PicView &rec, const PicView &pred,
   }
   if (!bi) return;
   __syncthreads();
-  // AddAvgBi (inter_prediction.cc:1545-1547)
-  const int sh = (head > 2 ? head : 2) + 1;
-  const int off = (1 << (sh - 1)) + 2 * 8192;
-  for (int i = threadIdx.x; i < cw * ch; i += 256)
-    out[(ptrdiff_t)(i >> lw) * pd.stride + (i & (cw - 1))] =
-        d_clip_bd(((int)p16[0][i] + (int)p16[1][i] + off) >> sh, smax);
+  wg_add_avg_bi(bd, cw, ch, p16[0], p16[1], out, pd.stride);
 }
 
 __global__ void __launch_bounds__(256)

@@ -137,14 +137,6 @@ __device__ __forceinline__ int wave_reduce_add_i32(int v) {
 #endif
 #define ME2_MIN_WAVES(MS) ((MS) <= 16 ? 4 : 1)  // 5 (96 VGPRs) spills: 80 -> 147 us
 
-// Orders LDS traffic between the lanes of ONE wave (jobs never share data
-// across waves, so no workgroup barrier is ever needed): LDS requests of a
-// wave are serviced in issue order; this only stops compiler reordering and
-// drains outstanding LDS returns.
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
 #define ME2_LANE ((int)(threadIdx.x & 63))
 
 // H-only sub-pel prediction from the 14-bit plane.  FilterHorSampleSample

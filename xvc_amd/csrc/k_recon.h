@@ -26,74 +26,13 @@ struct __attribute__((aligned(16))) ReconShared {
   uint16_t win[23 * 24];  // reference window of the block, rows/cols -3..+4
 };
 
-// MotionCompUniPred -> Sample by one wave (same arithmetic as wg_interp_block
-// in k_interp.h; inter_prediction.cc:1138-1154, :1207-1448).
-template <bool CHROMA>
-__device__ __forceinline__ void wave_interp_block(int bd, int w, int h, int fx,
-                                                  int fy, const uint16_t *ref, int rs,
-                                                  int16_t *tmp, uint16_t *dst) {
-  constexpr int N = CHROMA ? 4 : 8;
-  constexpr int BACK = N / 2 - 1;
-  const int lane = ME2_LANE;
-  const int smax = (1 << bd) - 1;
-  const int lw = 31 - __clz(w);
-  const int16_t *fh = CHROMA ? kChromaTaps[fx] : kLumaTaps[fx];
-  const int16_t *fv = CHROMA ? kChromaTaps[fy] : kLumaTaps[fy];
-  if (fx == 0 && fy == 0) {
-    for (int i = lane; i < w * h; i += 64)
-      dst[i] = ref[(ptrdiff_t)(i >> lw) * rs + (i & (w - 1))];
-    return;
-  }
-  if (fy == 0) {
-    for (int i = lane; i < w * h; i += 64) {
-      const uint16_t *s = ref + (ptrdiff_t)(i >> lw) * rs + (i & (w - 1)) - BACK;
-      int sum = 0;
-#pragma unroll
-      for (int k = 0; k < N; k++) sum += (int)s[k] * fh[k];
-      dst[i] = d_clip_bd((sum + 32) >> 6, smax);
-    }
-    return;
-  }
-  if (fx == 0) {
-    for (int i = lane; i < w * h; i += 64) {
-      const uint16_t *s = ref + (ptrdiff_t)((i >> lw) - BACK) * rs + (i & (w - 1));
-      int sum = 0;
-#pragma unroll
-      for (int k = 0; k < N; k++) sum += (int)s[(ptrdiff_t)k * rs] * fv[k];
-      dst[i] = d_clip_bd((int16_t)((sum + 32) >> 6), smax);
-    }
-    return;
-  }
-  {
-    const int shift = 6 - (14 - bd), offset = -(8192 << shift);
-    for (int i = lane; i < w * (h + N - 1); i += 64) {
-      const uint16_t *s =
-          ref + (ptrdiff_t)((i >> lw) - BACK) * rs + (i & (w - 1)) - BACK;
-      int sum = 0;
-#pragma unroll
-      for (int k = 0; k < N; k++) sum += (int)s[k] * fh[k];
-      tmp[i] = (int16_t)((sum + offset) >> shift);
-    }
-  }
-  wave_sync();
-  {
-    const int shift = 6 + (14 - bd);
-    const int offset = (8192 << 6) + (1 << (shift - 1));
-    for (int i = lane; i < w * h; i += 64) {
-      const int16_t *s = tmp + i;
-      int sum = 0;
-#pragma unroll
-      for (int k = 0; k < N; k++) sum += (int)s[k * w] * fv[k];
-      dst[i] = d_clip_bd((int16_t)((sum + offset) >> shift), smax);
-    }
-  }
-}
-
-// Same arithmetic with the reference window staged in LDS first: one batch of
-// 16-byte loads (one memory round trip) instead of a dependent load per filter
-// tap and loop iteration, and the horizontal pass on packed pairs
-// (v_dot2c_i32_i16: even outputs use the tap pairs as they are, odd outputs
-// the set shifted by one sample).  Blocks up to 16x16.
+// MotionCompUniPred -> Sample by one wave (inter_prediction.cc:1138-1154,
+// :1207-1448; the arithmetic of mc_filter_block, k_interp.h) with the reference
+// window staged in LDS first: one batch of 16-byte loads (one memory round trip)
+// instead of a dependent load per filter tap and loop iteration, and the
+// horizontal pass on packed pairs (v_dot2c_i32_i16: even outputs use the tap
+// pairs as they are, odd outputs the set shifted by one sample).  Blocks up to
+// 16x16.
 template <bool CHROMA, int FW = 0, int FH = 0>   // FW, FH > 0: that exact block size
 __device__ __forceinline__ void wave_interp_block_lds(int bd, int w_in, int h_in, int fx, int fy,
                                                       const uint16_t *ref, int rs,
