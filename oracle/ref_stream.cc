@@ -75,7 +75,7 @@ struct Cu {
 };
 
 struct Info {
-  int32_t poc, doc, tid, nal_type, pic_type; /* pic_type 0 intra 1 uni 2 bi */
+  int32_t poc, doc, tid, nal_type, pic_type; /* pic_type 2 intra 1 uni 0 bi */
   int32_t pic_qp, deblock, beta_offset, tc_offset, allow_lic, adaptive_qp;
   int32_t highest_layer, padded, width, height, bitdepth, two_trees;
   int32_t num_ref[2];
@@ -161,7 +161,9 @@ static void CtuDone() {
       r.qp[c] = static_cast<int8_t>(cu->GetQp(comp));
       r.cbf[c] = cu->GetCbf(comp);
       r.tx_skip[c] = cu->GetTransformSkip(comp);
-      r.dc_only[c] = cu->GetDcCoeffOnly(comp);
+      /* the reader sets it where it reads coefficients; without cbf the
+       * field is left as it was and differs from run to run */
+      r.dc_only[c] = r.cbf[c] ? cu->GetDcCoeffOnly(comp) : 0;
       r.tx_type[c][0] = static_cast<uint8_t>(cu->GetTransformType(comp, 0));
       r.tx_type[c][1] = static_cast<uint8_t>(cu->GetTransformType(comp, 1));
       if (cu->IsIntra()) r.intra_mode[c] = static_cast<int8_t>(cu->GetIntraMode(comp));
@@ -279,15 +281,27 @@ private:
 
 extern "C" {
 
+/* The public encoder parameters xr_stream_encode leaves at xvcenc's defaults.
+ * deblock, low_delay, num_ref_pics: a negative value leaves the default.  The
+ * four offsets are signed quantities (beta -6 is a setting), so for them the
+ * value that leaves the default is XR_STREAM_KEEP (INT32_MIN). */
+#define XR_STREAM_KEEP INT32_MIN
+struct xr_stream_tools {
+  int32_t deblock, beta_offset, tc_offset, low_delay, num_ref_pics;
+  int32_t chroma_qp_offset_u, chroma_qp_offset_v;
+};
+
 /* Encode n_frames packed planar 4:2:0 frames (8 bit: 1 byte per sample, else 2
  * LE) with the reference encoder through its public C API, xvcenc's defaults
- * plus the given qp / threads / (optional) explicit settings.  The NAL units
- * are appended to `out` in output order, each preceded by its 4-byte LE size
- * (the container xvcenc writes).  Returns the number of bytes, or -1. */
-long xr_stream_encode(int width, int height, int input_bitdepth, int internal_bitdepth,
-                      double framerate, int qp, int sub_gop_length, int speed_mode,
-                      int tune_mode, int threads, const char *explicit_settings, int n_frames,
-                      const uint8_t *frames, uint8_t *out, long out_cap) {
+ * plus the given qp / threads / (optional) explicit settings / (optional)
+ * tools.  The NAL units are appended to `out` in output order, each preceded by
+ * its 4-byte LE size (the container xvcenc writes).  Returns the number of
+ * bytes, or -1. */
+long xr_stream_encode_tools(int width, int height, int input_bitdepth, int internal_bitdepth,
+                            double framerate, int qp, int sub_gop_length, int speed_mode,
+                            int tune_mode, int threads, const char *explicit_settings,
+                            const xr_stream_tools *tools, int n_frames, const uint8_t *frames,
+                            uint8_t *out, long out_cap) {
   const xvc_encoder_api *api = xvc_encoder_api_get();
   xvc_encoder_parameters *p = api->parameters_create();
   api->parameters_set_default(p);
@@ -302,6 +316,19 @@ long xr_stream_encode(int width, int height, int input_bitdepth, int internal_bi
   if (speed_mode >= 0) p->speed_mode = speed_mode;
   if (tune_mode >= 0) p->tune_mode = tune_mode;
   p->threads = threads;
+  if (tools) {
+    if (tools->deblock >= 0) p->deblock = tools->deblock;
+    if (tools->beta_offset != XR_STREAM_KEEP) p->beta_offset = tools->beta_offset;
+    if (tools->tc_offset != XR_STREAM_KEEP) p->tc_offset = tools->tc_offset;
+    if (tools->low_delay >= 0) p->low_delay = tools->low_delay;
+    if (tools->num_ref_pics >= 0) p->num_ref_pics = tools->num_ref_pics;
+    if (tools->chroma_qp_offset_u != XR_STREAM_KEEP) {
+      p->chroma_qp_offset_u = tools->chroma_qp_offset_u;
+    }
+    if (tools->chroma_qp_offset_v != XR_STREAM_KEEP) {
+      p->chroma_qp_offset_v = tools->chroma_qp_offset_v;
+    }
+  }
   std::string settings = explicit_settings ? explicit_settings : "";
   if (!settings.empty()) p->explicit_encoder_settings = &settings[0];
   if (api->parameters_check(p) != XVC_ENC_OK) {
@@ -345,6 +372,16 @@ long xr_stream_encode(int width, int height, int input_bitdepth, int internal_bi
   api->encoder_destroy(enc);
   api->parameters_destroy(p);
   return overflow ? -1 : used;
+}
+
+/* The same with every tool at xvcenc's default. */
+long xr_stream_encode(int width, int height, int input_bitdepth, int internal_bitdepth,
+                      double framerate, int qp, int sub_gop_length, int speed_mode,
+                      int tune_mode, int threads, const char *explicit_settings, int n_frames,
+                      const uint8_t *frames, uint8_t *out, long out_cap) {
+  return xr_stream_encode_tools(width, height, input_bitdepth, internal_bitdepth, framerate, qp,
+                                sub_gop_length, speed_mode, tune_mode, threads,
+                                explicit_settings, nullptr, n_frames, frames, out, out_cap);
 }
 
 /* Decode a stream in that container with the reference decoder (one thread)

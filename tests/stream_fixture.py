@@ -19,6 +19,12 @@ import numpy as np
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
+# The small streams at other depths, settings and tool mixes than xvcenc's defaults
+# (test_stream_fixture_content.py says what each holds): the one list every test
+# of them reads.
+OTHER_STREAMS = ["t8", "t12", "t9", "t11", "tq8", "t12q2", "tq50", "tdb", "t8db", "t12nodb",
+                 "tld", "warp", "warpld"]
+
 STREAM_CU_DTYPE = np.dtype([
     ("x", "<i2"), ("y", "<i2"), ("w", "u1"), ("h", "u1"), ("tree", "u1"), ("pred_mode", "u1"),
     ("qp", "i1", (3,)), ("root_cbf", "u1"), ("cbf", "u1", (3,)), ("tx_skip", "u1", (3,)),

@@ -245,6 +245,29 @@ def test_decode_sequence_outputs_equal_reference(gpu, clip, lanes):
                 assert np.array_equal(got[m], full[m]), (clip, i, j, fmt)
 
 
+@pytest.mark.parametrize("clip", ["t8", "t12"])
+@pytest.mark.parametrize("kw", [
+    dict(chroma_format=1, bitdepth=0),                      # 4:2:0 at the internal depth
+    dict(chroma_format=3, bitdepth=8, dither=1),            # 4:4:4, 8 bit, dithered
+    dict(chroma_format=4, bitdepth=8, color_matrix=2),      # ARGB, 8 bit, BT.709
+    dict(width=101, height=37, chroma_format=1, bitdepth=16),
+], ids=["420", "444d8", "argb709", "resized16"])
+def test_decode_sequence_outputs_at_other_depths(gpu, clip, kw):
+    """Streams of 8 and 12 bit internal depth: every picture's output equals the
+    model's conversion of the planes of the same run, and those planes hash to
+    the stream's MD5."""
+    api, ctx = gpu
+    fx = sf.StreamFixture(clip)
+    w, h, bd = (int(fx.info[0][k]) for k in ("width", "height", "bitdepth"))
+    assert bd == {"t8": 8, "t12": 12}[clip]
+    fmt = api.OutputFormat(**kw)
+    data, _, planes = decode_with_outputs(api, ctx, fx, fmt)
+    for j in range(fx.n):
+        assert np.array_equal(sf.picture_md5(planes[j], bd), fx.info[j]["md5"]), (clip, j)
+        exp = om.convert_to(planes[j], bd, w, h, fmt_dict(fmt))
+        assert len(data[j]) == len(exp) and data[j] == exp, (clip, j, fmt)
+
+
 def test_decode_sequence_without_format_unchanged(gpu):
     """No output format: the same planes and launch count as with one (the
     conversion is not one of the decoder's counted launches)."""

@@ -50,7 +50,9 @@ def decode_stream_on_gpu(api, ctx, fx, check, one_launch_intra=True):
 
 @pytest.mark.parametrize("name,one_launch", [("tiny", True), ("c0", True), ("c1", True),
                                              ("c1x", True), ("tiny", False), ("c1", False),
-                                             ("c0q22", True), ("c0q37", True)])
+                                             ("c0q22", True), ("c0q37", True)] +
+                         [(n, True) for n in sf.OTHER_STREAMS] +
+                         [(n, False) for n in ("t8", "t12", "tq8", "tld", "warpld")])
 def test_gpu_reconstructs_reference_stream(gpu, name, one_launch):
     """one_launch: the intra picture's dependency waves as ONE cooperative launch
     (xvcgpu_intra_recon_waves, the default) or as a launch set per wave."""
@@ -106,7 +108,8 @@ def test_gpu_stream_decode_rate(gpu):
 
 
 @pytest.mark.parametrize("name,lanes", [("tiny", 1), ("c1x", 1), ("tiny", 3), ("c0", 2), ("c1x", 3),
-                                        ("c1x", 4)])
+                                        ("c1x", 4)] + [(n, 1) for n in sf.OTHER_STREAMS] +
+                         [(n, 3) for n in ("t8", "t12q2", "tld", "warpld")])
 def test_decode_sequence_equals_stream_md5(gpu, name, lanes):
     """The whole stream through ONE call (PictureDecoder::DecodeSequence: the plan of
     picture i + 1 made on a worker thread while picture i is uploaded and launched; in

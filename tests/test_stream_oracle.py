@@ -51,3 +51,12 @@ def test_oracle_decodes_cif_stream():
 def test_oracle_decodes_1080p_stream():
     """BASELINE config 1 content (1080p QP 32): every picture's MD5."""
     _check_fixture("c1")
+
+
+# The two other CIF operating points and the small clips at other depths, settings
+# and tool mixes (tests/test_stream_fixture_content.py says what each holds).
+@pytest.mark.parametrize("name", ["c0q22", "c0q37"] + sf.OTHER_STREAMS)
+def test_oracle_decodes_other_streams(name):
+    """Every intra CU's neighbour flags and every picture's MD5 (the streams hold no
+    planes)."""
+    _check_fixture(name)

@@ -62,7 +62,7 @@ def main():
         tcap, tstride, tpoc = KEEP_TX[name]
         lib.xr_rd_capture_begin(tpoc)        # (the inter half of that capture is not kept here)
         lib.xr_rd_capture_intra(tstride, tcap)
-        stream = gsg.encode(lib, clip, c["w"], c["h"], c["n"], c["qp"], c["sub_gop"], threads=0)
+        stream = gsg.encode(lib, clip, dict(c, threads=0))
         lib.xr_intra_capture_end()
         lib.xr_rd_capture_end()
         committed = np.load(os.path.join(sf.GOLDEN, "stream_%s.npz" % name))["stream"]

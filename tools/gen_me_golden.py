@@ -52,7 +52,7 @@ def main():
         lib.xr_me_capture_begin(-1 if only is None else only[0])
         for extra in (only or [])[1:]:
             lib.xr_me_capture_also(extra)
-        stream = gsg.encode(lib, clip, c["w"], c["h"], c["n"], c["qp"], c["sub_gop"], threads=0)
+        stream = gsg.encode(lib, clip, dict(c, threads=0))
         n = lib.xr_me_capture_end()
         committed = np.load(os.path.join(sf.GOLDEN, "stream_%s.npz" % name))["stream"]
         assert np.array_equal(stream, committed), "stream differs from the committed fixture"

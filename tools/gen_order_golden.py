@@ -155,7 +155,7 @@ def main():
         lib.xr_intra_capture_begin(1 << 30, 1)
         lib.xr_intra_capture_poc(ipoc)
         lib.xr_rd_capture_intra_walk(1 << 30, ipoc)
-        stream = gsg.encode(lib, clip, c["w"], c["h"], c["n"], c["qp"], c["sub_gop"], threads=0)
+        stream = gsg.encode(lib, clip, dict(c, threads=0))
         n_me = lib.xr_me_capture_end()
         lib.xr_rd_capture_end()
         lib.xr_intra_capture_end()

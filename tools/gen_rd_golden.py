@@ -87,7 +87,7 @@ def main():
         c = gsg.CLIPS[name]
         clip = synth.SyntheticClip(c["w"], c["h"], 8)
         lib.xr_rd_capture_begin(-1 if only is None else only)
-        stream = gsg.encode(lib, clip, c["w"], c["h"], c["n"], c["qp"], c["sub_gop"], threads=0)
+        stream = gsg.encode(lib, clip, dict(c, threads=0))
         lib.xr_rd_capture_end()
         committed = np.load(os.path.join(sf.GOLDEN, "stream_%s.npz" % name))["stream"]
         assert np.array_equal(stream, committed), "stream differs from the committed fixture"
