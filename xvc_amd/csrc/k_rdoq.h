@@ -33,315 +33,13 @@
 #define XVCGPU_K_RDOQ_H_
 
 #include "dev_common.h"
-#include "dev_tables.h"
 #include "k_me.h"
 #include "k_me2.h"
+#include "k_quant.h"
+#include "k_rdoq4.h"
+#include "k_rdoq_common.h"
+#include "k_scan.h"
 #include "xvcgpu_internal.h"
-
-// ContextModel::kEntropyBits_ (context_model.cc:75-93): bits = table[state ^ bin]
-__constant__ uint32_t kEntropyBits[128] = {
-#include "entropy_bits.inc"
-};
-
-#define RQ_BYPASS 32768u  // ContextModel::kEntropyBypassBits
-// the same table in global memory (filled by xvcgpu_create): a lookup by lane from
-// __constant__ memory is one scalar load per distinct index
-__device__ uint32_t gEntropyBits[128];
-
-// Per-block scratch: N = coefficients of the (at most 32x32) low-frequency
-// region; arrays indexed by rec_pos(x, y) (sub-block major, RQ_SB_STRIDE).
-// Developer build (-DXVCGPU_TRACE): clock readings of the walk's sections, one
-// row per workgroup of quant_rdo_packed_kernel (tools/trace_rdoq.py).
-#ifdef XVCGPU_TRACE
-__device__ unsigned long long g_rq_trace[4096][16];
-#define RQ_TRACE(k)                                                          \
-  do {                                                                       \
-    if (threadIdx.x == 0 && blockIdx.x < 4096)                               \
-      g_rq_trace[blockIdx.x][k] = __builtin_amdgcn_s_memtime();              \
-  } while (0)
-// the 100 MHz wall clock beside it (rows 2048 + workgroup, columns 0 / 1): what a
-// tick of s_memtime is worth at the clock the chip runs this kernel at
-#define RQ_TRACE_RT(k)                                                       \
-  do {                                                                       \
-    if (threadIdx.x == 0 && blockIdx.x < 2048)                               \
-      g_rq_trace[2048 + blockIdx.x][k] = __builtin_amdgcn_s_memrealtime();   \
-  } while (0)
-#else
-#define RQ_TRACE(k) do {} while (0)
-#define RQ_TRACE_RT(k) do {} while (0)
-#endif
-// step times inside the diagonal loop, summed (rows' columns 11-13, 14 = diagonals)
-#ifdef XVCGPU_TRACE
-#define RQ_STEP_BEGIN() unsigned long long rq_t_ = __builtin_amdgcn_s_memtime(), rq_a_[4] = {0, 0, 0, 0}
-#define RQ_STEP(i)                                              \
-  do {                                                          \
-    const unsigned long long n_ = __builtin_amdgcn_s_memtime(); \
-    rq_a_[i] += n_ - rq_t_;                                     \
-    rq_t_ = n_;                                                 \
-  } while (0)
-#define RQ_STEP_END()                                                           \
-  do {                                                                          \
-    if (threadIdx.x == 0 && blockIdx.x < 2048)                                  \
-      for (int i_ = 0; i_ < 4; i_++) g_rq_trace[blockIdx.x][11 + i_] = rq_a_[i_]; \
-  } while (0)
-// a second set of four (EvalLastPos' parts): rows 2048 + workgroup
-#define RQ_STEP2_BEGIN() rq_t_ = __builtin_amdgcn_s_memtime(); rq_a_[0] = rq_a_[1] = rq_a_[2] = rq_a_[3] = 0
-#define RQ_STEP2_END()                                                          \
-  do {                                                                          \
-    if (threadIdx.x == 0 && blockIdx.x < 2048)                                  \
-      for (int i_ = 0; i_ < 4; i_++) g_rq_trace[2048 + blockIdx.x][11 + i_] = rq_a_[i_]; \
-  } while (0)
-#else
-#define RQ_STEP_BEGIN() do {} while (0)
-#define RQ_STEP(i) do {} while (0)
-#define RQ_STEP_END() do {} while (0)
-#define RQ_STEP2_BEGIN() do {} while (0)
-#define RQ_STEP2_END() do {} while (0)
-#endif
-
-// Per-coefficient records are laid out sub-block by sub-block with a stride of 17
-// entries (rq_pos): the lanes of a group address the SAME offset of DIFFERENT
-// sub-blocks together, and with the raster layout (stride 4 in x, 64 in y) the
-// 16 lanes of a 16x16 block - and the four blocks of a wave - fell onto the same
-// LDS banks (SQ_LDS_BANK_CONFLICT was 52 % of the LDS cycles).  17 is odd: any 16
-// consecutive sub-blocks land on distinct banks for 1-, 2-, 4- and 8-byte entries.
-#define RQ_SB_STRIDE 17
-#define RQ_PADDED(n) ((n) + (n) / 16)
-// the coefficient / level tiles of the packed kernel are copied 8 bytes at a
-// time: stride 20 keeps every sub-block row 8-byte aligned
-#define RQ_CF_STRIDE 20
-#define RQ_CF_PADDED(n) ((n) + (n) / 4)
-
-// wave_rdoq4's working levels (k_rdoq4.h): the corner's raster with two zero columns /
-// rows to the right / below; its largest shape per coefficient budget: 4x16 / 8x32 /
-// 32x32 ((w + 2) x (h + 2))
-#define RQ_WL(n) ((n) + 2 * ((n) >= 1024 ? 64 : ((n) >= 256 ? 40 : 20)) + 4)
-
-template <int N0>
-struct RdoqShared {
-  static constexpr int N = RQ_PADDED(N0);
-  // coeff_cost_to_zero_ is not kept (8 bytes per coefficient: the records' size is
-  // what limits the waves per CU): EvalLastPos recomputes a coefficient's entry
-  // from what is kept - its level and its 16-bit decision record (rq ctz_of).
-  // coeff_sig_bits_ / the sig-flag rate as what they are made of: the count that
-  // selects the coefficient's significance context, 3 bits of its record - with
-  // the records in LDS their size is what limits the waves per CU
-  unsigned short rate_up[N];   // the decision-time state, 16 bits (RQ_STATE_PACK)
-  // (delta_u - the quantisation error the sign hiding prices, rdo_quant.cc:360-365 - is
-  // a function of the coefficient and its level: re-derived there, err_of below;
-  // a sub-block's zero distortion stays in its owner lane's register)
-  long long sb_code_cost[64];
-  unsigned csbf_bits[64];      // csbf_bits_to_zero
-  unsigned char csbf[64];
-  unsigned char sb_live[64];   // the walk reaches the sub-block
-  unsigned char sb_dcz[64];    // its k = 0 coefficient was decided with sig1 = 0 (rdo_quant.cc:343)
-  unsigned char sb_of_scan[256];  // sub-block scan index -> sy * gw + sx
-  unsigned lp_bits[32];        // EvalLastPos: last-position bits by group of x [0..15], of y [16..31]
-  // GetEntropyBits(bin) of every context of the snapshot: [2 * i + bin] for the
-  // context at byte offset i of xvcgpu_rdoq_contexts.  The walk looks a dozen
-  // of these up per coefficient, each depending on the previous decision: from
-  // global / constant memory that is a dozen dependent ~1 us round trips per
-  // coefficient (the first version ran 0.86 ms per 1080p picture that way).
-  alignas(8) unsigned ctx_bits[2 * sizeof(xvcgpu_rdoq_contexts)];
-  alignas(8) int16_t wl[RQ_WL(N0)];
-  // wave_rdoq4: the flag costs at / behind a scan position (blocks with a 64-point
-  // side: up to 256 positions; the others re-use sb_code_cost)
-  long long fcs_store[N0 >= 1024 ? 256 : 1];
-};
-template <int N0>
-__device__ __forceinline__ long long *rq_fcs(RdoqShared<N0> &s) {
-  return N0 >= 1024 ? s.fcs_store : s.sb_code_cost;
-}
-
-// The same members as pointers (packed kernel: per-coefficient arrays in
-// global memory, the rest in LDS).
-struct RdoqView {
-  int16_t *wl;
-  long long *fcs;
-  unsigned short *rate_up;
-  long long *sb_code_cost;
-  unsigned *csbf_bits;
-  unsigned char *csbf, *sb_live, *sb_dcz;
-  unsigned char *sb_of_scan;
-  unsigned *lp_bits;
-  unsigned *ctx_bits;
-};
-
-// byte offsets of the context groups inside xvcgpu_rdoq_contexts
-#define RQ_OFF(field) ((int)__builtin_offsetof(xvcgpu_rdoq_contexts, field))
-
-__device__ __forceinline__ unsigned rq_bits(unsigned char state, int bin) {
-  return kEntropyBits[state ^ bin];
-}
-__device__ __forceinline__ long long rq_bit_cost(unsigned bits, long long lambda) {
-  return ((long long)bits * lambda) >> 16;
-}
-__device__ __forceinline__ int rq_log2(int size) {  // util::SizeToLog2, powers of two
-  return 31 - __clz(size);
-}
-__device__ __forceinline__ int rq_last_pos_group(int pos) {  // kLastPosGroupIdx
-  if (pos < 4) return pos;
-  const int l = 31 - __clz(pos);                // 4..7 -> 2, 8..15 -> 3, ...
-  return 2 * l + ((pos >> (l - 1)) & 1);
-}
-// reductions over the G (64 or 32) lanes that share a block
-template <int G>
-__device__ __forceinline__ int rq_wave_max_i32(int v) {
-#pragma unroll
-  for (int s = 1; s < G; s <<= 1) {
-    const int o = __shfl_xor(v, s, 64);
-    v = o > v ? o : v;
-  }
-  return v;
-}
-template <int G>
-__device__ __forceinline__ long long rq_wave_sum_i64(long long v) {
-#pragma unroll
-  for (int s = 1; s < G; s <<= 1) v += __shfl_xor(v, s, 64);
-  return v;
-}
-template <int G>
-__device__ __forceinline__ int rq_wave_sum_i32(int v) {
-#pragma unroll
-  for (int s = 1; s < G; s <<= 1) v += __shfl_xor(v, s, 64);
-  return v;
-}
-
-// 64-bit sum over each aligned group of SEG (4 or 16) lanes without LDS traffic:
-// three 32-bit DPP sums (the high word, and the low word as two 16-bit halves so
-// that no partial sum can overflow); every lane of the group gets the total.
-template <int SEG>
-__device__ __forceinline__ long long rq_group_sum_i64(long long v) {
-  const unsigned lo = (unsigned)v;
-  const int hi = dpp_group_sum<SEG>((int)(v >> 32));
-  const int l0 = dpp_group_sum<SEG>((int)(lo & 0xffffu));
-  const int l1 = dpp_group_sum<SEG>((int)(lo >> 16));
-  return (long long)(((unsigned long long)(unsigned)hi << 32) +
-                     ((unsigned long long)(unsigned)l1 << 16) + (unsigned long long)(unsigned)l0);
-}
-
-// Inclusive prefix sum of a 64-bit value over each aligned row of 16 lanes (lane
-// offsets ascending), by DPP row shifts - no LDS crossbar trips: four steps, both
-// halves moved with the same control, lanes in front of the row's start read 0.
-template <int N>
-__device__ __forceinline__ long long rq_row_shr_add_i64(long long v) {
-  const int lo = __builtin_amdgcn_update_dpp(0, (int)(unsigned)v, 0x110 + N, 0xF, 0xF, true);
-  const int hi = __builtin_amdgcn_update_dpp(0, (int)(v >> 32), 0x110 + N, 0xF, 0xF, true);
-  return v + (long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
-}
-__device__ __forceinline__ long long rq_row_scan_i64(long long v) {
-  v = rq_row_shr_add_i64<1>(v);
-  v = rq_row_shr_add_i64<2>(v);
-  v = rq_row_shr_add_i64<4>(v);
-  v = rq_row_shr_add_i64<8>(v);
-  return v;
-}
-
-__device__ __forceinline__ long long *rq_fcs(RdoqView &v) { return v.fcs; }
-
-struct RdoqCoeffState {  // RdoQuant::CoeffCodingState, the part the extended set reads
-  int c1_idx, c2_idx;
-  unsigned golomb_rice_k;
-};
-
-// The greater1 / greater2 flag costs of the coefficient's two contexts, loaded
-// once per coefficient (c1[bin], c2[bin]); the function itself touches no memory.
-struct RdoqFlagBits {
-  unsigned c1_0, c1_1, c2_0, c2_1;
-};
-__device__ __forceinline__ unsigned rq_abs_level_bits(const RdoqFlagBits &f, int level,
-                                                      const RdoqCoeffState &s) {
-  const int base_level = s.c1_idx < 8 ? (2 + (s.c2_idx < 1)) : 1;
-  // TransformHelper::kGolombRiceRangeExt = {6, 5, 6, 3, 3, ...} (transform.cc:61-63), as
-  // arithmetic: a divergent lookup in constant memory costs a ~1 us round trip
-  const unsigned threshold =
-      s.golomb_rice_k < 3 ? (s.golomb_rice_k == 1 ? 5u : 6u) : 3u;
-  unsigned bits = RQ_BYPASS;
-  if (level >= base_level) {
-    unsigned code = (unsigned)(level - base_level);
-    if (code < (threshold << s.golomb_rice_k)) {
-      bits += ((code >> s.golomb_rice_k) + 1 + s.golomb_rice_k) * RQ_BYPASS;
-    } else {
-      // the escape's prefix: the reference subtracts 2^k, 2^(k+1), ... while the
-      // rest is not smaller (rdo_quant.cc:862-866); the sum of those powers is
-      // 2^length - 2^k, so length = floor(log2(rest + 2^k))
-      code -= threshold << s.golomb_rice_k;
-      const int length = 31 - __clz((int)(code + (1u << s.golomb_rice_k)));
-      bits += (unsigned)(length + (int)threshold + length + 1 - (int)s.golomb_rice_k) * RQ_BYPASS;
-    }
-    if (s.c1_idx < 8) {
-      bits += f.c1_1;
-      if (s.c2_idx < 1) bits += f.c2_1;
-    }
-  } else if (level == 1) {
-    bits += f.c1_0;
-  } else if (level == 2) {
-    bits += f.c1_1 + f.c2_0;
-  } else {
-    return 0;
-  }
-  return bits;
-}
-
-// GetCoeffLastPosCtx (cabac.cc:727-770) + GetLastPosBits (rdo_quant.cc:900-947);
-// returns the table index of the context
-__device__ __forceinline__ int rq_last_pos_ctx(bool luma, int w, int h, int pos, bool is_x) {
-  const int size = is_x ? w : h;
-  if (luma) {
-    const int l2 = rq_log2(size);
-    const int off = l2 < 3 ? 0 : (l2 == 3 ? 3 : (l2 == 4 ? 6 : (l2 == 5 ? 10 : (l2 == 6 ? 15 : 21))));
-    const int idx = off + (pos >> ((l2 + 1) >> 2));
-    return 2 * ((is_x ? RQ_OFF(last_x_luma) : RQ_OFF(last_y_luma)) + idx);
-  }
-  const int shift = d_clip3(size >> 3, 0, 2);
-  return 2 * ((is_x ? RQ_OFF(last_x_chroma) : RQ_OFF(last_y_chroma)) + (pos >> shift));
-}
-__device__ __forceinline__ unsigned rq_last_pos_bits(const unsigned *cb, bool luma, int w, int h,
-                                                     int scan_order, int lx, int ly) {
-  if (scan_order == 2) {
-    int t = lx; lx = ly; ly = t;
-    t = w; w = h; h = t;
-  }
-  const int gx = rq_last_pos_group(lx), gy = rq_last_pos_group(ly);
-  unsigned bits = 0;
-  int k;
-  for (k = 0; k < gx; k++) bits += cb[rq_last_pos_ctx(luma, w, h, k, true) + 1];
-  if (gx < rq_last_pos_group(w - 1)) bits += cb[rq_last_pos_ctx(luma, w, h, k, true)];
-  for (k = 0; k < gy; k++) bits += cb[rq_last_pos_ctx(luma, w, h, k, false) + 1];
-  if (gy < rq_last_pos_group(h - 1)) bits += cb[rq_last_pos_ctx(luma, w, h, k, false)];
-  if (gx > 3) bits += (unsigned)((gx - 2) >> 1) * RQ_BYPASS;
-  if (gy > 3) bits += (unsigned)((gy - 2) >> 1) * RQ_BYPASS;
-  return bits;
-}
-
-// One axis of GetLastPosBits for a whole position GROUP g (every position of a
-// group costs the same): the bits of the x (is_x) or y part in a block of
-// (already scan-swapped) size w x h - rq_last_pos_bits = axis(group(x)) +
-// axis(group(y)).  The context costs of all possible prefix bins are read
-// together.
-__device__ __forceinline__ unsigned rq_last_pos_group_bits(const unsigned *cb, bool luma, int w,
-                                                           int h, int g, bool is_x) {
-  const int gmax = rq_last_pos_group((is_x ? w : h) - 1);
-  const int gc = gmax > 0 ? gmax - 1 : 0;
-  unsigned one[10];
-#pragma unroll
-  for (int k = 0; k < 10; k++) one[k] = cb[rq_last_pos_ctx(luma, w, h, k < gc ? k : gc, is_x) + 1];
-  const unsigned zero_bits = cb[rq_last_pos_ctx(luma, w, h, g < gc ? g : gc, is_x)];
-  unsigned bits = 0;
-#pragma unroll
-  for (int k = 0; k < 10; k++) bits += k < g ? one[k] : 0u;
-  if (g < gmax) bits += zero_bits;
-  if (g > 3) bits += (unsigned)((g - 2) >> 1) * RQ_BYPASS;
-  return bits;
-}
-
-// Position of scan offset k inside a sub-block: (x, y) packed as y << 2 | x.
-__device__ __forceinline__ int rq_scan_pos(int sbs, int order, int k) {
-  if (sbs == 2) return (int)((d_scan4_table(order) >> (4 * k)) & 15ull);
-  // TransformHelper::kScanCoeff2x2 (transform.cc:65-69): {0,2,1,3} / raster / {0,2,1,3}
-  const int p = order == 1 ? k : (((k & 1) << 1) | (k >> 1));
-  return ((p >> 1) << 2) | (p & 1);
-}
 
 // G lanes quantise one block: G = 64 (one block per wave), or 32 / 16 / 4 (the
 // blocks of a wave side by side - `s`, cf, lev, the contexts and parameters
@@ -373,24 +71,10 @@ __device__ __forceinline__ int rq_scan_pos(int sbs, int order, int k) {
 // (three GetAbsLevelBits evaluations) are formed when - and if - the sign
 // hiding asks for them: rate_up[] then holds the coefficient's decision-time
 // state (RQ_STATE_*), rate_down[] does not exist.
-// 16 bits per coefficient, ALL that is kept of a decision: the template counts
-// that select its three contexts - n1 / n2 = 0 for the last position, else
-// min(greater-1 / greater-2 neighbours, 4) + 1 (cabac.cc:594-684), nsig =
-// min(significant neighbours, 5) (cabac.cc:520-560); the contexts' position
-// class is a function of x + y and is re-derived by the readers -, what
-// GetAbsLevelBits reads of the budget (c1_idx < 8, c2_idx < 1) and the
-// Golomb-Rice parameter (0..9).  A coefficient left at level 0 only needs n1 (the
-// cost of its greater1 flag's zero bin) and nsig; RQ_STATE_NO_RATE marks the tail
-// of the last sub-block, whose rate is 0.
-#define RQ_STATE_PACK(n1, n2, c1_idx, c2_idx, k, nsig)                                   \
-  ((unsigned short)((unsigned)(n1) | ((unsigned)(n2) << 3) |                              \
-                    ((unsigned)((c1_idx) >= 8) << 6) | ((unsigned)((c2_idx) > 0) << 7) | \
-                    ((unsigned)(k) << 8) | ((unsigned)(nsig) << 12)))
-#define RQ_STATE_NO_RATE 0x8000u
 
 template <int G = 64, typename S, typename CF, typename LEV>
-__device__ __forceinline__ int wave_rdoq(S &s, int lane, int bd, int w, int h,
-                                         int comp_qp, bool luma, int scan_order, bool sign_hide,
+__device__ __forceinline__ int wave_rdoq(S &s, int lane, const BlockQuant &bq, int w, int h,
+                                         bool luma, int scan_order, bool sign_hide,
                                          const xvcgpu_rdoq_contexts &ctx,
                                          const xvcgpu_rdoq_params &prm, CF cf, LEV lev,
                                          bool stage_ctx = true, bool clear_levels = true) {
@@ -399,20 +83,8 @@ __device__ __forceinline__ int wave_rdoq(S &s, int lane, int bd, int w, int h,
   const int gw = w >> sbs, gh = h >> sbs;                   // the whole grid (scan indices)
   const int rw = w < 32 ? w : 32, rh = h < 32 ? h : 32;     // coefficients exist here
   const int rgw = rw >> sbs, rgh = rh >> sbs;
-  const int lw = rq_log2(w), lh = rq_log2(h);
-  int qpb = comp_qp + 6 * (bd - 8);
-  qpb = qpb > 0 ? qpb : 0;
-  const int tshift = 15 - bd - ((lw + lh) >> 1);
-  const bool bias = ((lw + lh) & 1) != 0;
-  const int shift = 14 + qpb / 6 + tshift;
-  const int size_bias_shift = bias ? 7 : 0, size_bias_offset = bias ? 64 : 0;
-  const int scale = kFwdQuantScales[qpb % 6] * (bias ? 181 : 1);
-  const int cost_scale = 15 - 2 * tshift - 2 * (bd - 8) + 2 * (bias ? 1 : 0);
+  const int size_cls = (rq_log2(w) + rq_log2(h)) >> 1;
   const long long lambda = prm.lambda;
-  const int fq_shift = shift + (bias ? 7 : 0);
-  const long long fq_offset = 1ll << (fq_shift - 1);
-  const int iq_shift = 6 - tshift + (bias ? 8 : 0);
-  const int iq_scale = (kInvQuantScales[qpb % 6] << (qpb / 6)) * (bias ? 181 : 1);
 
   const bool mine = lane < rgw * rgh;
   const int sx = mine ? lane % rgw : 0, sy = mine ? lane / rgw : 0;
@@ -428,9 +100,6 @@ __device__ __forceinline__ int wave_rdoq(S &s, int lane, int bd, int w, int h,
   auto rec_pos = [&](int x, int y) {
     return sbs == 2 ? ((y >> 2) * rgw + (x >> 2)) * RQ_SB_STRIDE + (((y & 3) << 2) | (x & 3))
                     : y * rw + x;
-  };
-  auto quant = [&](int a) {  // GetFwdQuantFunc on a magnitude (rdo_quant.cc:949-964)
-    return (int)(short)(int)((((long long)a * scale) + fq_offset) >> fq_shift);
   };
   // the template of decided neighbours (cabac.cc:535-552): five reads issued
   // together (clamped addresses, masked values) - inside the region; beyond it
@@ -452,21 +121,10 @@ __device__ __forceinline__ int wave_rdoq(S &s, int lane, int bd, int w, int h,
     };
     nb(v0, m0); nb(v1, m1); nb(v2, m2); nb(v3, m3); nb(v4, m4);
   };
-  auto sig_ctx_of = [&](int posxy, int n_sig) {  // GetCoeffSigCtx (cabac.cc:520-560)
-    const int size = (lw + lh) >> 1;
-    int start = posxy < 2 ? 6 : 0;
-    start += luma && posxy < 5 ? 6 : 0;
-    start += size > 2 && luma ? 18 << (size - 3 < 1 ? size - 3 : 1) : 0;
-    const int off = n_sig < 5 ? n_sig : 5;
-    return 2 * ((luma ? RQ_OFF(sig_luma) : RQ_OFF(sig_chroma)) + start + off);
+  auto sig_ctx_of = [&](int posxy, int n_sig) {
+    return rq_sig_ctx_base(luma, posxy, size_cls) + 2 * (n_sig < 5 ? n_sig : 5);
   };
-  // greater-1 / greater-2 context from a record's count field nn (0: last position)
-  auto greater_ctx_nn = [&](int posxy, int nn) {  // cabac.cc:594-684
-    const int g1 = luma ? RQ_OFF(greater1_luma) : RQ_OFF(greater1_chroma);
-    const int start = luma ? (posxy < 3 ? 10 : (posxy < 10 ? 5 : 0)) : 0;
-    return nn == 0 ? 2 * g1 : 2 * (g1 + start + nn);
-  };
-  auto greater_nn = [](int n, bool is_last) { return is_last ? 0 : (n < 4 ? n : 4) + 1; };
+  auto greater_ctx_nn = [&](int posxy, int nn) { return rq_greater_ctx(luma, posxy, nn); };
 
   // The last position: the first non-zero quantised value in reverse scan; every
   // sub-block's sum of zero costs (what a sub-block beyond the last position
@@ -477,21 +135,21 @@ __device__ __forceinline__ int wave_rdoq(S &s, int lane, int bd, int w, int h,
   unsigned qmask = 0;
   long long my_zero_dist = 0;
   if (mine) {
-    // sum of (a * a) << cost_scale = (sum of a * a) << cost_scale: cost_scale =
-    // 1 + 2 * ((lw + lh) / 2) + 2 * bias > 0, a * a < 2^31
+    // sum of zero_dist(a) = (sum of a * a) << cost_scale: cost_scale = 1 + 2 * (the
+    // block's size class) + 2 * bias > 0, a * a < 2^31
     unsigned long long sum_sq = 0;
     for (int k = sb_size - 1; k >= 0; k--) {
       int x, y;
       coeff_xy(k, x, y);
       const int a = (short)d_abs(cf(x, y));
       sum_sq += (unsigned)(a * a);
-      if (quant(a)) {
+      if (bq.fwd(a)) {
         qmask |= 1u << k;
         if (last < 0) last = sb_index + k;
       }
       if (clear_levels) *lev(x, y) = 0;   // (a caller that staged zero levels says so)
     }
-    my_zero_dist = (long long)(sum_sq << cost_scale);
+    my_zero_dist = (long long)(sum_sq << bq.cost_scale);
   }
   const int last_pos_index = rq_wave_max_i32<G>(last);
   RQ_TRACE(4);
@@ -541,18 +199,6 @@ __device__ __forceinline__ int wave_rdoq(S &s, int lane, int bd, int w, int h,
     st.c2_idx = (int)((pk >> 7) & 1u);
     st.golomb_rice_k = (pk >> 8) & 15u;
   };
-  auto dequant = [&](int lvl) {
-    int deq;
-    if (iq_shift > 0) deq = (lvl * iq_scale + (1 << (iq_shift - 1))) >> iq_shift;
-    else deq = (lvl * iq_scale) << -iq_shift;
-    return (int)(short)d_clip3(deq, -32768, 32767);
-  };
-  auto err_of = [&](int abs_coeff, int level) {
-    const long long orig_scaled =
-        (((long long)abs_coeff * scale) + size_bias_offset) >> size_bias_shift;
-    const long long quant_err = orig_scaled - ((long long)level << shift);
-    return (int)(short)(quant_err >> (shift - 8));
-  };
   // coeff_cost_to_zero_[index] (rdo_quant.cc:350, :307) of a coefficient whose
   // sub-block is coded, recomputed: zero_cost - best_cost of the decision that
   // left it at level v.  A level of 0 - chosen, or without a choice - cost a zero
@@ -564,14 +210,14 @@ __device__ __forceinline__ int wave_rdoq(S &s, int lane, int bd, int w, int h,
     unsigned sig0, sig1;
     sig_pair(pk, posxy, index, k, dcz, sig0, sig1);
     if (v == 0) return -rq_bit_cost(sig0, lambda);
-    const long long zero_cost = ((long long)(abs_coeff * abs_coeff)) << cost_scale;
+    const long long zero_cost = bq.zero_dist(abs_coeff);
     if (v < 0) return zero_cost - 0x7fffffffffffffffll;
     RdoqFlagBits fb;
     RdoqCoeffState st;
     state_of(pk, posxy, fb, st);
     const unsigned bits = sig1 + rq_abs_level_bits(fb, v, st);
-    const int err = abs_coeff - dequant(v);
-    return zero_cost - ((((long long)err * err) << cost_scale) + rq_bit_cost(bits, lambda));
+    const int err = abs_coeff - bq.dequant(v);
+    return zero_cost - (bq.dist(err) + rq_bit_cost(bits, lambda));
   };
   if (mine) {
     s.csbf[lane] = 0;
@@ -611,14 +257,14 @@ __device__ __forceinline__ int wave_rdoq(S &s, int lane, int bd, int w, int h,
         coeff_xy(k, x, y);
         const int pos = rec_pos(x, y);
         const int abs_coeff = (short)d_abs(cf(x, y));
-        const long long zero_cost = ((long long)(abs_coeff * abs_coeff)) << cost_scale;
-        const int q = quant(abs_coeff);
+        const long long zero_cost = bq.zero_dist(abs_coeff);
+        const int q = bq.fwd(abs_coeff);
         const bool is_last = index == last_pos_index;
         int n_sig, n_g1, n_g2, sum_abs;
         neighbours(x, y, n_sig, n_g1, n_g2, sum_abs);
         const int posxy = x + y;
         const int sig_ctx = sig_ctx_of(posxy, n_sig);
-        const int nn1 = greater_nn(n_g1, is_last), nn2 = greater_nn(n_g2, is_last);
+        const int nn1 = rq_greater_nn(n_g1, is_last), nn2 = rq_greater_nn(n_g2, is_last);
         const int c1_ctx = greater_ctx_nn(posxy, nn1);
         const int c2_ctx = greater_ctx_nn(posxy, nn2);
         {  // GetCoeffGolombRiceK (cabac.cc:686-725): smallest k with 2^(k+3) > threshold
@@ -644,13 +290,9 @@ __device__ __forceinline__ int wave_rdoq(S &s, int lane, int bd, int w, int h,
         if (q > 0) {
           for (int lvl = q > 1 ? q - 1 : q; lvl <= q; lvl++) {
             const unsigned bits = sig1 + rq_abs_level_bits(fb, lvl, st);
-            int deq;
-            if (iq_shift > 0) deq = (lvl * iq_scale + (1 << (iq_shift - 1))) >> iq_shift;
-            else deq = (lvl * iq_scale) << -iq_shift;
-            deq = (short)d_clip3(deq, -32768, 32767);
-            const int err = abs_coeff - deq;
+            const int err = abs_coeff - bq.dequant(lvl);
             const long long cost =
-                (((long long)err * err) << cost_scale) + rq_bit_cost(bits, lambda);
+                bq.dist(err) + rq_bit_cost(bits, lambda);
             if (lvl == q - 1 || cost <= best_cost) {
               best_cost = cost;
               best_level = lvl;
@@ -707,8 +349,8 @@ __device__ __forceinline__ int wave_rdoq(S &s, int lane, int bd, int w, int h,
           const int x = (ax << sbs) + (p & 3), y = (ay << sbs) + (p >> 2);
           const int pos = rec_pos(x, y);
           const int abs_coeff = (short)d_abs(cf(x, y));
-          if (!quant(abs_coeff)) {  // (else: decided in step 1)
-            cost = ((long long)(abs_coeff * abs_coeff)) << cost_scale;
+          if (!bq.codes(abs_coeff)) {  // (else: decided in step 1)
+            cost = bq.zero_dist(abs_coeff);
             if (l2 == last_l && k > last_k) {  // rdo_quant.cc:303-307 (+ the memsets :262-265)
               s.rate_up[pos] = (unsigned short)RQ_STATE_NO_RATE;
             } else {
@@ -718,7 +360,7 @@ __device__ __forceinline__ int wave_rdoq(S &s, int lane, int bd, int w, int h,
               cost += rq_bit_cost(cb[sig_ctx2], lambda);
               // (the k == 0 coefficient of an otherwise empty sub-block codes no flag,
               // sig1 = 0 at rdo_quant.cc:343; nothing reads the rate of such a sub-block)
-              s.rate_up[pos] = RQ_STATE_PACK(greater_nn(n_g1, false), 0, 0, 0, 0,
+              s.rate_up[pos] = RQ_STATE_PACK(rq_greater_nn(n_g1, false), 0, 0, 0, 0,
                                              n_sig < 5 ? n_sig : 5);
             }
           }
@@ -910,9 +552,9 @@ __device__ __forceinline__ int wave_rdoq(S &s, int lane, int bd, int w, int h,
             const unsigned c1_0 = cb[greater_ctx_nn(x + y, (int)(pk & 7u))];
             const unsigned bits1 = sig1 + (((pk >> 6) & 1u) ? (2u + ((pk >> 8) & 15u)) * RQ_BYPASS
                                                            : RQ_BYPASS + c1_0);
-            const int err = ac - dequant(1);
-            ctz = (((long long)(ac * ac)) << cost_scale) -
-                  ((((long long)err * err) << cost_scale) + rq_bit_cost(bits1, lambda));
+            const int err = ac - bq.dequant(1);
+            ctz = bq.zero_dist(ac) -
+                  (bq.dist(err) + rq_bit_cost(bits1, lambda));
           } else if (v != 0) {
             ctz = ctz_of(pk, x + y, index, kk, dcz, ac, v);
           }
@@ -982,9 +624,9 @@ __device__ __forceinline__ int wave_rdoq(S &s, int lane, int bd, int w, int h,
                 const unsigned bits1 =
                     sig1[i] + (((pk[i] >> 6) & 1u) ? (2u + ((pk[i] >> 8) & 15u)) * RQ_BYPASS
                                                    : RQ_BYPASS + c1_0);
-                const int err = ac[i] - dequant(1);
-                ctz = (((long long)(ac[i] * ac[i])) << cost_scale) -
-                      ((((long long)err * err) << cost_scale) + rq_bit_cost(bits1, lambda));
+                const int err = ac[i] - bq.dequant(1);
+                ctz = bq.zero_dist(ac[i]) -
+                      (bq.dist(err) + rq_bit_cost(bits1, lambda));
               } else {
                 ctz = ctz_of(pk[i], xs[i] + ys[i], sb_index + k, k, dcz, ac[i], v[i]);
               }
@@ -1128,7 +770,7 @@ __device__ __forceinline__ int wave_rdoq(S &s, int lane, int bd, int w, int h,
         // delta_u (rdo_quant.cc:360-365) of the level as it was decided (the sign
         // was re-applied above: undo it - a magnitude of 32768 keeps its wrapped value)
         const int coeff = cf(x, y);
-        const int err_dist = err_of((short)d_abs(coeff), coeff < 0 ? -lvl : lvl);
+        const int err_dist = bq.err_of((short)d_abs(coeff), coeff < 0 ? -lvl : lvl);
         long long cost;
         int delta;
         if (lvl != 0) {
@@ -1178,35 +820,6 @@ __device__ __forceinline__ int wave_rdoq(S &s, int lane, int bd, int w, int h,
   }
   return nnz + rq_wave_sum_i32<G>(dn);
 }
-
-// the inverse of the 4x4 scan: position y * 4 + x -> scan offset, 16 nibbles
-constexpr unsigned long long rq_pack_scan4_inv(int order) {
-  const unsigned long long t = tx_pack_scan4(order);
-  unsigned long long r = 0;
-  for (int k = 0; k < 16; k++) r |= (unsigned long long)k << (4 * (int)((t >> (4 * k)) & 15ull));
-  return r;
-}
-
-// A snapshot's bit costs into cb[2 * sizeof(xvcgpu_rdoq_contexts)] by `lanes` lanes
-// (lane = 0 .. lanes - 1): a word of four contexts per lane and round, then its eight
-// table entries - two round trips (byte by byte: three dependent pairs).
-__device__ __forceinline__ void rq_stage_costs(const xvcgpu_rdoq_contexts *snap, unsigned *cb,
-                                               int lane, int lanes) {
-  static_assert(sizeof(xvcgpu_rdoq_contexts) % 4 == 0, "whole words of contexts");
-  constexpr int kWords = (int)sizeof(xvcgpu_rdoq_contexts) / 4;
-  const uint32_t *cw = reinterpret_cast<const uint32_t *>(snap);
-  for (int wi = lane; wi < kWords; wi += lanes) {
-    const uint32_t word = cw[wi];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      const unsigned st8 = (word >> (8 * k)) & 127;
-      *reinterpret_cast<uint2 *>(cb + 8 * wi + 2 * k) =
-          make_uint2(kEntropyBits[st8], kEntropyBits[st8 ^ 1]);
-    }
-  }
-}
-
-#include "k_rdoq4.h"
 
 // ---- the quantiser alone, packed ------------------------------------------------
 // For flows that hold the transform coefficients (xvcgpu_fwd_transform_batch ->
@@ -1302,7 +915,7 @@ __device__ __forceinline__ void rq_scatter_word(uint32_t v, int i, int end, cons
 // per sub-block (wave_rdoq4); 2: everything else (the other scans, 2-wide blocks,
 // more than sixteen sub-blocks, 64-point sides) - a lane per sub-block (wave_rdoq)
 __device__ __forceinline__ int rq_class_of(const xvcgpu_tx_block &b) {
-  if (!rq4_takes(64, b.w, b.h, (b.intra_pic >> XVC_TXF_SCAN_SHIFT) & 3) || b.w > 32 || b.h > 32)
+  if (!rq4_takes(64, b.w, b.h, tx_block_flags(b.intra_pic).scan_order) || b.w > 32 || b.h > 32)
     return 2;
   const int n_sb = (b.w >> 2) * (b.h >> 2);
   return n_sb <= 4 ? 0 : (n_sb <= 16 ? 1 : 2);
@@ -1321,20 +934,11 @@ __device__ __forceinline__ void rdoq_classify_kernel_body(int bd, const xvcgpu_t
   const int lane = threadIdx.x & 63;
   const xvcgpu_tx_block b = blocks[bi];
   const int w = b.w, h = b.h;
-  const int lw = rq_log2(w), lh = rq_log2(h);
-  int qpb = b.qp + 6 * (bd - 8);
-  qpb = qpb > 0 ? qpb : 0;
-  const bool bias = ((lw + lh) & 1) != 0;
-  const int fq_shift = 14 + qpb / 6 + (15 - bd - ((lw + lh) >> 1)) + (bias ? 7 : 0);
-  const int scale = kFwdQuantScales[qpb % 6] * (bias ? 181 : 1);
-  const long long fq_offset = 1ll << (fq_shift - 1);
+  const BlockQuant q = block_quant(b, bd);
   const int16_t *src = coeffs + d_off[bi];
   int16_t *dst = levels + d_off[bi];
   bool any = false;
-  for (int i = lane; i < w * h; i += 64) {
-    const int a = (short)d_abs((int)src[i]);
-    any |= (short)(int)((((long long)a * scale) + fq_offset) >> fq_shift) != 0;
-  }
+  for (int i = lane; i < w * h; i += 64) any |= q.codes((short)d_abs((int)src[i]));
   if (__ballot(any)) {
     if (lane == 0) l.cls[bi] = (signed char)rq_class_of(b);
     return;
@@ -1380,62 +984,29 @@ rdoq_classify_kernel(int bd, const xvcgpu_tx_block *blocks, int n, const int16_t
 #define RQ_PROVE_BLOCKS 16
 #define RQ_PROVE_MAX_CANDS 16
 
-// a block's quantiser constants, as QuantRdo derives them (rdo_quant.cc:223-300)
-struct RqProveBlock {
-  int w, h, lw, lh, scale, fq_shift, cost_scale, iq_shift, iq_scale, scan_order;
-  long long fq_offset, lambda;
-  bool luma, intra_cu;
-};
-
-__device__ __forceinline__ RqProveBlock rq_prove_block(const xvcgpu_tx_block &b, int bd,
-                                                       const xvcgpu_rdoq_params &prm) {
-  RqProveBlock k;
-  k.w = b.w;
-  k.h = b.h;
-  k.luma = b.comp == 0;
-  k.intra_cu = (prm.flags & XVC_RDOQ_INTRA_CU) != 0;
-  k.scan_order = (b.intra_pic >> XVC_TXF_SCAN_SHIFT) & 3;
-  k.lw = rq_log2(k.w);
-  k.lh = rq_log2(k.h);
-  int qpb = b.qp + 6 * (bd - 8);
-  qpb = qpb > 0 ? qpb : 0;
-  const int tshift = 15 - bd - ((k.lw + k.lh) >> 1);
-  const bool bias = ((k.lw + k.lh) & 1) != 0;
-  k.scale = kFwdQuantScales[qpb % 6] * (bias ? 181 : 1);
-  k.fq_shift = 14 + qpb / 6 + tshift + (bias ? 7 : 0);
-  k.fq_offset = 1ll << (k.fq_shift - 1);
-  k.cost_scale = 15 - 2 * tshift - 2 * (bd - 8) + 2 * (bias ? 1 : 0);
-  k.iq_shift = 6 - tshift + (bias ? 8 : 0);
-  k.iq_scale = (kInvQuantScales[qpb % 6] << (qpb / 6)) * (bias ? 181 : 1);
-  k.lambda = prm.lambda;
-  return k;
-}
-
-__device__ __forceinline__ int rq_prove_quant(const RqProveBlock &k, int a) {
-  return (int)(short)(int)((((long long)a * k.scale) + k.fq_offset) >> k.fq_shift);
-}
-
 // the smallest magnitude that quantises to a level: a * scale >= 2^(shift - 1)
-__device__ __forceinline__ int rq_prove_threshold(const RqProveBlock &k) {
-  long long t = (long long)((double)k.fq_offset / (double)k.scale);
-  while (t * k.scale < k.fq_offset) t++;
-  while (t > 0 && (t - 1) * k.scale >= k.fq_offset) t--;
+__device__ __forceinline__ int rq_prove_threshold(const BlockQuant &bq) {
+  long long t = (long long)((double)bq.fq_offset / (double)bq.scale);
+  while (t * bq.scale < bq.fq_offset) t++;
+  while (t > 0 && (t - 1) * bq.scale >= bq.fq_offset) t--;
   return t > 32768 ? 32768 : (int)t;
 }
 
-// One candidate (x, y) with magnitude a: what coding it can save at most as an
-// inner coefficient (gain) and as the last one (gain_last), what a last position
-// there costs on top (rhs), and its place in the scan (idx).  qat(x, y) = the
-// plain quantised magnitude at a position, 0 outside the block; cb = the
-// snapshot's bit costs (entry 2 * ctx + bin).
+// One candidate (x, y) of block b (quantiser bq) with magnitude a: what coding it
+// can save at most as an inner coefficient (gain) and as the last one (gain_last),
+// what a last position there costs on top (rhs), and its place in the scan (idx).
+// qat(x, y) = the plain quantised magnitude at a position, 0 outside the block; cb
+// = the snapshot's bit costs (entry 2 * ctx + bin).
 template <class QAt>
-__device__ __forceinline__ void rq_prove_candidate(const RqProveBlock &k, const unsigned *cb,
-                                                   int x, int y, int a, QAt qat,
-                                                   long long &gain, long long &gain_last,
+__device__ __forceinline__ void rq_prove_candidate(const BlockQuant &bq, const xvcgpu_tx_block &b,
+                                                   const xvcgpu_rdoq_params &prm,
+                                                   const unsigned *cb, int x, int y, int a,
+                                                   QAt qat, long long &gain, long long &gain_last,
                                                    long long &rhs, int &idx) {
-  const int w = k.w, h = k.h;
-  const bool luma = k.luma;
-  const int q = rq_prove_quant(k, a);
+  const int w = b.w, h = b.h, scan_order = tx_block_flags(b.intra_pic).scan_order;
+  const bool luma = b.comp == 0;
+  const long long lambda = prm.lambda;
+  const int q = bq.fwd(a);
   int cnt, cnt1;
   {
     const int q0 = qat(x + 1, y), q1 = qat(x + 2, y), q2 = qat(x + 1, y + 1), q3 = qat(x, y + 1),
@@ -1443,86 +1014,50 @@ __device__ __forceinline__ void rq_prove_candidate(const RqProveBlock &k, const 
     cnt = (q0 > 0) + (q1 > 0) + (q2 > 0) + (q3 > 0) + (q4 > 0);
     cnt1 = (q0 > 1) + (q1 > 1) + (q2 > 1) + (q3 > 1) + (q4 > 1);
   }
-  const int posxy = x + y, size = (k.lw + k.lh) >> 1;
-  // GetCoeffSigCtx (cabac.cc:520-560): the cheapest "1" bin the flag can meet
-  int start = posxy < 2 ? 6 : 0;
-  start += luma && posxy < 5 ? 6 : 0;
-  start += size > 2 && luma ? 18 << (size - 3 < 1 ? size - 3 : 1) : 0;
-  const int sig_base = (luma ? RQ_OFF(sig_luma) : RQ_OFF(sig_chroma)) + start;
+  const int posxy = x + y;
+  // the cheapest "1" bin the significance flag can meet
+  const int sig_base = rq_sig_ctx_base(luma, posxy, (rq_log2(w) + rq_log2(h)) >> 1);
   unsigned sig1 = 0xffffffffu;
   for (int nn = 0; nn <= cnt; nn++) {
-    const unsigned v = cb[2 * (sig_base + nn) + 1];
+    const unsigned v = cb[sig_base + 2 * nn + 1];
     sig1 = v < sig1 ? v : sig1;
   }
   const bool sub_dc = ((x | y) & 3) == 0 && (x | y) != 0;   // k = 0 behind the first sub-block
   if (sub_dc) sig1 = 0;
-  // the greater-1 contexts (cabac.cc:594-684): the last position's, or by the count
-  const int g1 = luma ? RQ_OFF(greater1_luma) : RQ_OFF(greater1_chroma);
-  const int gstart = luma ? (posxy < 3 ? 10 : (posxy < 10 ? 5 : 0)) : 0;
+  // the greater-1 contexts: the last position's, or by the count
   unsigned flag_min = RQ_BYPASS;   // (budget spent: a Golomb-Rice code of at least one bin)
-  {
-    const unsigned v0 = cb[2 * g1], v1 = cb[2 * g1 + 1];
-    flag_min = v0 < flag_min ? v0 : flag_min;
-    flag_min = v1 < flag_min ? v1 : flag_min;
-  }
-  for (int nn = 0; nn <= cnt1; nn++) {
-    const int c = 2 * (g1 + gstart + (nn < 4 ? nn : 4) + 1);
+  auto meet = [&](int nn) {
+    const int c = rq_greater_ctx(luma, posxy, nn);
     const unsigned v0 = cb[c], v1 = cb[c + 1];
     flag_min = v0 < flag_min ? v0 : flag_min;
     flag_min = v1 < flag_min ? v1 : flag_min;
-  }
-  const unsigned lvl_min = RQ_BYPASS + flag_min;   // sign + the cheapest continuation
-  auto dist_of = [&](int lvl) {
-    int deq;
-    if (k.iq_shift > 0) deq = (lvl * k.iq_scale + (1 << (k.iq_shift - 1))) >> k.iq_shift;
-    else deq = (lvl * k.iq_scale) << -k.iq_shift;
-    deq = (short)d_clip3(deq, -32768, 32767);
-    const int err = a - deq;
-    return ((long long)err * err) << k.cost_scale;
   };
-  long long d_best = dist_of(q);
+  meet(0);
+  for (int n = 0; n <= cnt1; n++) meet(rq_greater_nn(n, false));
+  const unsigned lvl_min = RQ_BYPASS + flag_min;   // sign + the cheapest continuation
+  long long d_best = bq.dist(a - bq.dequant(q));
   if (q > 1) {
-    const long long d1 = dist_of(q - 1);
+    const long long d1 = bq.dist(a - bq.dequant(q - 1));
     d_best = d1 < d_best ? d1 : d_best;
   }
-  const long long zd = ((long long)(a * a)) << k.cost_scale;
-  const long long coded = d_best + rq_bit_cost(sig1 + lvl_min, k.lambda);
-  const long long coded_last = d_best + rq_bit_cost(lvl_min, k.lambda);
+  const long long zd = bq.zero_dist(a);
+  const long long coded = d_best + rq_bit_cost(sig1 + lvl_min, lambda);
+  const long long coded_last = d_best + rq_bit_cost(lvl_min, lambda);
   gain = zd - (coded < zd ? coded : zd);
   gain_last = zd - coded_last;
-  const unsigned lp = rq_last_pos_bits(cb, luma, w, h, k.scan_order, x, y);
+  const unsigned lp = rq_last_pos_bits(cb, luma, w, h, scan_order, x, y);
   const int cbf_ctx = 2 * (!luma ? RQ_OFF(cbf_chroma)
-                                 : (k.intra_cu ? RQ_OFF(cbf_luma) : RQ_OFF(root_cbf)));
-  rhs = rq_bit_cost(cb[cbf_ctx + 1], k.lambda) - rq_bit_cost(cb[cbf_ctx], k.lambda) +
-        rq_bit_cost(lp, k.lambda);
+                                 : ((prm.flags & XVC_RDOQ_INTRA_CU) ? RQ_OFF(cbf_luma)
+                                                                    : RQ_OFF(root_cbf)));
+  rhs = rq_bit_cost(cb[cbf_ctx + 1], lambda) - rq_bit_cost(cb[cbf_ctx], lambda) +
+        rq_bit_cost(lp, lambda);
   // scan index: sub-block in the grid's scan, offset in the sub-block's (the
   // inverse of the 4x4 scan: position y * 4 + x -> scan offset, 16 nibbles)
   constexpr unsigned long long inv0 = rq_pack_scan4_inv(0), inv1 = rq_pack_scan4_inv(1),
                                inv2 = rq_pack_scan4_inv(2);
-  const unsigned long long inv = k.scan_order == 0 ? inv0 : (k.scan_order == 1 ? inv1 : inv2);
+  const unsigned long long inv = scan_order == 0 ? inv0 : (scan_order == 1 ? inv1 : inv2);
   const int kk = (int)((inv >> (4 * (((y & 3) << 2) | (x & 3)))) & 15ull);
-  idx = (d_sb_scan_index(k.scan_order, w >> 2, h >> 2, x >> 2, y >> 2) << 4) + kk;
-}
-
-// A snapshot's bit costs into cb[2 * 152] by the first `lanes` lanes (a word of
-// four contexts per lane and round, its eight entries).
-__device__ __forceinline__ void rq_prove_stage_costs(const xvcgpu_rdoq_contexts *snap,
-                                                     unsigned *cb, int lane, int lanes) {
-  constexpr int kWords = (int)sizeof(xvcgpu_rdoq_contexts) / 4;
-  const uint32_t *cw = reinterpret_cast<const uint32_t *>(snap);
-  for (int wi = lane; wi < kWords; wi += lanes) {
-    const uint32_t word = cw[wi];
-    unsigned e[8];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      const unsigned st8 = (word >> (8 * k)) & 127;
-      e[2 * k] = gEntropyBits[st8];
-      e[2 * k + 1] = gEntropyBits[st8 ^ 1];
-    }
-    uint4 *o = reinterpret_cast<uint4 *>(cb + 8 * wi);
-    o[0] = make_uint4(e[0], e[1], e[2], e[3]);
-    o[1] = make_uint4(e[4], e[5], e[6], e[7]);
-  }
+  idx = (d_sb_scan_index(scan_order, w >> 2, h >> 2, x >> 2, y >> 2) << 4) + kk;
 }
 
 __global__ void __launch_bounds__(256)
@@ -1549,7 +1084,7 @@ rdoq_prove_zero_kernel(int bd, const xvcgpu_tx_block *blocks, int n, const int16
   __syncthreads();
   const int wg_ctx = s_ctx;
   if (wg_ctx < 0) return;   // no live block (uniform)
-  rq_prove_stage_costs(&rq_ctx[wg_ctx], s_cb, (int)threadIdx.x, 256);
+  rq_stage_costs(gEntropyBits, &rq_ctx[wg_ctx], s_cb, (int)threadIdx.x, 256);
   __syncthreads();   // the context costs are in place
   // From here on a group of sixteen lanes works on its own block and its own rows
   // of the shared arrays: groups never share data, a wave holds four of them, so
@@ -1564,8 +1099,8 @@ rdoq_prove_zero_kernel(int bd, const xvcgpu_tx_block *blocks, int n, const int16
       s_fail[g] = 0;
     }
     wave_sync();
-    const RqProveBlock k = rq_prove_block(b, bd, prm);
-    const int w = k.w, h = k.h;
+    const BlockQuant bq = block_quant(b, bd);
+    const int w = b.w, h = b.h;
     const int16_t *src = coeffs + d_off[live ? bi : 0];
     // (coefficients are read four at a time: a block that does not start on 8 bytes
     // is left to the walk)
@@ -1573,12 +1108,12 @@ rdoq_prove_zero_kernel(int bd, const xvcgpu_tx_block *blocks, int n, const int16
                        h <= 32 && (reinterpret_cast<uintptr_t>(src) & 7) == 0;
     auto qat = [&](int x, int y) {
       if (x >= w || y >= h) return 0;
-      return rq_prove_quant(k, (short)d_abs((int)src[y * w + x]));
+      return bq.fwd((short)d_abs((int)src[y * w + x]));
     };
     // the candidates: coefficients with q > 0 - one compare against the smallest
     // such magnitude, four coefficients per load (a magnitude of 32768: no proof)
     if (tried) {
-      const int thr = rq_prove_threshold(k);
+      const int thr = rq_prove_threshold(bq);
       bool wrap = false;
       for (int i = 4 * gl; i < w * h; i += 64) {
         const uint2 v = *reinterpret_cast<const uint2 *>(src + i);
@@ -1591,7 +1126,7 @@ rdoq_prove_zero_kernel(int bd, const xvcgpu_tx_block *blocks, int n, const int16
             const int slot = atomicAdd(&s_n[g], 1);
             const int ii = i + t;
             if (slot < RQ_PROVE_MAX_CANDS)
-              s_xy[g][slot] = (unsigned short)(((ii >> k.lw) << 8) | (ii & (w - 1)));
+              s_xy[g][slot] = (unsigned short)(((ii >> rq_log2(w)) << 8) | (ii & (w - 1)));
           }
         }
       }
@@ -1607,7 +1142,7 @@ rdoq_prove_zero_kernel(int bd, const xvcgpu_tx_block *blocks, int n, const int16
       const int x = s_xy[g][gl] & 255, y = s_xy[g][gl] >> 8;
       const int a = (short)d_abs((int)src[y * w + x]);
       long long gain;
-      rq_prove_candidate(k, s_cb, x, y, a, qat, gain, gain_last, rhs, my_idx);
+      rq_prove_candidate(bq, b, prm, s_cb, x, y, a, qat, gain, gain_last, rhs, my_idx);
       s_idx[g][gl] = my_idx;
       s_gain[g][gl] = gain;
     }
@@ -1649,7 +1184,8 @@ struct RqProveLds {
 };
 
 template <int G>
-__device__ __forceinline__ bool rq_prove_zero_lds(RqProveLds &pv, const xvcgpu_tx_block &b, int bd,
+__device__ __forceinline__ bool rq_prove_zero_lds(RqProveLds &pv, const xvcgpu_tx_block &b,
+                                                  int bd,
                                                   const xvcgpu_rdoq_contexts *rq_ctx,
                                                   const xvcgpu_rdoq_params &prm,
                                                   const int16_t *c, bool live) {
@@ -1665,14 +1201,14 @@ __device__ __forceinline__ bool rq_prove_zero_lds(RqProveLds &pv, const xvcgpu_t
   tried = tried && (int)prm.ctx_index == wave_ctx;
   if (pv.staged_ctx != wave_ctx) {
     wave_sync();
-    rq_prove_stage_costs(&rq_ctx[wave_ctx], pv.cb, wl, 64);
+    rq_stage_costs(gEntropyBits, &rq_ctx[wave_ctx], pv.cb, wl, 64);
     if (wl == 0) pv.staged_ctx = wave_ctx;
     wave_sync();
   }
-  const RqProveBlock k = rq_prove_block(b, bd, prm);
+  const BlockQuant bq = block_quant(b, bd);
   auto qat = [&](int x, int y) {
     if (x >= w || y >= h) return 0;
-    return rq_prove_quant(k, (short)d_abs((int)c[x * h + y]));
+    return bq.fwd((short)d_abs((int)c[x * h + y]));
   };
   long long gain_last = 0, rhs = 0;
   int my_idx = 0;
@@ -1681,7 +1217,7 @@ __device__ __forceinline__ bool rq_prove_zero_lds(RqProveLds &pv, const xvcgpu_t
     const int x = pv.xy[grp][lane] & 255, y = pv.xy[grp][lane] >> 8;
     const int a = (short)d_abs((int)c[x * h + y]);
     long long gain;
-    rq_prove_candidate(k, pv.cb, x, y, a, qat, gain, gain_last, rhs, my_idx);
+    rq_prove_candidate(bq, b, prm, pv.cb, x, y, a, qat, gain, gain_last, rhs, my_idx);
     pv.idx[grp][lane] = my_idx;
     pv.gain[grp][lane] = gain;
   }
@@ -2044,26 +1580,12 @@ __device__ __forceinline__ void quant_rdo_packed_wave(
     const long long klambda = __shfl(prm.lambda, leader, 64);
     wave_sync();  // the previous round's readers are done with the table
     {
-      // two round trips in all: a word of four contexts per lane, then its eight
-      // table entries (byte by byte it was three dependent pairs of trips)
-      static_assert(sizeof(xvcgpu_rdoq_contexts) % 4 == 0 &&
-                        sizeof(xvcgpu_rdoq_contexts) / 4 <= 64,
-                    "one word of contexts per lane");
-      constexpr int kWords = (int)sizeof(xvcgpu_rdoq_contexts) / 4;
+      // rq_stage_costs with a word per lane, the lane's own word already at hand
+      static_assert(RQ_CTX_WORDS <= 64, "one word of contexts per lane");
       const uint32_t *cw = reinterpret_cast<const uint32_t *>(&rq_ctx[cur]);
       const uint32_t word = (int)prm.ctx_index == cur ? word_own : cw[ctx_wi];
-      unsigned e[8];
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        const unsigned st8 = (word >> (8 * k)) & 127;
-        e[2 * k] = kEntropyBits[st8];
-        e[2 * k + 1] = kEntropyBits[st8 ^ 1];
-      }
-      if ((int)threadIdx.x < kWords) {
-        uint4 *o = reinterpret_cast<uint4 *>(sm.ctx_bits + 8 * threadIdx.x);
-        o[0] = make_uint4(e[0], e[1], e[2], e[3]);
-        o[1] = make_uint4(e[4], e[5], e[6], e[7]);
-      }
+      if ((int)threadIdx.x < RQ_CTX_WORDS)
+        rq_stage_word(kEntropyBits, word, sm.ctx_bits + 8 * threadIdx.x);
     }
     wave_sync();
     RQ_TRACE(3);
@@ -2092,19 +1614,28 @@ __device__ __forceinline__ void quant_rdo_packed_wave(
       xvcgpu_rdoq_params uprm = prm;   // rd_factor stays the lane's own
       uprm.lambda = ulambda;
       uprm.flags = (uint8_t)upf;
-      const int uscan = (uflags >> XVC_TXF_SCAN_SHIFT) & 3;
+      const TxBlockFlags ufl = tx_block_flags(uflags);
+      const int uscan = ufl.scan_order;
+      const bool ush = ufl.sign_hide;
+      // (k_quant.h; derived in the arm that walks, in front of the walk)
+      auto ubq = [&](int bw, int bh) { return block_quant(bw, bh, uqp, bd, ufl.intra_pic); };
       auto cf_at = [cf, utile](int x, int y) { return (int)cf[utile(x, y)]; };
       auto lv_at = [lv, utile](int x, int y) { return lv + utile(x, y); };
-      const bool ush = !(uflags & XVC_TXF_NO_SIGN_HIDING);
       if (FOUR) {
         // four lanes per sub-block (k_rdoq4.h): the class lists hold what it takes; the
         // levels go straight to the block's place in global memory
         const RqTileCf cf4 = {cf, urgw4};
         const RqGlobalLev lv4 = {dst, uw};
-        nnz = wave_rdoq4<G, 1>(v, lane, bd, uw, uh, uqp, uluma != 0, ush, uprm, cf4, lv4);
-      } else if (NSB == 64 && rq4_takes(64, uw, uh, uscan)) {
-        // (more than sixteen sub-blocks or a 64-point side: four units per lane)
-        nnz = wave_rdoq4<64, 4>(v, lane, bd, uw, uh, uqp, uluma != 0, ush, uprm, cf_at, lv_at);
+        nnz = wave_rdoq4<G, 1>(v, lane, ubq(uw, uh), uw, uh, uluma != 0, ush, uprm, cf4, lv4);
+      } else if (NSB == 64) {
+        // the general class: more than sixteen sub-blocks or a 64-point side in the diagonal
+        // scan (four units per lane), or a lane per sub-block
+        const BlockQuant q = ubq(uw, uh);
+        if (rq4_takes(64, uw, uh, uscan))
+          nnz = wave_rdoq4<64, 4>(v, lane, q, uw, uh, uluma != 0, ush, uprm, cf_at, lv_at);
+        else
+          nnz = wave_rdoq<G>(v, lane, q, uw, uh, uluma != 0, uscan, ush, rq_ctx[cur], uprm, cf_at,
+                             lv_at, false, false);
       } else if (G == 16 && NSB == 16 && uw == 16 && uh == 16) {
         // (the instance for the exact 16x16 block beside the any-size one: the long lists of
         // a large picture - RDOQ4_LATENCY_BLOCKS - are almost only these)
@@ -2114,10 +1645,10 @@ __device__ __forceinline__ void quant_rdo_packed_wave(
         auto lv16 = [lv](int x, int y) {
           return lv + ((y >> 2) * 4 + (x >> 2)) * RQ_CF_STRIDE + (((y & 3) << 2) | (x & 3));
         };
-        nnz = wave_rdoq<G>(v, lane, bd, 16, 16, uqp, uluma != 0, uscan, ush, rq_ctx[cur], uprm,
+        nnz = wave_rdoq<G>(v, lane, ubq(16, 16), 16, 16, uluma != 0, uscan, ush, rq_ctx[cur], uprm,
                            cf16, lv16, false, false);
       } else {
-        nnz = wave_rdoq<G>(v, lane, bd, uw, uh, uqp, uluma != 0, uscan, ush, rq_ctx[cur], uprm,
+        nnz = wave_rdoq<G>(v, lane, ubq(uw, uh), uw, uh, uluma != 0, uscan, ush, rq_ctx[cur], uprm,
                            cf_at, lv_at, false, false);
       }
       pending = false;

@@ -47,6 +47,12 @@
 #ifndef XVCGPU_K_RDOQ4_H_
 #define XVCGPU_K_RDOQ4_H_
 
+#include "dev_common.h"
+#include "k_me2.h"
+#include "k_quant.h"
+#include "k_rdoq_common.h"
+#include "k_scan.h"
+
 // ---- quad (four consecutive lanes) exchanges: DPP quad_perm, no LDS ------------
 template <int I>
 __device__ __forceinline__ int rq4_quad_bcast(int v) {   // lane I of the quad to all four
@@ -153,7 +159,7 @@ __device__ __forceinline__ long long rq4_suffix_i64(long long v) {
 }
 
 // TransformHelper::DeriveSubblockScan's index of sub-block (sx, sy) in the diagonal
-// scan over a gw x gh grid (d_sb_scan_index, k_tx.h) in closed form: the cells on the
+// scan over a gw x gh grid (d_sb_scan_index, k_scan.h) in closed form: the cells on the
 // diagonals in front of s = sx + sy (their lengths grow to min(gw, gh), stay, shrink),
 // then the place on its own diagonal.
 __device__ __forceinline__ int rq4_sb_scan_index(int gw, int gh, int sx, int sy) {
@@ -215,7 +221,7 @@ __device__ __forceinline__ void rq4_store_row(const LEV &lev, int px, int y, con
 // number of non-zero levels to every lane; every level of the corner is written
 // (levels of a 64-point side beyond it are the caller's to clear).
 template <int G, int NR, typename S, typename CF, typename LEV>
-__device__ __forceinline__ int wave_rdoq4(S &s, int lane, int bd, int w, int h, int comp_qp,
+__device__ __forceinline__ int wave_rdoq4(S &s, int lane, const BlockQuant &bq, int w, int h,
                                           bool luma, bool sign_hide,
                                           const xvcgpu_rdoq_params &prm, CF cf, LEV lev) {
   static_assert(NR == 1 || (NR == 4 && G == 64), "one unit per lane, or four with 64 lanes");
@@ -225,20 +231,8 @@ __device__ __forceinline__ int wave_rdoq4(S &s, int lane, int bd, int w, int h, 
   const int rw = w < 32 ? w : 32, rh = h < 32 ? h : 32;       // coefficients exist here
   const int rgw = rw >> 2, rgh = rh >> 2, nsb = rgw * rgh;
   const bool outside = gw * gh != nsb;                        // a 64-point side
-  const int lw = rq_log2(w), lh = rq_log2(h), lrgw = rq_log2(rgw);
-  int qpb = comp_qp + 6 * (bd - 8);
-  qpb = qpb > 0 ? qpb : 0;
-  const int tshift = 15 - bd - ((lw + lh) >> 1);
-  const bool bias = ((lw + lh) & 1) != 0;
-  const int shift = 14 + qpb / 6 + tshift;
-  const int size_bias_shift = bias ? 7 : 0, size_bias_offset = bias ? 64 : 0;
-  const int scale = kFwdQuantScales[qpb % 6] * (bias ? 181 : 1);
-  const int cost_scale = 15 - 2 * tshift - 2 * (bd - 8) + 2 * (bias ? 1 : 0);
+  const int size_cls = (rq_log2(w) + rq_log2(h)) >> 1, lrgw = rq_log2(rgw);
   const long long lambda = prm.lambda;
-  const int fq_shift = shift + (bias ? 7 : 0);
-  const long long fq_offset = 1ll << (fq_shift - 1);
-  const int iq_shift = 6 - tshift + (bias ? 8 : 0);
-  const int iq_scale = (kInvQuantScales[qpb % 6] << (qpb / 6)) * (bias ? 181 : 1);
   const unsigned *cb = s.ctx_bits;
   int16_t *wl = s.wl;                     // the levels being decided, (rw + 2) x (rh + 2)
   const int WS = rw + 2;
@@ -252,21 +246,6 @@ __device__ __forceinline__ int wave_rdoq4(S &s, int lane, int bd, int w, int h, 
   auto rec_pos = [&](int x, int y) {
     return ((y >> 2) * rgw + (x >> 2)) * RQ_SB_STRIDE + (((y & 3) << 2) | (x & 3));
   };
-  auto quant = [&](int a) {  // GetFwdQuantFunc on a magnitude (rdo_quant.cc:949-964)
-    return (int)(short)(int)((((long long)a * scale) + fq_offset) >> fq_shift);
-  };
-  auto dequant = [&](int lvl) {
-    int deq;
-    if (iq_shift > 0) deq = (lvl * iq_scale + (1 << (iq_shift - 1))) >> iq_shift;
-    else deq = (lvl * iq_scale) << -iq_shift;
-    return (int)(short)d_clip3(deq, -32768, 32767);
-  };
-  auto err_of = [&](int abs_coeff, int level) {   // delta_u, rdo_quant.cc:360-365
-    const long long orig_scaled =
-        (((long long)abs_coeff * scale) + size_bias_offset) >> size_bias_shift;
-    const long long quant_err = orig_scaled - ((long long)level << shift);
-    return (int)(short)(quant_err >> (shift - 8));
-  };
   // the template of decided neighbours (cabac.cc:535-552) of the coefficient at wl[p]
   auto neighbours = [&](int p, int &n_sig, int &n_g1, int &n_g2, int &sum_abs) {
     const int v0 = d_abs((int)wl[p + 1]), v1 = d_abs((int)wl[p + 2]),
@@ -277,25 +256,10 @@ __device__ __forceinline__ int wave_rdoq4(S &s, int lane, int bd, int w, int h, 
     n_g2 = (v0 > 2) + (v1 > 2) + (v2 > 2) + (v3 > 2) + (v4 > 2);
     sum_abs = v0 + v1 + v2 + v3 + v4;
   };
-  const int size_cls = (lw + lh) >> 1;
-  const int sig_luma_size =
-      size_cls > 2 && luma ? 18 << (size_cls - 3 < 1 ? size_cls - 3 : 1) : 0;
-  auto sig_base_of = [&](int posxy) {  // GetCoeffSigCtx (cabac.cc:520-560) without the count
-    int start = posxy < 2 ? 6 : 0;
-    start += luma && posxy < 5 ? 6 : 0;
-    return 2 * ((luma ? RQ_OFF(sig_luma) : RQ_OFF(sig_chroma)) + start + sig_luma_size);
-  };
   auto sig_ctx_of = [&](int posxy, int n_sig) {
-    return sig_base_of(posxy) + 2 * (n_sig < 5 ? n_sig : 5);
+    return rq_sig_ctx_base(luma, posxy, size_cls) + 2 * (n_sig < 5 ? n_sig : 5);
   };
-  const int g1_off = luma ? RQ_OFF(greater1_luma) : RQ_OFF(greater1_chroma);
-  auto greater_start_of = [&](int posxy) {   // cabac.cc:594-684
-    return luma ? (posxy < 3 ? 10 : (posxy < 10 ? 5 : 0)) : 0;
-  };
-  auto greater_ctx_nn = [&](int posxy, int nn) {
-    return nn == 0 ? 2 * g1_off : 2 * (g1_off + greater_start_of(posxy) + nn);
-  };
-  auto greater_nn = [](int n, bool is_last) { return is_last ? 0 : (n < 4 ? n : 4) + 1; };
+  auto greater_ctx_nn = [&](int posxy, int nn) { return rq_greater_ctx(luma, posxy, nn); };
 
   // ---- the units: magnitudes, plain quantised values, signs (two 16-bit halves a
   // register); per sub-block the zero distortion and the q != 0 set; the last position
@@ -322,7 +286,7 @@ __device__ __forceinline__ int wave_rdoq4(S &s, int lane, int bd, int w, int h, 
 #pragma unroll
     for (int i = 0; i < 4; i++) {
       a[i] = (short)d_abs(c[i]);
-      q[i] = quant(a[i]);
+      q[i] = bq.fwd(a[i]);
       negs |= (unsigned)(c[i] < 0) << (4 * r + i);
       sum_sq += (unsigned)(a[i] * a[i]);
       if (q[i]) qm |= 1u << kof(i);
@@ -333,7 +297,7 @@ __device__ __forceinline__ int wave_rdoq4(S &s, int lane, int bd, int w, int h, 
     pq[r][1] = (unsigned)(q[2] & 0xffff) | ((unsigned)q[3] << 16);
     valid |= (unsigned)mine << r;
     const unsigned qmask = (unsigned)rq4_quad_or((int)qm);
-    zd_u[r] = (long long)((unsigned long long)rq_group_sum_i64<4>((long long)sum_sq) << cost_scale);
+    zd_u[r] = (long long)((unsigned long long)rq_group_sum_i64<4>((long long)sum_sq) << bq.cost_scale);
     const int l = mine && qmask ? (scan_u[r] << 4) + 31 - __clz((int)qmask) : -1;
     last = l > last ? l : last;
   }
@@ -482,7 +446,7 @@ __device__ __forceinline__ int wave_rdoq4(S &s, int lane, int bd, int w, int h, 
       const int p = row_p + xi;
       // the position class x + y is the step's: 4 d + sd
       const int posxy = 4 * d + sd;
-      const int sig_base = sig_base_of(posxy), g_start = greater_start_of(posxy);
+      const int sig_base = rq_sig_ctx_base(luma, posxy, size_cls);
       // what does not depend on the budget
       int nn1 = 0, nn2 = 0, n_sig5 = 0;
       unsigned gr = 0, sig1 = 0;
@@ -493,8 +457,8 @@ __device__ __forceinline__ int wave_rdoq4(S &s, int lane, int bd, int w, int h, 
         const bool is_last = sb_index + k == last_pos_index;
         int n_sig, n_g1, n_g2, sum_abs;
         neighbours(p, n_sig, n_g1, n_g2, sum_abs);
-        nn1 = greater_nn(n_g1, is_last);
-        nn2 = greater_nn(n_g2, is_last);
+        nn1 = rq_greater_nn(n_g1, is_last);
+        nn2 = rq_greater_nn(n_g2, is_last);
         n_sig5 = n_sig < 5 ? n_sig : 5;
         {  // GetCoeffGolombRiceK (cabac.cc:686-725): smallest k with 2^(k+3) > threshold
           const unsigned threshold = 4u + (unsigned)(sum_abs - n_sig);
@@ -502,24 +466,18 @@ __device__ __forceinline__ int wave_rdoq4(S &s, int lane, int bd, int w, int h, 
           gr = (unsigned)(kk < 0 ? 0 : (kk > 9 ? 9 : kk));
         }
         const uint2 sig_b = *reinterpret_cast<const uint2 *>(cb + sig_base + 2 * n_sig5);
-        const uint2 c1_b = *reinterpret_cast<const uint2 *>(
-            cb + (nn1 == 0 ? 2 * g1_off : 2 * (g1_off + g_start + nn1)));
-        const uint2 c2_b = *reinterpret_cast<const uint2 *>(
-            cb + (nn2 == 0 ? 2 * g1_off : 2 * (g1_off + g_start + nn2)));
+        const uint2 c1_b = *reinterpret_cast<const uint2 *>(cb + greater_ctx_nn(posxy, nn1));
+        const uint2 c2_b = *reinterpret_cast<const uint2 *>(cb + greater_ctx_nn(posxy, nn2));
         fb.c1_0 = c1_b.x; fb.c1_1 = c1_b.y; fb.c2_0 = c2_b.x; fb.c2_1 = c2_b.y;
         // (k == 0 is alone on its anti-diagonal: nz is final for it)
         dc_sig_zero = sb_index > 0 && k == 0 && nz == 0;
         sig1 = (is_last || dc_sig_zero) ? 0u : sig_b.y;
-        const long long zero_cost = ((long long)(abs_coeff * abs_coeff)) << cost_scale;
+        const long long zero_cost = bq.zero_dist(abs_coeff);
         zero_ok = !is_last && qv < 3;
         zero_alt = zero_cost + rq_bit_cost(sig_b.x, lambda);
         if (qv > 0) {
-          const int e0 = abs_coeff - dequant(qv);
-          dist_q = ((long long)e0 * e0) << cost_scale;
-          if (qv > 1) {
-            const int e1 = abs_coeff - dequant(qv - 1);
-            dist_q1 = ((long long)e1 * e1) << cost_scale;
-          }
+          dist_q = bq.dist(abs_coeff - bq.dequant(qv));
+          if (qv > 1) dist_q1 = bq.dist(abs_coeff - bq.dequant(qv - 1));
         }
       }
       // QuantCoeffRdo (rdo_quant.cc:708-735) + the zero alternative (:333-341) with the
@@ -604,15 +562,15 @@ __device__ __forceinline__ int wave_rdoq4(S &s, int lane, int bd, int w, int h, 
           const int pp = rq_scan_pos(2, 0, k);
           const int x = (ax << 2) + (pp & 3), y = (ay << 2) + (pp >> 2);
           const int abs_coeff = (short)d_abs(cf(x, y));
-          if (!quant(abs_coeff)) {  // (else: decided in step 1)
-            cost = ((long long)(abs_coeff * abs_coeff)) << cost_scale;
+          if (!bq.codes(abs_coeff)) {  // (else: decided in step 1)
+            cost = bq.zero_dist(abs_coeff);
             if (l2 == last_l && k > last_k) {  // rdo_quant.cc:303-307 (+ the memsets :262-265)
               s.rate_up[rec_pos(x, y)] = (unsigned short)RQ_STATE_NO_RATE;
             } else {
               int n_sig, n_g1, n_g2, sum_abs;
               neighbours(y * WS + x, n_sig, n_g1, n_g2, sum_abs);
               cost += rq_bit_cost(cb[sig_ctx_of(x + y, n_sig)], lambda);
-              s.rate_up[rec_pos(x, y)] = RQ_STATE_PACK(greater_nn(n_g1, false), 0, 0, 0, 0,
+              s.rate_up[rec_pos(x, y)] = RQ_STATE_PACK(rq_greater_nn(n_g1, false), 0, 0, 0, 0,
                                                        n_sig < 5 ? n_sig : 5);
             }
           }
@@ -805,13 +763,11 @@ __device__ __forceinline__ int wave_rdoq4(S &s, int lane, int bd, int w, int h, 
           const unsigned c1_0 = cb[greater_ctx_nn(x + y, (int)(pk & 7u))];
           const unsigned bits1 = sig1 + (((pk >> 6) & 1u) ? (2u + ((pk >> 8) & 15u)) * RQ_BYPASS
                                                          : RQ_BYPASS + c1_0);
-          const int err = ac - dequant(1);
-          ctz = (((long long)(ac * ac)) << cost_scale) -
-                ((((long long)err * err) << cost_scale) + rq_bit_cost(bits1, lambda));
+          ctz = bq.zero_dist(ac) - (bq.dist(ac - bq.dequant(1)) + rq_bit_cost(bits1, lambda));
         } else if (v < 0) {
           // (a magnitude of 32768 decided as the last position: best_cost stayed at
           // its initial value)
-          ctz = (((long long)(ac * ac)) << cost_scale) - 0x7fffffffffffffffll;
+          ctz = bq.zero_dist(ac) - 0x7fffffffffffffffll;
         }
       }
       const long long inc = rq_row_scan_i64(ctz);
@@ -963,7 +919,7 @@ __device__ __forceinline__ int wave_rdoq4(S &s, int lane, int bd, int w, int h, 
         const bool ng = ((negs >> (4 * r + i)) & 1u) != 0;
         // delta_u of the level as it was decided (the sign was re-applied: undo it -
         // a magnitude of 32768 keeps its wrapped value)
-        const int err_dist = err_of(half(pa[r], i), ng ? -lvl : lvl);
+        const int err_dist = bq.err_of(half(pa[r], i), ng ? -lvl : lvl);
         long long cost;
         int delta;
         if (lvl != 0) {

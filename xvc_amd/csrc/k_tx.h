@@ -16,6 +16,9 @@
 
 #include "dev_common.h"
 #include "dev_tables.h"
+#include "k_quant.h"
+#include "k_rdoq.h"
+#include "k_scan.h"
 #include "xvcgpu_internal.h"
 
 #define TX_THREADS 256
@@ -115,96 +118,6 @@ __device__ __forceinline__ void tx_inv_dst4(int shift, const int16_t *in,
   }
 }
 
-// ---- sign-data hiding: RdoQuant::CoeffSignHideFast (rdo_quant.cc:448-573) --
-// Scan position k of a 4x4 sub-block as y*4 + x (TransformHelper::
-// kScanCoeff4x4, transform.cc:72-76): order 0 walks the anti-diagonals from
-// bottom-left to top-right, 1 is raster, 2 is column-major.
-constexpr unsigned long long tx_pack_scan4(int order) {
-  unsigned long long t = 0;
-  int k = 0;
-  if (order == 0) {
-    for (int s = 0; s < 7; s++)
-      for (int y = (s < 4 ? s : 3); y >= 0 && s - y < 4; y--, k++)
-        t |= (unsigned long long)((y << 2) | (s - y)) << (4 * k);
-  } else {
-    for (k = 0; k < 16; k++)
-      t |= (unsigned long long)(order == 1 ? k : (((k & 3) << 2) | (k >> 2))) << (4 * k);
-  }
-  return t;
-}
-// 16 nibbles: scan position k -> y*4 + x
-__device__ __forceinline__ unsigned long long d_scan4_table(int order) {
-  constexpr unsigned long long t0 = tx_pack_scan4(0), t1 = tx_pack_scan4(1),
-                               t2 = tx_pack_scan4(2);
-  return order == 0 ? t0 : (order == 1 ? t1 : t2);
-}
-// Index of sub-block (sx, sy) in the scan over a gw x gh grid of sub-blocks
-// (TransformHelper::DeriveSubblockScan, transform.cc:1639-1683).
-__device__ __forceinline__ int d_sb_scan_index(int order, int gw, int gh, int sx, int sy) {
-  if (order == 1) return sy * gw + sx;
-  if (order == 2) return sx * gh + sy;
-  const int s = sx + sy;
-  int idx = 0;
-  for (int d = 0; d < s; d++) {
-    int c = d < gw - 1 ? d : gw - 1;
-    c = c < gh - 1 ? c : gh - 1;
-    c = c < gw + gh - 2 - d ? c : gw + gh - 2 - d;
-    idx += c + 1;
-  }
-  return idx + ((s < gh - 1 ? s : gh - 1) - sy);
-}
-
-// One 4x4 sub-block, by one thread.  IDX(x, y) maps a coefficient position
-// to the index used by the three arrays (levels in/out, remainders, the
-// unquantised coefficients).  Returns the change of the non-zero count.
-template <typename IDX>
-__device__ __forceinline__ int d_sign_hide_subblock(int order, int px, int py,
-                                                    bool is_last_sb, int16_t *lev,
-                                                    const int16_t *dl, const int16_t *cf,
-                                                    IDX idx) {
-  const unsigned long long tab = d_scan4_table(order);
-  auto at = [&](int k) {
-    const int p = (int)((tab >> (4 * k)) & 15ull);
-    return idx(px + (p & 3), py + (p >> 2));
-  };
-  int last = -1, first = 16, sum = 0;
-  for (int k = 0; k < 16; k++) {
-    const int c = lev[at(k)];
-    if (c) {
-      first = k < first ? k : first;
-      last = k;
-      sum += c;
-    }
-  }
-  if (last - first <= 3) return 0;
-  const int sign = lev[at(first)] > 0 ? 0 : 1;
-  if (sign == (sum & 1)) return 0;
-  int curr_cost = 32767, curr_change = 0, min_cost = 32767, min_change = 0, min_index = 0;
-  for (int k = is_last_sb ? last : 15; k >= 0; k--) {
-    const int p = at(k);
-    const int l = lev[p], d = dl[p];
-    if (l != 0) {
-      if (d > 0) { curr_cost = -d; curr_change = 1; }
-      else if (k == first && d_abs(l) == 1) curr_cost = 32767;
-      else { curr_cost = d; curr_change = -1; }
-    } else if (k < first && (cf[p] >= 0 ? 0 : 1) != sign) {
-      curr_cost = 32767;
-    } else {
-      curr_cost = -d;
-      curr_change = 1;
-    }
-    if (curr_cost < min_cost) { min_cost = curr_cost; min_change = curr_change; min_index = k; }
-  }
-  const int p = at(min_index);
-  const int before = lev[p];
-  if (before == -32768 || before == 32767) min_change = -1;
-  const int after = (int16_t)(before + (cf[p] >= 0 ? min_change : -min_change));
-  lev[p] = (int16_t)after;
-  return (after != 0) - (before != 0);
-}
-
-#include "k_rdoq.h"  // needs the scan helpers above
-
 // Jobs taken by the one-wave-per-job kernel (k_tx2.h); the rest stay here.
 __device__ __forceinline__ bool tx_small_job(const xvcgpu_tx_block &b) {
   const bool okw = b.w == 4 || b.w == 8 || b.w == 16;
@@ -239,14 +152,18 @@ __device__ __forceinline__ int residual_job(TxShared &s, int bi, const PicView &
   __syncthreads();  // previous job of this workgroup is done with s
   const xvcgpu_tx_block b = blocks[bi];
   const int w = b.w, h = b.h, bd = pred.bd;
-  const int lw = 31 - __clz(w);
-  const int lgw = d_log2_size(w), lgh = d_log2_size(h);
+  const int lw = rq_log2(w);
   const PlaneView pp = pred.c[b.comp];
   const bool skip = b.tx_hor == XVC_TX_SKIP;  // TransformSkip, blocks <= 4x4
-  const bool intra_pic = (b.intra_pic & XVC_TXF_INTRA_PIC) != 0;
-  const bool sign_hide = !(b.intra_pic & XVC_TXF_NO_SIGN_HIDING);
-  const int scan_order = (b.intra_pic >> XVC_TXF_SCAN_SHIFT) & 3;
+  const TxBlockFlags fl = tx_block_flags(b.intra_pic);
+  const bool sign_hide = fl.sign_hide;
+  const int scan_order = fl.scan_order;
   const bool dst4 = b.dst4x4 && w == 4 && h == 4 && !skip;
+  // k_quant.h; called in front of each use, so that nothing of them is live across a transform
+  auto quant = [&]() { return block_quant(w, h, b.qp, bd, fl.intra_pic); };
+  auto shifts = [&]() {
+    return dst4 ? tx_stage_shifts_dst4(bd) : tx_stage_shifts(b.tx_hor, b.tx_ver, lw, rq_log2(h), bd);
+  };
   int16_t *lv = (levels && level_off) ? levels + level_off[bi] : nullptr;
 
   // matrices
@@ -257,12 +174,6 @@ __device__ __forceinline__ int residual_job(TxShared &s, int bi, const PicView &
     for (int i = threadIdx.x; i < h * h; i += TX_THREADS) s.mv[i] = gv[i];
   }
   if (threadIdx.x == 0) s.nnz = 0;
-
-  // quantiser parameters (quantize.cc:48-72, :94-131; rdo_quant.cc:160-169)
-  int qpb = b.qp + 6 * (bd - 8);
-  qpb = qpb > 0 ? qpb : 0;
-  const bool bias = ((lgw + lgh) & 1) != 0;
-  const int tshift = 15 - bd - ((lgw + lgh) >> 1);
 
   int nnz;
   if (MODE != TX_MODE_INV) {
@@ -276,25 +187,24 @@ __device__ __forceinline__ int residual_job(TxShared &s, int bi, const PicView &
       s.a[y * TX_S + x] = (int16_t)(o - p);
     }
     __syncthreads();
-    // forward transform (transform.cc:869-961; a stage of XVC_TX_DCT2_LOW has the
-    // 6-bit matrix and no high-precision shift, :876-884)
-    const int shift1 = lgw + bd - 9 + (b.tx_hor == XVC_TX_DCT2_LOW ? 0 : 2);
-    const int shift2 = lgh + 6 + (b.tx_ver == XVC_TX_DCT2_LOW ? 0 : 2);
+    // forward transform (transform.cc:869-961)
+    const TxStageShifts st = shifts();
     if (skip) {  // ForwardTransform::TransformSkip, transform.cc:963-995
-      const int sh = tshift + (bias ? -8 : 0), sc = bias ? 181 : 1;
+      const BlockQuant q = quant();
+      const int sh = q.tshift + (q.bias ? -8 : 0), sc = q.bias ? 181 : 1;
       for (int i = threadIdx.x; i < w * h; i += TX_THREADS) {
         const int k = (i >> lw) * TX_S + (i & (w - 1));
         const int v = (int)s.a[k] * sc;
         s.a[k] = sh > 0 ? (int16_t)(v * (1 << sh)) : (int16_t)((v + (1 << (-sh - 1))) >> -sh);
       }
     } else if (dst4) {
-      tx_fwd_dst4(lgw + bd - 9, s.a, s.b);
+      tx_fwd_dst4(st.fwd1, s.a, s.b);
       __syncthreads();
-      tx_fwd_dst4(lgh + 6, s.b, s.a);
+      tx_fwd_dst4(st.fwd2, s.b, s.a);
     } else {
-      tx_fwd_1d(s.mh, w, shift1, h, false, s.a, s.b);
+      tx_fwd_1d(s.mh, w, st.fwd1, h, false, s.a, s.b);
       __syncthreads();
-      tx_fwd_1d(s.mv, h, shift2, w, true, s.b, s.a);
+      tx_fwd_1d(s.mv, h, st.fwd2, w, true, s.b, s.a);
     }
     __syncthreads();
     // s.a[ky*S + kx] = coefficients
@@ -304,12 +214,10 @@ __device__ __forceinline__ int residual_job(TxShared &s, int bi, const PicView &
           lv[i] = s.a[(i >> lw) * TX_S + (i & (w - 1))];
       return -1;
     }
-    // QuantFast (rdo_quant.cc:156-195)
-    const int qshift = 14 + qpb / 6 + tshift + (bias ? 7 : 0);
-    const int qscale = kFwdQuantScales[qpb % 6] * (bias ? 181 : 1);
-    const long long qoff = (long long)((intra_pic ? 171ull : 85ull) << (qshift - 9));
-    // levels -> s.b, rounding remainders -> s.dl, coefficients stay in s.a
-    bool use_rdoq = RQN > 4 && (b.intra_pic & XVC_TXF_RDOQ) != 0;
+    // QuantFast (rdo_quant.cc:156-195): levels -> s.b, rounding remainders -> s.dl,
+    // coefficients stay in s.a
+    const BlockQuant q = quant();
+    bool use_rdoq = RQN > 4 && fl.rdoq;
     if (use_rdoq && (w == 2 || h == 2) && (rq_prm[bi].flags & XVC_RDOQ_NO_2X2))
       use_rdoq = false;  // rdo_quant.cc:208-216: 2-wide blocks fall back to QuantFast
     if (RQN > 4 && use_rdoq) {
@@ -326,17 +234,17 @@ __device__ __forceinline__ int residual_job(TxShared &s, int bi, const PicView &
         int n_rq;
         if (RQN >= 1024 && rq4_takes(64, w, h, scan_order)) {
           // four lanes per sub-block (k_rdoq4.h), four units per lane beyond sixteen sub-blocks
-          rq_stage_costs(&rq_ctx[prm.ctx_index], rq->ctx_bits, (int)threadIdx.x, 64);
+          rq_stage_costs(kEntropyBits, &rq_ctx[prm.ctx_index], rq->ctx_bits, (int)threadIdx.x, 64);
           wave_sync();
           if (rq4_needs_nr4(w, h))
-            n_rq = wave_rdoq4<64, 4>(*rq, (int)threadIdx.x, bd, w, h, b.qp, b.comp == 0, sign_hide,
-                                     prm, cf_at, lv_at);
+            n_rq = wave_rdoq4<64, 4>(*rq, (int)threadIdx.x, q, w, h, b.comp == 0, sign_hide, prm,
+                                     cf_at, lv_at);
           else
-            n_rq = wave_rdoq4<64, 1>(*rq, (int)threadIdx.x, bd, w, h, b.qp, b.comp == 0, sign_hide,
-                                     prm, cf_at, lv_at);
+            n_rq = wave_rdoq4<64, 1>(*rq, (int)threadIdx.x, q, w, h, b.comp == 0, sign_hide, prm,
+                                     cf_at, lv_at);
         } else {
-          n_rq = wave_rdoq<64>(*rq, (int)threadIdx.x, bd, w, h, b.qp, b.comp == 0, scan_order,
-                               sign_hide, rq_ctx[prm.ctx_index], prm, cf_at, lv_at);
+          n_rq = wave_rdoq<64>(*rq, (int)threadIdx.x, q, w, h, b.comp == 0, scan_order, sign_hide,
+                               rq_ctx[prm.ctx_index], prm, cf_at, lv_at);
         }
         if (threadIdx.x == 0) s.nnz = n_rq;
       }
@@ -345,15 +253,11 @@ __device__ __forceinline__ int residual_job(TxShared &s, int bi, const PicView &
     int local = 0;
     if (!use_rdoq)
     for (int i = threadIdx.x; i < w * h; i += TX_THREADS) {
-      const int y = i >> lw, x = i & (w - 1);
-      const int v = s.a[y * TX_S + x];
-      const int sign = v < 0 ? -1 : 1;
-      const long long abs_coeff = d_abs(v);
-      const int level = (int)(((abs_coeff * qscale) + qoff) >> qshift);
-      local += level != 0;
-      s.b[y * TX_S + x] = (int16_t)d_clip3(level * sign, -32768, 32767);
-      s.dl[y * TX_S + x] =
-          (int16_t)(((abs_coeff * qscale) - ((long long)level << qshift)) >> (qshift - 8));
+      const int k = (i >> lw) * TX_S + (i & (w - 1));
+      const BlockQuant::Fast f = q.fast(s.a[k]);
+      local += f.level != 0;
+      s.b[k] = f.level;
+      s.dl[k] = f.rem;
     }
     local = group_sum<64>(local);
     if ((threadIdx.x & 63) == 0 && local) atomicAdd(&s.nnz, local);
@@ -424,30 +328,17 @@ __device__ __forceinline__ int residual_job(TxShared &s, int bi, const PicView &
   const bool dc_only = nnz == 1 && s.b[0] != 0;  // transform_encoder.cc:241
 
   // Quantize::Inverse (quantize.cc:94-125): levels in s.b -> s.a
-  {
-    const int shift = 6 - tshift + (bias ? 8 : 0);
-    const int scale = (kInvQuantScales[qpb % 6] << (qpb / 6)) * (bias ? 181 : 1);
-    for (int i = threadIdx.x; i < w * h; i += TX_THREADS) {
-      const int y = i >> lw, x = i & (w - 1);
-      const int prod = (int)s.b[y * TX_S + x] * scale;
-      int cf;
-      if (shift > 0)
-        cf = (prod + (1 << (shift - 1))) >> shift;
-      else
-        cf = (int)((unsigned)prod << -shift);
-      s.a[y * TX_S + x] = (int16_t)d_clip3(cf, -32768, 32767);
-    }
-    __syncthreads();
+  const BlockQuant q = quant();
+  for (int i = threadIdx.x; i < w * h; i += TX_THREADS) {
+    const int k = (i >> lw) * TX_S + (i & (w - 1));
+    s.a[k] = (int16_t)q.dequant(s.b[k]);
   }
+  __syncthreads();
   // InverseTransform::Transform (transform.cc:83-182) -> residual in s.a
   {
-    const int shift1 = 7 + (b.tx_ver == XVC_TX_DCT2_LOW ? 0 : 2);
-    const int shift2 = 20 - bd + (b.tx_hor == XVC_TX_DCT2_LOW ? 0 : 2);
-    const bool dct2_both =
-        (b.tx_ver == XVC_TX_DEFAULT || b.tx_ver == XVC_TX_DCT2 || b.tx_ver == XVC_TX_DCT2_LOW) &&
-        (b.tx_hor == XVC_TX_DEFAULT || b.tx_hor == XVC_TX_DCT2 || b.tx_hor == XVC_TX_DCT2_LOW);
+    const TxStageShifts st = shifts();
     if (skip) {  // InverseTransform::TransformSkip, transform.cc:184-215
-      const int sh = tshift + (bias ? 7 : 0), sc = bias ? 181 : 1;
+      const int sh = q.tshift + (q.bias ? 7 : 0), sc = q.bias ? 181 : 1;
       for (int i = threadIdx.x; i < w * h; i += TX_THREADS) {
         const int k = (i >> lw) * TX_S + (i & (w - 1));
         const int v = (int)s.a[k] * sc;
@@ -455,19 +346,19 @@ __device__ __forceinline__ int residual_job(TxShared &s, int bi, const PicView &
                         : (int16_t)((uint32_t)v << -sh);
       }
     } else if (dst4) {
-      tx_inv_dst4(7, s.a, s.b);
+      tx_inv_dst4(st.inv1, s.a, s.b);
       __syncthreads();
-      tx_inv_dst4(20 - bd, s.b, s.a);
-    } else if (dc_only && dct2_both) {  // InvDct2Dc, transform.cc:279-291
+      tx_inv_dst4(st.inv2, s.b, s.a);
+    } else if (dc_only && st.dct2_both) {  // InvDct2Dc, transform.cc:279-291
       const int sh = 14 - bd, add = 1 << (sh - 1);
       const int16_t cf = (int16_t)(((((int)s.a[0] + 1) >> 1) + add) >> sh);
       __syncthreads();
       for (int i = threadIdx.x; i < w * h; i += TX_THREADS)
         s.a[(i >> lw) * TX_S + (i & (w - 1))] = cf;
     } else {
-      tx_inv_1d(s.mv, h, shift1, w, true, s.a, s.b);
+      tx_inv_1d(s.mv, h, st.inv1, w, true, s.a, s.b);
       __syncthreads();
-      tx_inv_1d(s.mh, w, shift2, h, false, s.b, s.a);
+      tx_inv_1d(s.mh, w, st.inv2, h, false, s.b, s.a);
     }
     __syncthreads();
   }

@@ -23,6 +23,8 @@
 #include "dev_tables.h"
 #include "k_me.h"
 #include "k_me2.h"
+#include "k_quant.h"
+#include "k_rdoq.h"
 #include "k_tx.h"
 #include "xvcgpu_internal.h"
 
@@ -194,10 +196,11 @@ __device__ __forceinline__ int tx2_job(Tx2Shared &sh, const xvcgpu_tx_block &b, 
   const int16_t *Mh = tx_tables + offh, *Mv = tx_tables + offv;
   const int16_t *MhT = tx_tables_t + offh, *MvT = tx_tables_t + offv;
 
-  int qpb = b.qp + 6 * (bd - 8);
-  qpb = qpb > 0 ? qpb : 0;
-  const bool bias = ((lgw + lgh) & 1) != 0;
-  const int tshift = 15 - bd - ((lgw + lgh) >> 1);
+  // (the quantiser's constants and the stage shifts, k_quant.h, are derived in front of each
+  // use, not here: in the half-wave instances `b` is a per-lane value and what is derived from
+  // it up here stays in vector registers across the loads - inv_cu_pairs_kernel lost a wave)
+  const TxBlockFlags fl = tx_block_flags(b.intra_pic);
+  auto quant = [&]() { return block_quant(w, h, b.qp, bd, fl.intra_pic); };
   const int n_el = w * h;
   constexpr int NE = FW * FH;   // > 0: n_el at compile time, lane_loop unrolls the trips
 
@@ -223,22 +226,19 @@ __device__ __forceinline__ int tx2_job(Tx2Shared &sh, const xvcgpu_tx_block &b, 
     });
     wave_sync();
     ME2_TRACE(2);
-    const int shift1 = lgw + bd - 9 + (b.tx_hor == XVC_TX_DCT2_LOW ? 0 : 2);
-    const int shift2 = lgh + 6 + (b.tx_ver == XVC_TX_DCT2_LOW ? 0 : 2);
     // fwd 1: T[k][y] (w rows of h), fwd 2: C[x][k2] (w rows of h)
-    tx2_stage_dispatch<false, G>(w, Mh, s.r, w, h, 1 << (shift1 - 1), shift1, s.t);
+    const TxStageShifts st = tx_stage_shifts(b.tx_hor, b.tx_ver, lgw, lgh, bd);
+    tx2_stage_dispatch<false, G>(w, Mh, s.r, w, h, 1 << (st.fwd1 - 1), st.fwd1, s.t);
     wave_sync();
     ME2_TRACE(3);
-    tx2_stage_dispatch<false, G>(h, s.t, Mv, w, h, 1 << (shift2 - 1), shift2, s.c);
+    tx2_stage_dispatch<false, G>(h, s.t, Mv, w, h, 1 << (st.fwd2 - 1), st.fwd2, s.c);
     wave_sync();
     ME2_TRACE(4);
     if (MODE == TX_MODE_FWD) {
       if (fc && fc->cls) {
         // the classification pass of the RDO quantiser (rdoq_classify_kernel, k_rdoq.h)
         // on the coefficients at hand: does any of them quantise to a level at all?
-        const int fq_shift = 14 + qpb / 6 + tshift + (bias ? 7 : 0);
-        const int fq_scale = kFwdQuantScales[qpb % 6] * (bias ? 181 : 1);
-        const long long fq_offset = 1ll << (fq_shift - 1);
+        const BlockQuant q = quant();
         bool any = false;
         RqProveLds *pv = fc->pv;
         const int grp = ME2_LANE / G;
@@ -251,7 +251,7 @@ __device__ __forceinline__ int tx2_job(Tx2Shared &sh, const xvcgpu_tx_block &b, 
         }
         lane_loop<NE, G>(lane, n_el, [&](int i) {
           const int a = (short)d_abs((int)s.c[i]);
-          const bool nz = (short)(int)((((long long)a * fq_scale) + fq_offset) >> fq_shift) != 0;
+          const bool nz = q.codes(a);
           any |= nz;
           if (pv && nz) {   // a candidate of the all-zero proof: C[x][y] at s.c[x * h + y]
             const int slot = atomicAdd(&pv->n[grp], 1);
@@ -284,15 +284,12 @@ __device__ __forceinline__ int tx2_job(Tx2Shared &sh, const xvcgpu_tx_block &b, 
     }
     // QuantFast (rdo_quant.cc:156-201): levels -> s.r, rounding remainders
     // -> s.t, the coefficients stay in s.c (same [x][k2] layout)
-    const bool intra_pic = (b.intra_pic & XVC_TXF_INTRA_PIC) != 0;
-    const bool sign_hide = !(b.intra_pic & XVC_TXF_NO_SIGN_HIDING);
-    const int scan_order = (b.intra_pic >> XVC_TXF_SCAN_SHIFT) & 3;
-    const int qshift = 14 + qpb / 6 + tshift + (bias ? 7 : 0);
-    const int qscale = kFwdQuantScales[qpb % 6] * (bias ? 181 : 1);
-    const long long qoff = (long long)((intra_pic ? 171ull : 85ull) << (qshift - 9));
+    const bool sign_hide = fl.sign_hide;
+    const int scan_order = fl.scan_order;
     // (with G = 32 both halves of the wave take the same branch: the caller
     // gives the two blocks the same flags)
-    const bool use_rdoq = RDOQ && (b.intra_pic & XVC_TXF_RDOQ) != 0;
+    const bool use_rdoq = RDOQ && fl.rdoq;
+    const BlockQuant q = quant();
     if (RDOQ && use_rdoq) {
       // RdoQuant::QuantRdo (rdo_quant.cc:203-446): levels -> s.r, same layout
       const xvcgpu_rdoq_params prm = rq_prm[bi];
@@ -302,12 +299,11 @@ __device__ __forceinline__ int tx2_job(Tx2Shared &sh, const xvcgpu_tx_block &b, 
       auto lv_at = [lvp, h](int x, int y) { return lvp + x * h + y; };
       if (G == 64 && rq4_takes(64, w, h, scan_order)) {
         // four lanes per sub-block (k_rdoq4.h): the whole wave on this block's walk
-        rq_stage_costs(&rq_ctx[prm.ctx_index], rq->ctx_bits, lane, 64);
+        rq_stage_costs(kEntropyBits, &rq_ctx[prm.ctx_index], rq->ctx_bits, lane, 64);
         wave_sync();
-        nnz = wave_rdoq4<64, 1>(*rq, lane, bd, w, h, b.qp, b.comp == 0, sign_hide, prm, cf_at,
-                                lv_at);
+        nnz = wave_rdoq4<64, 1>(*rq, lane, q, w, h, b.comp == 0, sign_hide, prm, cf_at, lv_at);
       } else {
-        nnz = wave_rdoq<G>(*rq, lane, bd, w, h, b.qp, b.comp == 0, scan_order, sign_hide,
+        nnz = wave_rdoq<G>(*rq, lane, q, w, h, b.comp == 0, scan_order, sign_hide,
                            rq_ctx[prm.ctx_index], prm, cf_at, lv_at);
       }
       wave_sync();
@@ -315,13 +311,10 @@ __device__ __forceinline__ int tx2_job(Tx2Shared &sh, const xvcgpu_tx_block &b, 
     int local = 0;
     if (!use_rdoq) {
     for (int i = lane; i < n_el; i += G) {
-      const int v = s.c[i];
-      const int sign = v < 0 ? -1 : 1;
-      const long long abs_coeff = d_abs(v);
-      const int level = (int)(((abs_coeff * qscale) + qoff) >> qshift);
-      local += level != 0;
-      s.r[i] = (int16_t)d_clip3(level * sign, -32768, 32767);
-      s.t[i] = (int16_t)(((abs_coeff * qscale) - ((long long)level << qshift)) >> (qshift - 8));
+      const BlockQuant::Fast f = q.fast(s.c[i]);
+      local += f.level != 0;
+      s.r[i] = f.level;
+      s.t[i] = f.rem;
     }
     nnz = tx2_group_add<G>(local);
     }
@@ -388,24 +381,13 @@ __device__ __forceinline__ int tx2_job(Tx2Shared &sh, const xvcgpu_tx_block &b, 
   wave_sync();
   ME2_TRACE(5);
   // Quantize::Inverse (quantize.cc:94-125): levels in s.r -> s.c
-  {
-    const int shift = 6 - tshift + (bias ? 8 : 0);
-    const int scale = (kInvQuantScales[qpb % 6] << (qpb / 6)) * (bias ? 181 : 1);
-    lane_loop<NE, G>(lane, n_el, [&](int i) {
-      const int prod = (int)s.r[i] * scale;
-      int cf;
-      if (shift > 0) cf = (prod + (1 << (shift - 1))) >> shift;
-      else cf = (int)((unsigned)prod << -shift);
-      s.c[i] = (int16_t)d_clip3(cf, -32768, 32767);
-    });
-  }
+  const BlockQuant q = quant();
+  lane_loop<NE, G>(lane, n_el, [&](int i) { s.c[i] = (int16_t)q.dequant(s.r[i]); });
   wave_sync();
   ME2_TRACE(6);
   const int smax = (1 << bd) - 1;
-  const bool dct2_both =
-      (b.tx_ver == XVC_TX_DEFAULT || b.tx_ver == XVC_TX_DCT2 || b.tx_ver == XVC_TX_DCT2_LOW) &&
-      (b.tx_hor == XVC_TX_DEFAULT || b.tx_hor == XVC_TX_DCT2 || b.tx_hor == XVC_TX_DCT2_LOW);
-  if (dc_only && dct2_both) {  // InvDct2Dc, transform.cc:279-291
+  const TxStageShifts st = tx_stage_shifts(b.tx_hor, b.tx_ver, lgw, lgh, bd);
+  if (dc_only && st.dct2_both) {  // InvDct2Dc, transform.cc:279-291
     const int sh = 14 - bd, add = 1 << (sh - 1);
     const int cf = (int16_t)(((((int)s.c[0] + 1) >> 1) + add) >> sh);
     lane_loop<NE, 4 * G>(lane * 4, n_el, [&](int i) {
@@ -424,15 +406,11 @@ __device__ __forceinline__ int tx2_job(Tx2Shared &sh, const xvcgpu_tx_block &b, 
     return nnz;
   }
   // inverse: U[r][x] (h rows of w) into s.r, then residual rows into s.t
-  {
-    const int shift1 = 7 + (b.tx_ver == XVC_TX_DCT2_LOW ? 0 : 2);
-    const int shift2 = 20 - bd + (b.tx_hor == XVC_TX_DCT2_LOW ? 0 : 2);
-    tx2_stage_dispatch<true, G>(h, MvT, s.c, h, w, 1 << (shift1 - 1), shift1, s.r);
-    wave_sync();
-    tx2_stage_dispatch<true, G>(w, s.r, MhT, h, w, 1 << (shift2 - 1), shift2, s.t);
-    wave_sync();
-    ME2_TRACE(7);
-  }
+  tx2_stage_dispatch<true, G>(h, MvT, s.c, h, w, 1 << (st.inv1 - 1), st.inv1, s.r);
+  wave_sync();
+  tx2_stage_dispatch<true, G>(w, s.r, MhT, h, w, 1 << (st.inv2 - 1), st.inv2, s.t);
+  wave_sync();
+  ME2_TRACE(7);
   // SampleBuffer::AddClip
   lane_loop<NE, 4 * G>(lane * 4, n_el, [&](int i) {
     const int y = i >> lw, x = i & (w - 1);
