@@ -1317,6 +1317,65 @@ xvcgpu_status xvcgpu_frame_pass_bi_refs(
     xvcgpu_ctx *ctx, const xvcgpu_frame_pass_bi_refs_args *a,
     const xvcgpu_me_plan *const plans[2][XVC_CS_MAX_REFS], int phases);
 
+/* ---- the frame passes with adaptive QP ------------------------------------- *
+ * CuEncoder::EncodeCtu (cu_encoder.cc:92-97) gives every CTU its own QP, pic_qp +
+ * CalcDeltaQpFromVariance (cu_encoder.cc:308-363; on by default, encoder_settings.h:89-90),
+ * and every CU below it runs with that Qp object: its lambda_sqrt in the search, its
+ * quantiser step, its RDOQ constants, its QP in the deblocking filter.  Here the QP map is
+ * derived on the device from xvcgpu_variance_map's CTU statistic through the thresholds of
+ * the table (xvcgpu_types.h: xvcgpu_aqp_table) and written into the job arrays the passes
+ * read anyway; nothing is read back.
+ *
+ * xvcgpu_aqp_apply: one thread per CU, 256-thread workgroups, plain loads and stores.  CU i
+ * (origin d_me[0][i].x, .y; n_me = 1 .. 2 * XVC_CS_MAX_REFS job arrays of the same CUs)
+ * lies in CTU (y / ctu_size) * ctus_per_row + x / ctu_size; delta = XVC_AQP_DELTA_MIN +
+ * #{k : d_ctu_var[ctu] >= var_min[k]}.  With the table's entry of that delta it writes
+ * lambda16 of job i in every d_me array, qp of the transform blocks d_luma_tx_index[i] + 0,
+ * 1, 2 (qp_y, qp_c, qp_c), lambda and rd_factor of the same three records of d_rdoq_params
+ * (NULL: QuantFast, nothing to write; ctx_index and flags stay), {qp_y, qp_c} into
+ * d_cu_qp[2 i] and the delta into d_ctu_dqp[ctu] (NULL: not wanted; a CTU that holds no CU
+ * origin is not written) - and no other byte of those records.  The jobs must lie inside
+ * the picture d_ctu_var was computed for.
+ * xvcgpu_cu_info_set_qp: qp_y / qp_c of d_cus_own[i] = d_cu_qp[2 i], [2 i + 1], i < n: the
+ * correction behind xvcgpu_cu_info_from_me / xvcgpu_cu_info_from_choice_refs, which write the
+ * picture's scalar QP.
+ *
+ * xvcgpu_frame_pass_aqp: xvcgpu_frame_pass (plan NULL) or xvcgpu_frame_pass_planned with, in
+ * front of the search, xvcgpu_variance_map(a->orig -> q->d_var16, q->d_ctu_var) and
+ * xvcgpu_aqp_apply (a->d_me, a->d_tx, a->d_rdoq_params, a->d_luma_tx_index), and between the
+ * CU records and the tail xvcgpu_cu_info_set_qp(a->d_cus_own).  a->d_me, a->d_tx and
+ * a->d_rdoq_params are written (device memory of the caller's, const in the block for the
+ * flat pass's sake); a->qp_y and a->qp_c are not read for anything that stays.  The RDOQ
+ * context snapshot stays the caller's (the picture-initial one of pic_qp).  A plan reads
+ * lambda16 from a->d_me at search time (it keeps job indices, no copy of the jobs), so
+ * the plan of the flat pass serves.
+ * xvcgpu_frame_pass_bi_refs_aqp: the same around xvcgpu_frame_pass_bi_refs, over every
+ * b->d_me[l][r] of the lists (re-used entries too: their lambda16 prices list 1's side; the
+ * refinement jobs are copied from them behind the apply launch).
+ * Forms: those with a prediction picture and d_tx - FWD_TRANSFORM, RESIDUAL, RESIDUAL_RDOQ.
+ * RECON_FROM_ME and FWD_FROM_ME build their transform blocks from the scalar QP inside their
+ * kernels (and FWD_FROM_ME's all-zero proof is keyed on one QP): refused, naming `form`.
+ * Whole pictures with XVC_FP_ENCODE only; no multi-picture form.  Every check - those of the
+ * flat pass included - happens before the first launch (XVCGPU_INVALID_ARGUMENT, the message
+ * names the field: form, a missing array of q, the row ranges, ctu_size, ctus_per_row
+ * against the width of orig); after them the call only enqueues: no synchronisation, no
+ * allocation.  A table of strength 0 (every threshold above pic_qp's delta 0) gives the flat
+ * pass's bytes. */
+xvcgpu_status xvcgpu_aqp_apply(xvcgpu_ctx *ctx, const xvcgpu_aqp_table *table,
+                               const uint64_t *d_ctu_var, xvcgpu_me_block *const *d_me,
+                               int n_me, xvcgpu_tx_block *d_tx,
+                               xvcgpu_rdoq_params *d_rdoq_params,
+                               const int32_t *d_luma_tx_index, int n_cus, int8_t *d_cu_qp,
+                               int8_t *d_ctu_dqp);
+xvcgpu_status xvcgpu_cu_info_set_qp(xvcgpu_ctx *ctx, xvcgpu_cu_info *d_cus_own,
+                                    const int8_t *d_cu_qp, int n);
+xvcgpu_status xvcgpu_frame_pass_aqp(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_args *a,
+                                    const xvcgpu_aqp_args *q, const xvcgpu_me_plan *plan,
+                                    int phases);
+xvcgpu_status xvcgpu_frame_pass_bi_refs_aqp(
+    xvcgpu_ctx *ctx, const xvcgpu_frame_pass_bi_refs_args *b, const xvcgpu_aqp_args *q,
+    const xvcgpu_me_plan *const plans[2][XVC_CS_MAX_REFS], int phases);
+
 /* ---- tables (host side, no GPU needed) ---------------------------------- *
  * The 8-bit-fraction transform matrices the kernels use (transform_data.cc:
  * 109-796), for table-equality tests. out: size*size int16 row-major. */

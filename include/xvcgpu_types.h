@@ -665,6 +665,51 @@ typedef struct xvcgpu_frame_pass_bi_refs_args {
   xvcgpu_inter_block *d_inter;              /* 3 * n_cus: the CUs' prediction jobs Y, U, V */
 } xvcgpu_frame_pass_bi_refs_args;
 
+/* ---- adaptive QP: a QP per CTU, derived and applied on the device -------------- *
+ * CuEncoder::EncodeCtu (cu_encoder.cc:92-97) codes every CTU at pic_qp +
+ * CalcDeltaQpFromVariance(ctu) (cu_encoder.cc:308-363), the reference's default
+ * (adaptive_qp = 2, aqp_strength = 13: encoder_settings.h:89-90).  The delta is
+ * int(kStrength * (1.5 * log(v) - 15 - 2 * (bitdepth - 8))) clipped to -3 .. 7 with v the
+ * CTU statistic of xvcgpu_variance_map; it does not decrease in v, so ten thresholds say
+ * it without a logarithm: delta = XVC_AQP_DELTA_MIN + #{k : v >= var_min[k]}, var_min[k]
+ * the smallest v >= 1 whose delta is >= XVC_AQP_DELTA_MIN + 1 + k (UINT64_MAX: none).
+ * Per delta d (index d - XVC_AQP_DELTA_MIN) the table holds what a CU coded at that QP
+ * reads: qp_y = clip(pic_qp + d, 0, 63) (PictureData::GetQp, picture_data.h:51-53), its
+ * chroma QP, and the constants of a picture with recalculate_lambda, lambda = 0.57 *
+ * 2^((qp_y - 12) / 3) (picture_data.cc:94-106): the search's lambda16
+ * (xvcgpu_me_block.lambda16) and RDOQ's lambda / rd_factor per component
+ * (xvcgpu_rdoq_params).  Filled by the host once per pass object
+ * (xvc_gpu::AdaptiveQp::Table, pipeline.aqp_table: the same bytes). */
+#define XVC_AQP_DELTA_MIN (-3)
+#define XVC_AQP_DELTAS 11
+typedef struct xvcgpu_aqp_table {
+  int32_t pic_qp;
+  int32_t ctu_size;                         /* 16, 32, 64 or 128                       */
+  int32_t ctus_per_row;                     /* ceil(picture width / ctu_size)          */
+  int32_t reserved;
+  uint64_t var_min[XVC_AQP_DELTAS - 1];
+  int8_t qp_y[XVC_AQP_DELTAS];
+  int8_t qp_c[XVC_AQP_DELTAS];
+  uint8_t reserved2[2];
+  uint32_t lambda16[XVC_AQP_DELTAS];
+  uint32_t reserved3;
+  int64_t rdoq_lambda[XVC_AQP_DELTAS][3];   /* [delta][Y, U, V]                        */
+  int64_t rdoq_rd_factor[XVC_AQP_DELTAS][3];
+} xvcgpu_aqp_table;
+
+/* What the adaptive-QP frame passes (xvcgpu_frame_pass_aqp, xvcgpu_frame_pass_bi_refs_aqp)
+ * take beside the flat pass's block: the table and four arrays of the caller's, written by
+ * every call.  d_var16: ceil(w / 16) * ceil(h / 16) uint64 (xvcgpu_variance_map); d_ctu_var:
+ * one uint64 per CTU; d_ctu_dqp: one int8 per CTU, the delta (may be NULL); d_cu_qp: two
+ * int8 per CU of the pass, {qp_y, qp_c}. */
+typedef struct xvcgpu_aqp_args {
+  xvcgpu_aqp_table table;
+  uint64_t *d_var16;
+  uint64_t *d_ctu_var;
+  int8_t *d_ctu_dqp;
+  int8_t *d_cu_qp;
+} xvcgpu_aqp_args;
+
 /* One job of xvcgpu_affine_me_batch: InterSearch::MotionEstAffine for one
  * (list, ref_idx) of a CU (inter_search.cc:664-749).  Vectors are {x, y} in
  * 1/16 pel; mvp / bootstrap / other_mv are MotionVector3 (top-left, top-right,

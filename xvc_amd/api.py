@@ -169,6 +169,27 @@ class FramePassBiRefsArgs(C.Structure):
                 ("d_bi_slots", C.c_void_p), ("d_choice", C.c_void_p), ("d_inter", C.c_void_p)]
 
 
+AQP_DELTA_MIN, AQP_DELTAS = -3, 11    # XVC_AQP_DELTA_MIN, XVC_AQP_DELTAS
+
+
+class AqpTable(C.Structure):
+    """xvcgpu_aqp_table (include/xvcgpu_types.h); filled by pipeline.aqp_table"""
+    _fields_ = [("pic_qp", C.c_int32), ("ctu_size", C.c_int32), ("ctus_per_row", C.c_int32),
+                ("reserved", C.c_int32), ("var_min", C.c_uint64 * (AQP_DELTAS - 1)),
+                ("qp_y", C.c_int8 * AQP_DELTAS), ("qp_c", C.c_int8 * AQP_DELTAS),
+                ("reserved2", C.c_uint8 * 2), ("lambda16", C.c_uint32 * AQP_DELTAS),
+                ("reserved3", C.c_uint32), ("rdoq_lambda", (C.c_int64 * 3) * AQP_DELTAS),
+                ("rdoq_rd_factor", (C.c_int64 * 3) * AQP_DELTAS)]
+
+
+class AqpArgs(C.Structure):
+    """xvcgpu_aqp_args (include/xvcgpu_types.h)"""
+    _fields_ = [("table", AqpTable), ("d_var16", C.c_void_p), ("d_ctu_var", C.c_void_p),
+                ("d_ctu_dqp", C.c_void_p), ("d_cu_qp", C.c_void_p)]
+
+
+assert C.sizeof(AqpTable) == 696 and C.sizeof(AqpArgs) == 728
+
 # xvcgpu_fp_bi_refs_result: what SearchMotion ends with for one CU of a B picture
 FP_BI_REFS_RESULT_DTYPE = np.dtype([
     ("inter_dir", "<i4"), ("search_list", "<i4"), ("ref_idx", "<i4", (2,)),
@@ -234,6 +255,8 @@ SYMBOLS = [
     "xvcgpu_me_search_planned", "xvcgpu_frame_pass_planned",
     "xvcgpu_fp_bi_refs_uni_fold", "xvcgpu_fp_bi_refs_choice", "xvcgpu_cu_info_from_choice_refs",
     "xvcgpu_bipred_search_refs_planned", "xvcgpu_frame_pass_bi_refs",
+    "xvcgpu_aqp_apply", "xvcgpu_cu_info_set_qp", "xvcgpu_frame_pass_aqp",
+    "xvcgpu_frame_pass_bi_refs_aqp",
 ]
 
 _vp = C.c_void_p
@@ -444,6 +467,12 @@ def load_library(allow_missing=()):
         "xvcgpu_cu_info_from_choice_refs": [_vp, C.POINTER(FramePassBiRefsArgs)],
         "xvcgpu_bipred_search_refs_planned": [_vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp],
         "xvcgpu_frame_pass_bi_refs": [_vp, C.POINTER(FramePassBiRefsArgs), _vp, C.c_int],
+        "xvcgpu_aqp_apply": [_vp, C.POINTER(AqpTable), _vp, C.POINTER(_vp), C.c_int, _vp, _vp, _vp,
+                             C.c_int, _vp, _vp],
+        "xvcgpu_cu_info_set_qp": [_vp, _vp, _vp, C.c_int],
+        "xvcgpu_frame_pass_aqp": [_vp, C.POINTER(FramePassArgs), C.POINTER(AqpArgs), _vp, C.c_int],
+        "xvcgpu_frame_pass_bi_refs_aqp": [_vp, C.POINTER(FramePassBiRefsArgs), C.POINTER(AqpArgs),
+                                          _vp, C.c_int],
     }
     if "xvcgpu_me_plan_destroy" not in allow_missing or hasattr(lib, "xvcgpu_me_plan_destroy"):
         lib.xvcgpu_me_plan_destroy.restype = None

@@ -32,6 +32,7 @@
 #include "k_cu_state.h"
 #include "k_cs_engine.h"
 #include "k_fp_bi_refs.h"
+#include "k_aqp.h"
 #include "xvcgpu_internal.h"
 
 namespace {
@@ -2627,15 +2628,113 @@ static xvcgpu_status fp_search(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_args *a,
       d_me, a->n_cus, d_results, a->max_block_size);
 }
 
-// resolve, search, the form's launches, tail.  plan: null = xvcgpu_frame_pass
+/* ---- adaptive QP (k_aqp.h) ---- */
+static xvcgpu_status aqp_apply_launch(xvcgpu_ctx *ctx, const xvcgpu_aqp_table *t,
+                                      const uint64_t *d_ctu_var, int n_ctus,
+                                      xvcgpu_me_block *const *d_me, int n_me,
+                                      xvcgpu_tx_block *d_tx, xvcgpu_rdoq_params *d_rdoq_params,
+                                      const int32_t *d_luma_tx_index, int n_cus, int8_t *d_cu_qp,
+                                      int8_t *d_ctu_dqp) {
+  if (!ctx || !t || n_cus < 0 || n_me < 1 || n_me > 2 * XVC_CS_MAX_REFS || !d_me)
+    return XVCGPU_INVALID_ARGUMENT;
+  if (t->ctu_size != 16 && t->ctu_size != 32 && t->ctu_size != 64 && t->ctu_size != 128)
+    return fail(ctx, XVCGPU_INVALID_ARGUMENT, "aqp_apply: ctu_size");
+  if (t->ctus_per_row < 1) return fail(ctx, XVCGPU_INVALID_ARGUMENT, "aqp_apply: ctus_per_row");
+  AqpMeArrays me = {};
+  for (int k = 0; k < n_me; k++) {
+    if (!d_me[k]) return fail(ctx, XVCGPU_INVALID_ARGUMENT, "aqp_apply: d_me");
+    me.p[k] = d_me[k];
+  }
+  if (n_cus && (!d_ctu_var || !d_tx || !d_luma_tx_index || !d_cu_qp))
+    return fail(ctx, XVCGPU_INVALID_ARGUMENT,
+                "aqp_apply: d_ctu_var, d_tx, d_luma_tx_index and d_cu_qp");
+  if (n_cus == 0) return XVCGPU_OK;
+  hipLaunchKernelGGL(aqp_apply_kernel, dim3((n_cus + 255) / 256), dim3(256), 0, ctx->stream, *t,
+                     reinterpret_cast<const unsigned long long *>(d_ctu_var), n_ctus, me, n_me,
+                     d_tx, d_rdoq_params, d_luma_tx_index, n_cus, d_cu_qp, d_ctu_dqp);
+  CHECK_LAUNCH(ctx, "aqp_apply");
+  return XVCGPU_OK;
+}
+
+xvcgpu_status xvcgpu_aqp_apply(xvcgpu_ctx *ctx, const xvcgpu_aqp_table *table,
+                               const uint64_t *d_ctu_var, xvcgpu_me_block *const *d_me,
+                               int n_me, xvcgpu_tx_block *d_tx,
+                               xvcgpu_rdoq_params *d_rdoq_params,
+                               const int32_t *d_luma_tx_index, int n_cus, int8_t *d_cu_qp,
+                               int8_t *d_ctu_dqp) {
+  // (the caller's word that the jobs lie inside the picture of d_ctu_var: no clamp)
+  return aqp_apply_launch(ctx, table, d_ctu_var, 0x7fffffff, d_me, n_me, d_tx, d_rdoq_params,
+                          d_luma_tx_index, n_cus, d_cu_qp, d_ctu_dqp);
+}
+
+xvcgpu_status xvcgpu_cu_info_set_qp(xvcgpu_ctx *ctx, xvcgpu_cu_info *d_cus_own,
+                                    const int8_t *d_cu_qp, int n) {
+  if (!ctx || n < 0 || (n && (!d_cus_own || !d_cu_qp))) return XVCGPU_INVALID_ARGUMENT;
+  if (n == 0) return XVCGPU_OK;
+  hipLaunchKernelGGL(cu_info_set_qp_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream,
+                     d_cus_own, d_cu_qp, n);
+  CHECK_LAUNCH(ctx, "cu_info_set_qp");
+  return XVCGPU_OK;
+}
+
+// What an adaptive-QP pass asks beyond the flat pass's checks (frame_pass_resolve ran:
+// a, a->rec are there and, with a form, a->orig): every refusal names its field, nothing
+// is enqueued
+static xvcgpu_status fp_aqp_check(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_args *a,
+                                  const xvcgpu_aqp_args *q, int phases) {
+#define FPQ_NEED(cond, what) \
+  if (!(cond)) return fail(ctx, XVCGPU_INVALID_ARGUMENT, "frame_pass_aqp: " what)
+  FPQ_NEED(phases & XVC_FP_ENCODE, "phases: the QP map is applied in front of XVC_FP_ENCODE");
+  FPQ_NEED(a->n_cus == a->n_cus_total && a->db_y_begin == 0 && a->db_y_end >= a->rec->h &&
+               a->dbh_y_end >= a->rec->h && a->ssd_y_begin == 0 && a->ssd_y_end >= a->rec->h,
+           "whole pictures only (no row shard)");
+  if (a->n_cus <= 0) return XVCGPU_OK;
+  FPQ_NEED(a->form == XVC_FP_FORM_FWD_TRANSFORM || a->form == XVC_FP_FORM_RESIDUAL ||
+               a->form == XVC_FP_FORM_RESIDUAL_RDOQ,
+           "the form must be one with a prediction picture and d_tx: FWD_TRANSFORM, RESIDUAL "
+           "or RESIDUAL_RDOQ");
+  FPQ_NEED(q->d_var16 && q->d_ctu_var && q->d_cu_qp, "d_var16, d_ctu_var and d_cu_qp");
+  const int cs = q->table.ctu_size;
+  FPQ_NEED(cs == 16 || cs == 32 || cs == 64 || cs == 128, "table.ctu_size");
+  FPQ_NEED(q->table.ctus_per_row == (a->orig->w + cs - 1) / cs,
+           "table.ctus_per_row does not fit the width of orig");
+#undef FPQ_NEED
+  return XVCGPU_OK;
+}
+
+// In front of the search: the CTU statistic of orig, then the QP map into the job arrays
+static xvcgpu_status fp_aqp_front(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_args *a,
+                                  const xvcgpu_aqp_args *q, xvcgpu_me_block *const *d_me,
+                                  int n_me) {
+  const int cs = q->table.ctu_size;
+  xvcgpu_status st = xvcgpu_variance_map(ctx, a->orig, q->d_var16, cs, q->d_ctu_var);
+  if (st != XVCGPU_OK) return st;
+  // (the job arrays are device memory of the caller's; the block says const for the flat pass)
+  return aqp_apply_launch(ctx, &q->table, q->d_ctu_var,
+                          q->table.ctus_per_row * ((a->orig->h + cs - 1) / cs), d_me, n_me,
+                          const_cast<xvcgpu_tx_block *>(a->d_tx),
+                          const_cast<xvcgpu_rdoq_params *>(a->d_rdoq_params), a->d_luma_tx_index,
+                          a->n_cus, q->d_cu_qp, q->d_ctu_dqp);
+}
+
+// resolve, search, the form's launches, tail.  plan: null = xvcgpu_frame_pass; q: null = one
+// QP, else xvcgpu_frame_pass_aqp: the QP map in front of the search, the records' QPs
+// corrected in front of the tail
 static xvcgpu_status frame_pass_impl(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_args *a,
-                                     int phases, const xvcgpu_me_plan *plan) {
+                                     int phases, const xvcgpu_me_plan *plan,
+                                     const xvcgpu_aqp_args *q) {
   FramePassForm r;
   xvcgpu_status st = frame_pass_resolve(ctx, a, phases, plan, &r);
+  if (st == XVCGPU_OK && q) st = fp_aqp_check(ctx, a, q, phases);
   if (st != XVCGPU_OK) return st;
   xvcgpu_picture *const rec = r.fused_tail ? a->scratch_rec : a->rec;
   hipStream_t main_stream = nullptr;   // set while the pass runs on ctx->hi_stream
   if (r.form) {
+    if (q) {
+      xvcgpu_me_block *const jobs[1] = {const_cast<xvcgpu_me_block *>(a->d_me)};
+      st = fp_aqp_front(ctx, a, q, jobs, 1);
+      if (st != XVCGPU_OK) return st;
+    }
     st = fp_search(ctx, a, a->ref, a->d_me, a->d_results, plan);
     if (st != XVCGPU_OK) return st;   // (nothing behind a search that was refused)
     switch (r.form) {
@@ -2645,6 +2744,7 @@ static xvcgpu_status frame_pass_impl(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_ar
         break;
       default: st = fp_from_pred(ctx, a, rec, r.form); break;
     }
+    if (st == XVCGPU_OK && q) st = xvcgpu_cu_info_set_qp(ctx, a->d_cus_own, q->d_cu_qp, a->n_cus);
   }
   if (st == XVCGPU_OK) st = fp_tail(ctx, a, phases, r.fused_tail, 0);
   if (main_stream) {   // every way out: the chain continues on its own stream, after the tail
@@ -2657,18 +2757,33 @@ static xvcgpu_status frame_pass_impl(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_ar
 
 xvcgpu_status xvcgpu_frame_pass(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_args *a,
                                 int phases) {
-  return frame_pass_impl(ctx, a, phases, nullptr);
+  return frame_pass_impl(ctx, a, phases, nullptr, nullptr);
 }
 
-xvcgpu_status xvcgpu_frame_pass_planned(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_args *a,
-                                        const xvcgpu_me_plan *plan, int phases) {
+// what a plan must be to serve a->d_me's search
+static xvcgpu_status fp_plan_check(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_args *a,
+                                   const xvcgpu_me_plan *plan) {
   if (!ctx || !a || !plan || plan->n != a->n_cus || plan->d_blocks != a->d_me)
     return XVCGPU_INVALID_ARGUMENT;
   // (a plan of a smaller class would answer this pass's larger CUs as unsupported)
   if (plan->max_launched != me_class_of(a->max_block_size))
     return fail(ctx, XVCGPU_INVALID_ARGUMENT,
                 "frame_pass_planned: the plan was made for another max_block_size class");
-  return frame_pass_impl(ctx, a, phases, plan);
+  return XVCGPU_OK;
+}
+
+xvcgpu_status xvcgpu_frame_pass_planned(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_args *a,
+                                        const xvcgpu_me_plan *plan, int phases) {
+  const xvcgpu_status st = fp_plan_check(ctx, a, plan);
+  return st != XVCGPU_OK ? st : frame_pass_impl(ctx, a, phases, plan, nullptr);
+}
+
+xvcgpu_status xvcgpu_frame_pass_aqp(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_args *a,
+                                    const xvcgpu_aqp_args *q, const xvcgpu_me_plan *plan,
+                                    int phases) {
+  if (!q) return XVCGPU_INVALID_ARGUMENT;
+  const xvcgpu_status st = plan ? fp_plan_check(ctx, a, plan) : XVCGPU_OK;
+  return st != XVCGPU_OK ? st : frame_pass_impl(ctx, a, phases, plan, q);
 }
 
 /* ---- several pictures per call: every kernel launched once for all of them ---- */
@@ -3125,9 +3240,11 @@ xvcgpu_status xvcgpu_cu_info_from_choice_refs(xvcgpu_ctx *ctx,
   return XVCGPU_OK;
 }
 
-xvcgpu_status xvcgpu_frame_pass_bi_refs(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_bi_refs_args *b,
-                                        const xvcgpu_me_plan *const plans[2][XVC_CS_MAX_REFS],
-                                        int phases) {
+// q: null = one QP (xvcgpu_frame_pass_bi_refs), else xvcgpu_frame_pass_bi_refs_aqp
+static xvcgpu_status frame_pass_bi_refs_impl(xvcgpu_ctx *ctx,
+                                             const xvcgpu_frame_pass_bi_refs_args *b,
+                                             const xvcgpu_me_plan *const plans[2][XVC_CS_MAX_REFS],
+                                             int phases, const xvcgpu_aqp_args *q) {
   if (!ctx || !b || !b->p.rec) return XVCGPU_INVALID_ARGUMENT;
   // the P pass's block with list 0's first picture in the fields the shared helpers read
   xvcgpu_frame_pass_args pa = b->p;
@@ -3184,9 +3301,19 @@ xvcgpu_status xvcgpu_frame_pass_bi_refs(xvcgpu_ctx *ctx, const xvcgpu_frame_pass
 #undef FPB_NEED
   FramePassForm r;
   xvcgpu_status st = frame_pass_resolve(ctx, a, phases, plan0, &r);
+  if (st == XVCGPU_OK && q) st = fp_aqp_check(ctx, a, q, phases);
   if (st != XVCGPU_OK) return st;
   xvcgpu_picture *const rec = r.fused_tail ? a->scratch_rec : a->rec;
   if (r.form) {
+    if (q) {   // every (list, picture)'s jobs, the re-used entries' too: they price list 1
+      xvcgpu_me_block *jobs[2 * XVC_CS_MAX_REFS];
+      int n_me = 0;
+      for (int l = 0; l < 2; l++)
+        for (int k = 0; k < b->num_ref[l]; k++)
+          jobs[n_me++] = const_cast<xvcgpu_me_block *>(b->d_me[l][k]);
+      st = fp_aqp_front(ctx, a, q, jobs, n_me);
+      if (st != XVCGPU_OK) return st;
+    }
     for (int l = 0; l < 2 && st == XVCGPU_OK; l++)
       for (int q = 0; q < b->num_ref[l] && st == XVCGPU_OK; q++) {
         if (l == 1 && b->same_poc_in_l0[q] >= 0) continue;   // :536-542: list 0 searched it
@@ -3208,9 +3335,23 @@ xvcgpu_status xvcgpu_frame_pass_bi_refs(xvcgpu_ctx *ctx, const xvcgpu_frame_pass
       st = xvcgpu_inter_pred_batch(ctx, b->refs, b->n_refs, a->rec, a->pred, b->d_inter, 3 * n);
     if (st == XVCGPU_OK) st = fp_residual(ctx, a, rec, r.form);
     if (st == XVCGPU_OK) st = xvcgpu_cu_info_from_choice_refs(ctx, b);
+    if (st == XVCGPU_OK && q) st = xvcgpu_cu_info_set_qp(ctx, a->d_cus_own, q->d_cu_qp, n);
   }
   if (st == XVCGPU_OK) st = fp_tail(ctx, a, phases, r.fused_tail, 1);
   return st;
+}
+
+xvcgpu_status xvcgpu_frame_pass_bi_refs(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_bi_refs_args *b,
+                                        const xvcgpu_me_plan *const plans[2][XVC_CS_MAX_REFS],
+                                        int phases) {
+  return frame_pass_bi_refs_impl(ctx, b, plans, phases, nullptr);
+}
+
+xvcgpu_status xvcgpu_frame_pass_bi_refs_aqp(
+    xvcgpu_ctx *ctx, const xvcgpu_frame_pass_bi_refs_args *b, const xvcgpu_aqp_args *q,
+    const xvcgpu_me_plan *const plans[2][XVC_CS_MAX_REFS], int phases) {
+  if (!q) return XVCGPU_INVALID_ARGUMENT;
+  return frame_pass_bi_refs_impl(ctx, b, plans, phases, q);
 }
 
 xvcgpu_status xvcgpu_mc_metric_batch_refs(xvcgpu_ctx *ctx, const xvcgpu_picture *orig,

@@ -18,21 +18,48 @@
 
 namespace xvc_gpu {
 
-// Qp::ScaleChromaQp for 4:2:0 with chroma table 1 (quantize.cc:34-38, :74-82):
-// identity below 30, then the standard chroma mapping.
-inline int ChromaQp(int qp) {
-  static const int8_t tail[] = {29, 30, 31, 32, 33, 33, 34, 34, 35, 35, 36, 36, 37, 37};
-  qp = qp < 0 ? 0 : (qp > 57 ? 57 : qp);
-  if (qp < 30) return qp;
-  if (qp < 44) return tail[qp - 30];
-  return qp - 6;
-}
-// floor(65536 * sqrt(lambda)), lambda = 0.57 * 2^((qp-12)/3)
-// (picture_data.cc:96-97, inter_tz_search.cc:98-99)
-inline uint32_t Lambda16(int qp) {
-  return static_cast<uint32_t>(
-      std::floor(65536.0 * std::sqrt(0.57 * std::pow(2.0, (qp - 12) / 3.0))));
-}
+// (ChromaQp and Lambda16: xvc_gpu_ops.h, beside the adaptive-QP table that needs them too)
+
+// What a pass object holds for adaptive QP (FramePass::SetAdaptiveQp,
+// FramePassBiRefs::SetAdaptiveQp): the table and the four arrays of xvcgpu_aqp_args, made
+// once; every Run writes the arrays (xvcgpu_frame_pass_aqp, xvcgpu_frame_pass_bi_refs_aqp).
+class AdaptiveQpArrays {
+ public:
+  AdaptiveQpArrays(const Context &ctx, int width, int height, int bitdepth, int pic_qp,
+                   int aqp_strength, int n_cus, int ctu_size = 64)
+      : var16_(ctx, static_cast<size_t>((width + 15) / 16) * ((height + 15) / 16)),
+        ctu_var_(ctx, Ctus(width, height, ctu_size)),
+        ctu_dqp_(ctx, Ctus(width, height, ctu_size)),
+        cu_qp_(ctx, 2 * static_cast<size_t>(n_cus > 0 ? n_cus : 1)),
+        n_cus_(n_cus) {
+    args_ = xvcgpu_aqp_args();
+    args_.table = AdaptiveQp::Table(pic_qp, bitdepth, aqp_strength, width, ctu_size);
+    args_.d_var16 = var16_.data();
+    args_.d_ctu_var = ctu_var_.data();
+    args_.d_ctu_dqp = ctu_dqp_.data();
+    args_.d_cu_qp = cu_qp_.data();
+  }
+  const xvcgpu_aqp_args *args() const { return &args_; }
+  // the last Run's delta per CTU in raster order / {qp_y, qp_c} per CU (synchronise)
+  std::vector<int8_t> CtuDeltaQp() const { return ctu_dqp_.ToHost(); }
+  std::vector<int8_t> CuQp() const {
+    std::vector<int8_t> v = cu_qp_.ToHost();
+    v.resize(2 * static_cast<size_t>(n_cus_));
+    return v;
+  }
+
+ private:
+  static size_t Ctus(int width, int height, int ctu_size) {
+    if (ctu_size != 16 && ctu_size != 32 && ctu_size != 64 && ctu_size != 128)
+      throw Error(XVCGPU_INVALID_ARGUMENT, "AdaptiveQpArrays: ctu_size");
+    return static_cast<size_t>((width + ctu_size - 1) / ctu_size) *
+           ((height + ctu_size - 1) / ctu_size);
+  }
+  DeviceArray<uint64_t> var16_, ctu_var_;
+  DeviceArray<int8_t> ctu_dqp_, cu_qp_;
+  int n_cus_;
+  xvcgpu_aqp_args args_;
+};
 
 // One CU of a partition: a luma rectangle.
 struct CuRect {
@@ -117,17 +144,7 @@ class FramePass {
           map[static_cast<size_t>(yy) * map_stride_ + xx] = static_cast<int32_t>(i);
       me.push_back(b);
       luma.push_back(static_cast<int32_t>(3 * i));
-      for (int c = 0; c < 3; c++) {   // Y U V per CU: block 3 * cu + comp
-        const int sh = c ? 1 : 0;
-        xvcgpu_tx_block t = xvcgpu_tx_block();
-        t.x = static_cast<int16_t>(p.x >> sh);
-        t.y = static_cast<int16_t>(p.y >> sh);
-        t.w = static_cast<uint8_t>(p.w >> sh);
-        t.h = static_cast<uint8_t>(p.h >> sh);
-        t.comp = static_cast<uint8_t>(c);
-        t.qp = static_cast<int8_t>(c ? qp_c_ : qp);
-        tx.push_back(t);
-      }
+      for (int c = 0; c < 3; c++) tx.push_back(TxBlockOf(p, c, c ? qp_c_ : qp));
       side = p.w > side ? p.w : side;
       side = p.h > side ? p.h : side;
       small = p.w < small ? p.w : small;
@@ -194,6 +211,32 @@ class FramePass {
   FramePass(const FramePass &) = delete;
   FramePass &operator=(const FramePass &) = delete;
 
+  // From now on every Run codes with adaptive QP (CuEncoder::EncodeCtu, cu_encoder.cc:92-97;
+  // aqp_strength as encoder_settings.h:90, 13 by default there): qp is the picture's QP,
+  // each 64x64 CTU gets qp + its delta, derived on the device from the original in front of
+  // the search (xvcgpu_frame_pass_aqp).  The pass takes the form with a prediction picture
+  // and transform blocks (RESIDUAL), which is the one that reads a QP per block; its
+  // transform blocks are made here where the grid's fused form had none.
+  void SetAdaptiveQp(int aqp_strength) {
+    aqp_.reset(new AdaptiveQpArrays(ctx_, w_, h_, bd_, qp_, aqp_strength, n_cus_));
+    if (!d_tx_) {
+      std::vector<xvcgpu_tx_block> tx;
+      std::vector<int32_t> luma;
+      for (size_t i = 0; i < rects_.size(); i++) {
+        luma.push_back(static_cast<int32_t>(3 * i));
+        for (int c = 0; c < 3; c++) tx.push_back(TxBlockOf(rects_[i], c, c ? qp_c_ : qp_));
+      }
+      d_tx_.reset(new DeviceArray<xvcgpu_tx_block>(ctx_, tx));
+      d_luma_.reset(new DeviceArray<int32_t>(ctx_, luma));
+      pred_.reset(new Picture(ctx_, w_, h_, bd_));
+    }
+    form_ = XVC_FP_FORM_RESIDUAL;
+  }
+  // the last Run's delta per CTU (raster order) and {qp_y, qp_c} per CU (synchronise)
+  std::vector<int8_t> CtuDeltaQp() const { return aqp_->CtuDeltaQp(); }
+  std::vector<int8_t> CuQp() const { return aqp_->CuQp(); }
+  std::vector<xvcgpu_cu_info> CuInfo() const { return d_cus_->ToHost(); }
+
   // Enqueues one picture (asynchronous): rec becomes the padded reconstruction.
   // The whole sequence - search, CompressAndEvalCbf, deblocking, PadBorder,
   // PSNR parts - goes through one C call (xvcgpu_frame_pass).
@@ -225,11 +268,17 @@ class FramePass {
     a.form = form_;
     const int phases = XVC_FP_ENCODE | XVC_FP_DEBLOCK_V | XVC_FP_DEBLOCK_H | XVC_FP_PAD |
                        XVC_FP_SSD;
-    if (plan_) {   // a partition: the residual form's arguments, the planned search
+    if (plan_ || aqp_) {   // the residual form's arguments
       a.pred = pred_->get();
       a.d_tx = d_tx_->data();
       a.n_tx = 3 * n_cus_;
       a.d_luma_tx_index = d_luma_->data();
+    }
+    if (aqp_) {
+      ctx_.Check(xvcgpu_frame_pass_aqp(ctx_.get(), &a, aqp_->args(), plan_, phases));
+      return;
+    }
+    if (plan_) {   // a partition: the planned search
       ctx_.Check(xvcgpu_frame_pass_planned(ctx_.get(), &a, plan_, phases));
       return;
     }
@@ -246,8 +295,25 @@ class FramePass {
   int num_cus() const { return n_cus_; }
 
  private:
+  // Y, U or V block of a CU: block 3 * cu + comp
+  static xvcgpu_tx_block TxBlockOf(const CuRect &p, int comp, int qp) {
+    const int sh = comp ? 1 : 0;
+    xvcgpu_tx_block t = xvcgpu_tx_block();
+    t.x = static_cast<int16_t>(p.x >> sh);
+    t.y = static_cast<int16_t>(p.y >> sh);
+    t.w = static_cast<uint8_t>(p.w >> sh);
+    t.h = static_cast<uint8_t>(p.h >> sh);
+    t.comp = static_cast<uint8_t>(comp);
+    t.qp = static_cast<int8_t>(qp);
+    return t;
+  }
+
   void Allocate(const std::vector<xvcgpu_me_block> &me, const std::vector<int32_t> &map) {
     n_cus_ = static_cast<int>(me.size());
+    for (size_t i = 0; i < me.size(); i++) {
+      const CuRect p = {me[i].x, me[i].y, me[i].w, me[i].h};
+      rects_.push_back(p);
+    }
     d_me_.reset(new DeviceArray<xvcgpu_me_block>(ctx_, me));
     d_map_.reset(new DeviceArray<int32_t>(ctx_, map));
     d_res_.reset(new DeviceArray<xvcgpu_me_result>(ctx_, me.size()));
@@ -260,6 +326,8 @@ class FramePass {
   const Context &ctx_;
   int w_, h_, bd_, qp_, qp_c_, n_cus_, map_stride_, max_cu_, me_shape_, form_;
   xvcgpu_me_plan *plan_;
+  std::vector<CuRect> rects_;   // the CUs, in list order
+  std::unique_ptr<AdaptiveQpArrays> aqp_;
   std::unique_ptr<DeviceArray<xvcgpu_tx_block>> d_tx_;
   std::unique_ptr<DeviceArray<int32_t>> d_luma_;
   std::unique_ptr<Picture> pred_;
@@ -387,10 +455,22 @@ class FramePassBiRefs {
     b.d_bi_slots = d_bi_slots_->data();
     b.d_choice = d_choice_->data();
     b.d_inter = d_inter_->data();
-    ctx_.Check(xvcgpu_frame_pass_bi_refs(ctx_.get(), &b, plans,
-                                         XVC_FP_ENCODE | XVC_FP_DEBLOCK_V | XVC_FP_DEBLOCK_H |
-                                             XVC_FP_PAD | XVC_FP_SSD));
+    const int phases = XVC_FP_ENCODE | XVC_FP_DEBLOCK_V | XVC_FP_DEBLOCK_H | XVC_FP_PAD |
+                       XVC_FP_SSD;
+    if (aqp_) {
+      ctx_.Check(xvcgpu_frame_pass_bi_refs_aqp(ctx_.get(), &b, aqp_->args(), plans, phases));
+      return;
+    }
+    ctx_.Check(xvcgpu_frame_pass_bi_refs(ctx_.get(), &b, plans, phases));
   }
+
+  // From now on every Run codes with adaptive QP (FramePass::SetAdaptiveQp; the form is
+  // RESIDUAL already): xvcgpu_frame_pass_bi_refs_aqp.
+  void SetAdaptiveQp(int aqp_strength) {
+    aqp_.reset(new AdaptiveQpArrays(ctx_, w_, h_, bd_, qp_, aqp_strength, n_cus_));
+  }
+  std::vector<int8_t> CtuDeltaQp() const { return aqp_->CtuDeltaQp(); }
+  std::vector<int8_t> CuQp() const { return aqp_->CuQp(); }
 
   // SampleMetric::ComputePsnr parts of the last Run (synchronises).
   void Ssd(uint64_t *ssd, uint64_t *samples) const {
@@ -441,6 +521,7 @@ class FramePassBiRefs {
         if (poc_[0][q] == poc_[1][r]) same_[r] = q;   // (the first list-0 index)
     }
     rmax_ = num_ref_[0] > num_ref_[1] ? num_ref_[0] : num_ref_[1];
+    w_ = width;
     map_stride_ = (width + 3) / 4;
     max_cu_ = max_cu;
     n_cus_ = static_cast<int>(parts.size());
@@ -513,7 +594,8 @@ class FramePassBiRefs {
   }
 
   const Context &ctx_;
-  int h_, bd_, qp_, qp_c_, n_cus_, map_stride_, max_cu_, rmax_;
+  int h_, bd_, qp_, qp_c_, n_cus_, map_stride_, max_cu_, rmax_, w_;
+  std::unique_ptr<AdaptiveQpArrays> aqp_;
   int num_ref_[2], poc_[2][XVC_CS_MAX_REFS], slot_[2][XVC_CS_MAX_REFS], same_[XVC_CS_MAX_REFS];
   std::vector<int> distinct_;
   xvcgpu_me_plan *plan_[2][XVC_CS_MAX_REFS];

@@ -1017,12 +1017,107 @@ class Checksum {
   std::vector<uint8_t> hash_;
 };
 
+// Qp::ScaleChromaQp for 4:2:0 with chroma table 1 (quantize.cc:34-38, :74-82):
+// identity below 30, then the standard chroma mapping.
+inline int ChromaQp(int qp) {
+  static const int8_t tail[] = {29, 30, 31, 32, 33, 33, 34, 34, 35, 35, 36, 36, 37, 37};
+  qp = qp < 0 ? 0 : (qp > 57 ? 57 : qp);
+  if (qp < 30) return qp;
+  if (qp < 44) return tail[qp - 30];
+  return qp - 6;
+}
+// floor(65536 * sqrt(lambda)), lambda = 0.57 * 2^((qp-12)/3)
+// (picture_data.cc:96-97, inter_tz_search.cc:98-99)
+inline uint32_t Lambda16(int qp) {
+  return static_cast<uint32_t>(
+      std::floor(65536.0 * std::sqrt(0.57 * std::pow(2.0, (qp - 12) / 3.0))));
+}
+// The two double-arithmetic constants of RdoQuant::QuantRdo per component Y, U, V for a
+// picture of this QP (pipeline.rdoq_host_params): lambda = (int64)(GetLambdaScaled(comp) *
+// 65536 + 0.5) (rdo_quant.cc:251-252), rd_factor = (int64)(inv_scale^2 / lambda / 16 /
+// (1 << 2 (bitdepth - 8)) + 0.5) (:590-594); Qp: quantize.cc:44-92, the luma lambda
+// PictureData::Init's 0.57 * 2^((qp - 12) / 3).
+inline void RdoqHostParams(int qp, int bitdepth, int64_t lambda[3], int64_t rd_factor[3]) {
+  static const int kInvScales[6] = {40, 45, 51, 57, 64, 72};
+  const double lam = 0.57 * std::pow(2.0, (qp - 12) / 3.0);
+  const int qpc = ChromaQp(qp);
+  const int qp57 = qp < 0 ? 0 : (qp > 57 ? 57 : qp);
+  const double weight_c = std::pow(2.0, -(qpc - qp57) / 3.0);
+  for (int c = 0; c < 3; c++) {
+    const double lam_c = c == 0 ? lam : lam / weight_c;
+    int qpb = (c == 0 ? qp : qpc) + 6 * (bitdepth - 8);
+    qpb = qpb < 0 ? 0 : qpb;
+    const double inv_scale = static_cast<double>(static_cast<int64_t>(kInvScales[qpb % 6])
+                                                 << (qpb / 6));
+    lambda[c] = static_cast<int64_t>(lam_c * 65536 + 0.5);
+    rd_factor[c] = static_cast<int64_t>(inv_scale * inv_scale / lam_c / 16 /
+                                        (1 << (2 * (bitdepth - 8))) + 0.5);
+  }
+}
+
 // CuEncoder::CalcDeltaQpFromVariance for all CTUs of a picture at once: the
 // device computes the per-CTU block-variance statistic, the host the
-// floating-point part (cu_encoder.cc:359-363).
+// floating-point part (cu_encoder.cc:359-363) - or, through Table(), nothing per picture:
+// the thresholds of an xvcgpu_aqp_table say the delta without std::log, and the
+// adaptive-QP frame passes (xvcgpu_frame_pass_aqp) count them on the device.
 class AdaptiveQp {
  public:
   AdaptiveQp(const Context &ctx, int aqp_strength) : ctx_(ctx), strength_(aqp_strength) {}
+  // cu_encoder.cc:359-362 for one statistic: the reference's double expression, the
+  // truncating cast and the clip
+  static int DeltaQp(uint64_t variance, int bitdepth, int aqp_strength) {
+    const double k = 1.0 * aqp_strength / 10;
+    const double d =
+        k * (1.5 * std::log(static_cast<double>(variance)) - 15 - 2 * (bitdepth - 8));
+    const int q = static_cast<int>(d);
+    return q < XVC_AQP_DELTA_MIN
+               ? XVC_AQP_DELTA_MIN
+               : (q > XVC_AQP_DELTA_MIN + XVC_AQP_DELTAS - 1 ? XVC_AQP_DELTA_MIN + XVC_AQP_DELTAS - 1
+                                                             : q);
+  }
+  // The xvcgpu_aqp_table of a picture coded at pic_qp (pipeline.aqp_table: the same bytes).
+  // The delta does not decrease in the statistic for a strength >= 0 (a negative one is
+  // refused): var_min[k] = the smallest v >= 1 whose delta is >= XVC_AQP_DELTA_MIN + 1 + k,
+  // by bisection over [1, 2^63] with DeltaQp; UINT64_MAX: none.  Per delta the clipped QP
+  // (PictureData::GetQp, picture_data.h:51-53) and the constants of a picture of that QP
+  // with recalculate_lambda (picture_data.cc:94-106).
+  static xvcgpu_aqp_table Table(int pic_qp, int bitdepth, int aqp_strength, int width,
+                                int ctu_size = 64) {
+    if (aqp_strength < 0)
+      throw Error(XVCGPU_INVALID_ARGUMENT, "AdaptiveQp::Table: a negative aqp_strength");
+    if (ctu_size != 16 && ctu_size != 32 && ctu_size != 64 && ctu_size != 128)
+      throw Error(XVCGPU_INVALID_ARGUMENT, "AdaptiveQp::Table: ctu_size");
+    xvcgpu_aqp_table t = xvcgpu_aqp_table();
+    t.pic_qp = pic_qp;
+    t.ctu_size = ctu_size;
+    t.ctus_per_row = (width + ctu_size - 1) / ctu_size;
+    const uint64_t top = 1ull << 63;
+    for (int k = 0; k < XVC_AQP_DELTAS - 1; k++) {
+      const int want = XVC_AQP_DELTA_MIN + 1 + k;
+      if (DeltaQp(top, bitdepth, aqp_strength) < want) {
+        t.var_min[k] = ~0ull;
+        continue;
+      }
+      uint64_t lo = 1, hi = top;   // the answer lies in [lo, hi]; DeltaQp(hi) >= want
+      while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (DeltaQp(mid, bitdepth, aqp_strength) >= want)
+          hi = mid;
+        else
+          lo = mid + 1;
+      }
+      t.var_min[k] = lo;
+    }
+    for (int k = 0; k < XVC_AQP_DELTAS; k++) {
+      int qp = pic_qp + XVC_AQP_DELTA_MIN + k;
+      qp = qp < 0 ? 0 : (qp > 63 ? 63 : qp);
+      t.qp_y[k] = static_cast<int8_t>(qp);
+      t.qp_c[k] = static_cast<int8_t>(ChromaQp(qp));
+      t.lambda16[k] = Lambda16(qp);
+      RdoqHostParams(qp, bitdepth, t.rdoq_lambda[k], t.rdoq_rd_factor[k]);
+    }
+    return t;
+  }
   // -> one QP offset per CTU in raster order
   std::vector<int> CalcDeltaQpFromVariance(const Picture &orig_pic, int width, int height,
                                            int bitdepth, int ctu_size) const {
@@ -1034,12 +1129,7 @@ class AdaptiveQp {
                                    ctu_var.data()));
     const std::vector<uint64_t> v = ctu_var.ToHost();
     std::vector<int> dqp(nc);
-    const double k = 1.0 * strength_ / 10;
-    for (size_t i = 0; i < nc; i++) {
-      const double d = k * (1.5 * std::log(static_cast<double>(v[i])) - 15 - 2 * (bitdepth - 8));
-      const int q = static_cast<int>(d);
-      dqp[i] = q < -3 ? -3 : (q > 7 ? 7 : q);
-    }
+    for (size_t i = 0; i < nc; i++) dqp[i] = DeltaQp(v[i], bitdepth, strength_);
     return dqp;
   }
 

@@ -85,6 +85,93 @@ def rdoq_host_params(qp, bitdepth, lam=None):
     return out
 
 
+def _aqp_delta(var, bitdepth, strength):
+    """CuEncoder::CalcDeltaQpFromVariance's last lines (cu_encoder.cc:359-363) in the
+    reference's double expression, truncating cast included."""
+    d = (1.0 * strength / 10) * (1.5 * math.log(float(var)) - 15 - 2 * (bitdepth - 8))
+    return max(api.AQP_DELTA_MIN, min(api.AQP_DELTA_MIN + api.AQP_DELTAS - 1, int(d)))
+
+
+def aqp_table(pic_qp, bitdepth, strength, width, ctu_size=64):
+    """The xvcgpu_aqp_table (api.AqpTable) of a picture coded at pic_qp with adaptive QP
+    of this aqp_strength (CuEncoder::EncodeCtu, cu_encoder.cc:92-97; the reference's
+    default is 13, encoder_settings.h:89-90).  The delta does not decrease in the CTU
+    statistic v for a strength >= 0, so var_min[k] - the smallest v >= 1 whose delta is
+    >= -2 + k, found by bisection over [1, 2^63] with the reference's expression;
+    UINT64_MAX: none - says it without a logarithm.  Per delta: the clipped QP
+    (PictureData::GetQp, picture_data.h:51-53), its chroma QP and the constants of a
+    picture of that QP with recalculate_lambda (picture_data.cc:94-106) as
+    lambda16_for_qp and rdoq_host_params compute them.  The same bytes as
+    xvc_gpu::AdaptiveQp::Table (host/xvc_gpu_ops.h)."""
+    if strength < 0:
+        raise ValueError("aqp_strength %d: a negative strength makes the delta fall as the "
+                         "variance grows; the thresholds cannot say that" % strength)
+    if ctu_size not in (16, 32, 64, 128):
+        raise ValueError("ctu_size %r is not 16, 32, 64 or 128" % (ctu_size,))
+    t = api.AqpTable()
+    t.pic_qp, t.ctu_size = pic_qp, ctu_size
+    t.ctus_per_row = (width + ctu_size - 1) // ctu_size
+    top = 1 << 63
+    for k in range(api.AQP_DELTAS - 1):
+        want = api.AQP_DELTA_MIN + 1 + k
+        if _aqp_delta(top, bitdepth, strength) < want:
+            t.var_min[k] = 0xffffffffffffffff
+            continue
+        lo, hi = 1, top         # the answer lies in [lo, hi]; delta(hi) >= want
+        while lo < hi:
+            mid = (lo + hi) // 2
+            if _aqp_delta(mid, bitdepth, strength) >= want:
+                hi = mid
+            else:
+                lo = mid + 1
+        t.var_min[k] = lo
+    for k in range(api.AQP_DELTAS):
+        qp = max(0, min(63, pic_qp + api.AQP_DELTA_MIN + k))
+        t.qp_y[k], t.qp_c[k], t.lambda16[k] = qp, chroma_qp(qp), lambda16_for_qp(qp)
+        for c, (lf, rf) in enumerate(rdoq_host_params(qp, bitdepth)):
+            t.rdoq_lambda[k][c], t.rdoq_rd_factor[k][c] = lf, rf
+    return t
+
+
+class _AqpArrays:
+    """What an adaptive-QP pass object holds beside the flat pass's state: the table and
+    the four arrays of xvcgpu_aqp_args (allocated once; every run writes them)."""
+
+    def __init__(self, ctx, desc, bitdepth, strength, ctu_size=64):
+        self.ctx, self.strength, self.ctu_size = ctx, strength, ctu_size
+        self.table = aqp_table(desc.qp, bitdepth, strength, desc.w, ctu_size)
+        self.ctu_cols = (desc.w + ctu_size - 1) // ctu_size
+        self.ctu_rows = (desc.h + ctu_size - 1) // ctu_size
+        self.n_cus = desc.n_cus
+        self.d_var16 = ctx.alloc(8 * ((desc.w + 15) // 16) * ((desc.h + 15) // 16))
+        self.d_ctu_var = ctx.alloc(8 * self.ctu_cols * self.ctu_rows)
+        self.d_ctu_dqp = ctx.alloc(self.ctu_cols * self.ctu_rows)
+        self.d_cu_qp = ctx.alloc(2 * max(1, desc.n_cus))
+
+    def args(self):
+        q = api.AqpArgs()
+        q.table = self.table
+        q.d_var16, q.d_ctu_var = self.d_var16.ptr, self.d_ctu_var.ptr
+        q.d_ctu_dqp, q.d_cu_qp = self.d_ctu_dqp.ptr, self.d_cu_qp.ptr
+        return q
+
+    def ctu_delta_qp(self):
+        """The last run's delta QP per CTU, [rows, columns] int8."""
+        return self.d_ctu_dqp.to_array(np.int8, self.ctu_cols * self.ctu_rows).reshape(
+            self.ctu_rows, self.ctu_cols)
+
+    def cu_qp(self):
+        """The last run's (qp_y, qp_c) per CU, [n_cus, 2] int8."""
+        return self.d_cu_qp.to_array(np.int8, 2 * self.n_cus).reshape(-1, 2)
+
+    def free(self):
+        for b in (self.d_var16, self.d_ctu_var, self.d_ctu_dqp, self.d_cu_qp):
+            b.free()
+
+
+_AQP_FORMS = ("fwd_transform", "residual", "residual_rdoq")
+
+
 def cu_partition(width, height, cu=16, xcd_tiles=False):
     """List of (x, y, w, h): cu x cu CUs, smaller at right/bottom edge - in raster
     order, or (xcd_tiles) region by region of a 4 x 2 tiling of the picture, raster
@@ -278,13 +365,25 @@ class FramePass:
     the grid; else prediction picture + residual pipeline (`residual`, `residual_rdoq`,
     or `fwd_transform` for packed RDOQ) -, the fused tail needs CUs without a side of 4,
     and the search runs through a plan made here (xvcgpu_me_plan_create: the jobs sorted
-    once by kernel instance, one launch per non-empty bin)."""
+    once by kernel instance, one launch per non-empty bin).
+
+    form=: name the form instead of taking the one the shapes give - "fwd_transform" where
+    that would be "fwd_from_me" (the same buffers; the form an adaptive-QP pass can run).
+
+    aqp_strength=: None, or the reference's aqp_strength (13 by default there) for a pass
+    with adaptive QP (xvcgpu_frame_pass_aqp): qp is then the picture's QP, every 64x64 CTU
+    gets qp + its delta, derived on the device from orig in front of the search and written
+    into this object's job arrays; whole pictures, forms `fwd_transform`, `residual` and
+    `residual_rdoq` (else ValueError).  ctu_delta_qp() and cu_qp() read the last run's map
+    back."""
 
     def __init__(self, ctx, width, height, bitdepth=10, qp=32, cu=16,
                  search_range=96, row_range=None, fused=True, keep_levels=False,
-                 rdoq=False, rdoq_packed=None, xcd_tiles=False, partition=None):
+                 rdoq=False, rdoq_packed=None, xcd_tiles=False, partition=None, form=None,
+                 aqp_strength=None):
         self.ctx = ctx
         self.plan = None
+        self.aqp = None
         self.rdoq = rdoq
         # RDOQ keeps only a few lanes of a wave busy per block, so its own kernel
         # packs several blocks into a wave (xvcgpu_quant_rdo_batch) between the
@@ -313,6 +412,19 @@ class FramePass:
             self.form = "fwd_transform"     # packed RDOQ behind mc_from_me
         else:
             self.form = "residual_rdoq" if rdoq else "residual"
+        if form is not None and form != self.form:
+            if (self.form, form) != ("fwd_from_me", "fwd_transform"):
+                raise ValueError("form %r: these shapes and settings run %r" % (form, self.form))
+            self.form = form
+        if aqp_strength is not None:
+            if self.form not in _AQP_FORMS:
+                raise ValueError("aqp_strength: the form %r builds its transform blocks from "
+                                 "one QP inside its kernels; adaptive QP runs %s" %
+                                 (self.form, ", ".join(_AQP_FORMS)))
+            if d.row_range != (0, d.h):
+                raise ValueError("aqp_strength: whole pictures only (no row_range)")
+            aqp_table(qp, bitdepth, aqp_strength, width)    # (a refused strength: before
+            #                                                  anything is allocated)
         self.d_rdoq_ctx = ctx.buffer(d.rdoq_contexts) if rdoq else None
         self.d_rdoq_prm = ctx.buffer(d.rdoq_params) if rdoq else None
         self.d_me = ctx.buffer(d.me)
@@ -368,6 +480,8 @@ class FramePass:
         self.d_coeffs = ctx.alloc(2 * max(1, self.n_levels)) if self.rdoq_packed else None
         if self.rdoq_packed:    # no allocation inside the passes (they may be recorded)
             ctx._check(ctx.lib.xvcgpu_quant_rdo_reserve(ctx.h, len(d.tx), self.n_levels))
+        if aqp_strength is not None:
+            self.aqp = _AqpArrays(ctx, d, bitdepth, aqp_strength)
 
     @property
     def d_cus_own(self):
@@ -411,9 +525,12 @@ class FramePass:
         return a
 
     def run_phases(self, orig, ref, rec, phases, ref_poc=0, rows=None, dbh_end=None,
-                   ssd_rows=None, d_ssd=None):
-        """One call for the selected phases (api.FP_*)."""
+                   ssd_rows=None, d_ssd=None, fused_tail=True):
+        """One call for the selected phases (api.FP_*).  fused_tail=False: end with the
+        separate deblocking, padding and SSD launches also where the one launch applies."""
         a = self._call_args(orig, ref, rec, ref_poc)
+        if not fused_tail:
+            a.scratch_rec = None
         if rows is not None:
             a.db_y_begin, a.db_y_end = rows
             a.dbh_y_end = dbh_end if dbh_end is not None else rows[1]
@@ -421,6 +538,12 @@ class FramePass:
             a.ssd_y_begin, a.ssd_y_end = ssd_rows
         if d_ssd is not None:
             a.d_ssd = d_ssd
+        if self.aqp is not None:
+            q = self.aqp.args()
+            self.ctx._check(self.ctx.lib.xvcgpu_frame_pass_aqp(
+                self.ctx.h, C.byref(a), C.byref(q), self.plan.h if self.plan is not None else None,
+                phases))
+            return
         if self.plan is not None:
             self.ctx._check(self.ctx.lib.xvcgpu_frame_pass_planned(self.ctx.h, C.byref(a),
                                                                    self.plan.h, phases))
@@ -523,13 +646,14 @@ class FramePass:
         self.ctx.deblock_rows_dev(rec, self.d_cus.ptr, d.n_cus_total, self.d_map.ptr,
                                   d.cu_map.shape[1], pass_, y0, y1)
 
-    def run(self, orig, ref, rec, ref_poc=0, deblock=True, pad=True, ssd=True):
+    def run(self, orig, ref, rec, ref_poc=0, deblock=True, pad=True, ssd=True, fused_tail=True):
         """Enqueue one whole-picture frame pass (asynchronous)."""
         if self.desc.row_range == (0, self.desc.h):
             # the whole sequence behind one C call (xvcgpu_frame_pass), whatever the form
             self.run_phases(orig, ref, rec, api.FP_ENCODE |
                             (api.FP_DEBLOCK_V | api.FP_DEBLOCK_H if deblock else 0) |
-                            (api.FP_PAD if pad else 0) | (api.FP_SSD if ssd else 0), ref_poc)
+                            (api.FP_PAD if pad else 0) | (api.FP_SSD if ssd else 0), ref_poc,
+                            fused_tail=fused_tail)
             return
         enc, tail = self._launches(orig, ref, rec, ref_poc,
                                    self.fused_tail and deblock and pad and ssd)
@@ -545,7 +669,18 @@ class FramePass:
                 self.d_cus.to_array(api.CU_DTYPE, d.n_cus_total),
                 self.d_ssd.to_array(np.uint64, 2))
 
+    def ctu_delta_qp(self):
+        """Adaptive QP: the last run's delta per CTU, [rows, columns] int8."""
+        return self.aqp.ctu_delta_qp()
+
+    def cu_qp(self):
+        """Adaptive QP: the last run's (qp_y, qp_c) per CU, [n_cus, 2] int8."""
+        return self.aqp.cu_qp()
+
     def destroy(self):
+        if self.aqp is not None:
+            self.aqp.free()
+            self.aqp = None
         for b in (self.d_me, self.d_tx, self.d_luma_idx, self.d_map, self.d_res,
                   self.d_nnz, self.d_cus, self.d_ssd, self.d_levels, self.d_level_off,
                   self.d_rdoq_ctx, self.d_rdoq_prm, self.d_coeffs):
@@ -598,8 +733,12 @@ class BiRefsFramePass:
 
     def __init__(self, ctx, width, height, bitdepth=10, qp=32, cu=16, rdoq=False,
                  rdoq_packed=None, keep_levels=False, partition=None, cur_poc=8,
-                 ref_pocs=((4,), (12,)), search_range=96, side_bits=(3, 3, 5)):
+                 ref_pocs=((4,), (12,)), search_range=96, side_bits=(3, 3, 5),
+                 aqp_strength=None):
         self.ctx = ctx
+        self.aqp = None
+        if aqp_strength is not None:    # (a refused strength: before anything is allocated)
+            aqp_table(qp, bitdepth, aqp_strength, width)
         self.cur_poc, self.side_bits = cur_poc, tuple(side_bits)
         self.ref_pocs = [list(ref_pocs[0]), list(ref_pocs[1])]
         self.num_ref = [len(l) for l in self.ref_pocs]
@@ -632,6 +771,8 @@ class BiRefsFramePass:
         self.d_choice = ctx.alloc(api.FP_BI_REFS_RESULT_DTYPE.itemsize * n)
         self.d_inter = ctx.alloc(api.INTER_DTYPE.itemsize * 3 * n)
         self.plans = [[None] * self.num_ref[l] for l in range(2)]
+        if aqp_strength is not None:    # (every form of this pass is one adaptive QP runs)
+            self.aqp = _AqpArrays(ctx, d, bitdepth, aqp_strength)
         if p.plan is not None:
             for l in range(2):
                 for r in range(self.num_ref[l]):
@@ -697,9 +838,14 @@ class BiRefsFramePass:
         a = self._call_args(orig, refs, rec)
         if not fused_tail:
             a.p.scratch_rec = None
+        phases = api.FP_ENCODE | api.FP_DEBLOCK_V | api.FP_DEBLOCK_H | api.FP_PAD | api.FP_SSD
+        if self.aqp is not None:
+            q = self.aqp.args()
+            self.ctx._check(self.ctx.lib.xvcgpu_frame_pass_bi_refs_aqp(
+                self.ctx.h, C.byref(a), C.byref(q), self.plan_handles(planned), phases))
+            return
         self.ctx._check(self.ctx.lib.xvcgpu_frame_pass_bi_refs(
-            self.ctx.h, C.byref(a), self.plan_handles(planned),
-            api.FP_ENCODE | api.FP_DEBLOCK_V | api.FP_DEBLOCK_H | api.FP_PAD | api.FP_SSD))
+            self.ctx.h, C.byref(a), self.plan_handles(planned), phases))
 
     def kernel_steps(self, orig, refs, rec, fused_tail=None, planned=True):
         """The launches of one pass as (name, callable) in issue order, each through its own
@@ -771,7 +917,18 @@ class BiRefsFramePass:
                 self.d_bi_res.to_array(api.MERES_DTYPE, d.n_cus * self.rmax).reshape(-1, self.rmax),
                 self.d_bi_slots.to_array(np.uint8, 2 * d.n_cus * self.rmax).reshape(-1, self.rmax, 2))
 
+    def ctu_delta_qp(self):
+        """Adaptive QP: the last run's delta per CTU, [rows, columns] int8."""
+        return self.aqp.ctu_delta_qp()
+
+    def cu_qp(self):
+        """Adaptive QP: the last run's (qp_y, qp_c) per CU, [n_cus, 2] int8."""
+        return self.aqp.cu_qp()
+
     def destroy(self):
+        if self.aqp is not None:
+            self.aqp.free()
+            self.aqp = None
         bufs = [self.d_bi_jobs, self.d_bi_res, self.d_bi_slots, self.d_choice, self.d_inter]
         for l in range(2):
             bufs += self.d_me[l] + [b for b in self.d_res[l] if b is not None]
