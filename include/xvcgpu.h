@@ -1376,6 +1376,67 @@ xvcgpu_status xvcgpu_frame_pass_bi_refs_aqp(
     xvcgpu_ctx *ctx, const xvcgpu_frame_pass_bi_refs_args *b, const xvcgpu_aqp_args *q,
     const xvcgpu_me_plan *const plans[2][XVC_CS_MAX_REFS], int phases);
 
+/* ---- the P frame pass with affine motion ---------------------------------------- *
+ * InterSearch::CompressInter (inter_search.cc:74-99): every CU that CanUseAffine is searched
+ * twice, translational and with the three-corner model, and keeps the cheaper state.  The
+ * pass composes launches that exist with four small ones (k_fp_affine.h); nothing is read
+ * back.  xvcgpu_types.h: xvcgpu_fp_affine_result, xvcgpu_frame_pass_affine_args.
+ *
+ * xvcgpu_fp_affine_boot: one thread per listed CU (d_order[0 .. n_listed)), 256-thread
+ * workgroups.  d_affine[i].bootstrap = the plain result's vector through ClipMv (the CU's
+ * position in a pic_w x pic_h picture) at all three corners - DeriveMvAffine(mv, mv),
+ * inter_prediction.cc:615-630: the third corner equals the first - and flags =
+ * XVC_AFFINE_ME_HAS_BOOTSTRAP.  A plain result of XVCGPU_ME_UNSUPPORTED gives no job:
+ * flags = XVC_AFFINE_ME_NO_JOB, bootstrap zero.  No other byte of the job is written, no
+ * job outside the list is touched.
+ * xvcgpu_affine_me_listed: xvcgpu_affine_me_batch over the jobs d_order names - workgroup
+ * g of the instance of class c (NW = 2, 4, 8 waves for CU heights 16, 32, 64) takes job
+ * d_order[first_c + g]; one launch per non-empty class.  d_order must be grouped as
+ * n_class says (a job of another height than its class's is left alone).  Results equal
+ * xvcgpu_affine_me_batch's record for record; records outside the list, and those of
+ * XVC_AFFINE_ME_NO_JOB jobs, are not touched.
+ * xvcgpu_fp_affine_choice: one thread per CU.  cost_plain = subpel_dist + (((side_bits + 1 +
+ * GetMvdBits(mvp, mv, fullpel ? 2 : 0)) * lambda16) >> 16), cost_affine = dist +
+ * (((side_bits + 1 + the exp-Golomb bits of corner 0's and corner 1's quarter-sample
+ * difference to d_affine[i].mvp) * d_affine[i].lambda16) >> 16), both with 64-bit products
+ * and kept in 32 bits; affine only where cost_affine < cost_plain.  A CU counts as searched
+ * where it is capable (xvcgpu_types.h) and its job carries XVC_AFFINE_ME_HAS_BOOTSTRAP.
+ * Writes d_choice[i] and d_inter[3 i + comp]: ref = {0, -1}, and XVC_INTER_AFFINE with the
+ * three corners or the plain vector at corner 0; an unsupported plain search: the record
+ * all ones, jobs with ref = {-1, -1}.
+ * xvcgpu_cu_info_from_affine_choice: xvcgpu_cu_info_from_me with corners - an affine CU's
+ * mv[0][UL, UR, DL] the result and DR = UR + DL - UL, else all four the vector; list 1
+ * unused (ref_poc -1, vectors zero); cbf_luma from d_nnz[d_luma_tx_index[i]] (NULL: d_nnz[i]).
+ *
+ * xvcgpu_frame_pass_affine: the search (plan NULL: sized; else planned) -> boot -> the listed
+ * search -> choice -> xvcgpu_inter_pred_batch({a->ref} -> a->pred, f->d_inter) -> the
+ * residual pipeline of a->form -> the record kernel -> the tail exactly as xvcgpu_frame_pass
+ * runs it, fused or separate.  Forms: FWD_TRANSFORM, RESIDUAL, RESIDUAL_RDOQ; the _from_me
+ * forms predict inside their kernels and are refused, naming `form`.  Every check - the flat
+ * pass's included - happens before the first launch (XVCGPU_INVALID_ARGUMENT, the message
+ * names the field): a missing array, n_class counts below 0 or above n_cus in sum, part of
+ * a picture, phases without XVC_FP_ENCODE, a plan with LIC jobs.  After them the call only
+ * enqueues: no synchronisation, no allocation.  With no capable CU the pass gives
+ * xvcgpu_frame_pass's bytes. */
+xvcgpu_status xvcgpu_fp_affine_boot(xvcgpu_ctx *ctx, const xvcgpu_me_result *d_results,
+                                    const int32_t *d_order, int n_listed, int pic_w,
+                                    int pic_h, xvcgpu_affine_me_block *d_affine);
+xvcgpu_status xvcgpu_affine_me_listed(xvcgpu_ctx *ctx, const xvcgpu_picture *orig,
+                                      const xvcgpu_picture *ref,
+                                      const xvcgpu_affine_me_block *d_blocks, int n,
+                                      const int32_t *d_order, const int32_t n_class[3],
+                                      xvcgpu_affine_me_result *d_results);
+xvcgpu_status xvcgpu_fp_affine_choice(xvcgpu_ctx *ctx, const xvcgpu_me_block *d_me,
+                                      const xvcgpu_me_result *d_results, int n_cus,
+                                      const xvcgpu_frame_pass_affine_args *f);
+xvcgpu_status xvcgpu_cu_info_from_affine_choice(
+    xvcgpu_ctx *ctx, const xvcgpu_me_block *d_me, const xvcgpu_fp_affine_result *d_choice,
+    const int32_t *d_nnz, const int32_t *d_luma_tx_index, int n, int qp_y, int qp_c,
+    int ref_poc, xvcgpu_cu_info *d_cus_own);
+xvcgpu_status xvcgpu_frame_pass_affine(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_args *a,
+                                       const xvcgpu_frame_pass_affine_args *f,
+                                       const xvcgpu_me_plan *plan, int phases);
+
 /* ---- tables (host side, no GPU needed) ---------------------------------- *
  * The 8-bit-fraction transform matrices the kernels use (transform_data.cc:
  * 109-796), for table-equality tests. out: size*size int16 row-major. */

@@ -719,6 +719,8 @@ typedef struct xvcgpu_aqp_args {
  * are halved, 5 iterations, the bootstrap vector always wins. */
 #define XVC_AFFINE_ME_HAS_BOOTSTRAP 1
 #define XVC_AFFINE_ME_BIPRED 2
+#define XVC_AFFINE_ME_NO_JOB 4   /* xvcgpu_fp_affine_boot: the plain search had no result;
+                                  * xvcgpu_affine_me_listed leaves the job alone         */
 typedef struct xvcgpu_affine_me_block {
   int16_t x, y;        /* luma position of the CU */
   uint8_t w, h;        /* 16, 32 or 64 each (CodingUnit::CanUseAffine: > 8) */
@@ -735,6 +737,43 @@ typedef struct xvcgpu_affine_me_result {
   uint32_t dist;       /* *out_dist: SATD of the best prediction (>> 1 with BIPRED) */
   uint32_t iterations; /* gradient iterations that produced a non-zero update */
 } xvcgpu_affine_me_result;
+
+/* ---- the P frame pass with affine motion (xvcgpu_frame_pass_affine) --------------- *
+ * InterSearch::CompressInter (inter_search.cc:74-99) runs SearchMotion twice for a CU that
+ * CanUseAffine (both sides above 8, coding_unit.h:251-257): translational, then with the
+ * three-corner model bootstrapped from the translational vector (:525-531), and keeps the
+ * cheaper state - the translational one on a tie (:90).
+ * What the pass ends with for one CU, and what shows why.  A CU that is not capable:
+ * use_affine 0, cost_affine UINT32_MAX, the plain vector three times, dist_affine and
+ * iterations 0.  A CU whose plain search has no kernel instance (XVCGPU_ME_UNSUPPORTED):
+ * every byte 0xff. */
+typedef struct xvcgpu_fp_affine_result {
+  int32_t use_affine;
+  int32_t mv[3][2];     /* the chosen state's corners UL, UR, DL; 1/16 pel              */
+  uint32_t cost_plain;  /* subpel_dist + ((bits * lambda16) >> 16) of the plain state    */
+  uint32_t cost_affine; /* the same of the affine state; UINT32_MAX: not capable         */
+  uint32_t cost;        /* the chosen state's                                            */
+  uint32_t dist_affine; /* the affine search's SATD                                      */
+  uint32_t iterations;  /* ... and its gradient iterations                               */
+} xvcgpu_fp_affine_result;
+
+/* What xvcgpu_frame_pass_affine takes beside the flat pass's block; every array is the
+ * caller's, allocated once.  d_affine: one job per own CU in CU order - the caller fills
+ * x, y, w, h, lambda16 and mvp (an input, as the plain job's mvp is: no AMVP derivation),
+ * flags 0; the device writes flags and bootstrap.  d_order: the indices of the capable CUs
+ * - w and h each 16, 32 or 64, the plain job without XVC_ME_FULLPEL_MV and XVC_ME_USE_LIC -
+ * grouped by CU height: n_class[0] of height 16, then n_class[1] of 32, then n_class[2] of
+ * 64.  side_bits: GetInterPredBits without predictor index and vector difference, 1 for a
+ * picture with one list (inter_search.cc:1092). */
+typedef struct xvcgpu_frame_pass_affine_args {
+  xvcgpu_affine_me_block *d_affine;          /* n_cus                                    */
+  xvcgpu_affine_me_result *d_affine_results; /* n_cus                                    */
+  const int32_t *d_order;                    /* n_class[0] + n_class[1] + n_class[2]     */
+  int32_t n_class[3];
+  uint32_t side_bits;
+  xvcgpu_fp_affine_result *d_choice;         /* n_cus                                    */
+  xvcgpu_inter_block *d_inter;               /* 3 * n_cus: the prediction jobs Y, U, V   */
+} xvcgpu_frame_pass_affine_args;
 
 /* ---- C1, decision half: the folds of CompressAndEvalTransform and of
  * CompressAndEvalCbf (transform_encoder.cc:53-201, inter_search.cc:261-365).

@@ -190,6 +190,24 @@ class AqpArgs(C.Structure):
 
 assert C.sizeof(AqpTable) == 696 and C.sizeof(AqpArgs) == 728
 
+AFFINE_ME_NO_JOB = 4    # XVC_AFFINE_ME_NO_JOB
+
+# xvcgpu_fp_affine_result: what CompressInter's two SearchMotion runs end with for one CU
+FP_AFFINE_RESULT_DTYPE = np.dtype([
+    ("use_affine", "<i4"), ("mv", "<i4", (3, 2)), ("cost_plain", "<u4"),
+    ("cost_affine", "<u4"), ("cost", "<u4"), ("dist_affine", "<u4"), ("iterations", "<u4")])
+assert FP_AFFINE_RESULT_DTYPE.itemsize == 48
+
+
+class FramePassAffineArgs(C.Structure):
+    """xvcgpu_frame_pass_affine_args (include/xvcgpu_types.h)"""
+    _fields_ = [("d_affine", C.c_void_p), ("d_affine_results", C.c_void_p),
+                ("d_order", C.c_void_p), ("n_class", C.c_int32 * 3), ("side_bits", C.c_uint32),
+                ("d_choice", C.c_void_p), ("d_inter", C.c_void_p)]
+
+
+assert C.sizeof(FramePassAffineArgs) == 56
+
 # xvcgpu_fp_bi_refs_result: what SearchMotion ends with for one CU of a B picture
 FP_BI_REFS_RESULT_DTYPE = np.dtype([
     ("inter_dir", "<i4"), ("search_list", "<i4"), ("ref_idx", "<i4", (2,)),
@@ -257,6 +275,8 @@ SYMBOLS = [
     "xvcgpu_bipred_search_refs_planned", "xvcgpu_frame_pass_bi_refs",
     "xvcgpu_aqp_apply", "xvcgpu_cu_info_set_qp", "xvcgpu_frame_pass_aqp",
     "xvcgpu_frame_pass_bi_refs_aqp",
+    "xvcgpu_fp_affine_boot", "xvcgpu_affine_me_listed", "xvcgpu_fp_affine_choice",
+    "xvcgpu_cu_info_from_affine_choice", "xvcgpu_frame_pass_affine",
 ]
 
 _vp = C.c_void_p
@@ -473,6 +493,13 @@ def load_library(allow_missing=()):
         "xvcgpu_frame_pass_aqp": [_vp, C.POINTER(FramePassArgs), C.POINTER(AqpArgs), _vp, C.c_int],
         "xvcgpu_frame_pass_bi_refs_aqp": [_vp, C.POINTER(FramePassBiRefsArgs), C.POINTER(AqpArgs),
                                           _vp, C.c_int],
+        "xvcgpu_fp_affine_boot": [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp],
+        "xvcgpu_affine_me_listed": [_vp, _vp, _vp, _vp, C.c_int, _vp, C.POINTER(C.c_int32), _vp],
+        "xvcgpu_fp_affine_choice": [_vp, _vp, _vp, C.c_int, C.POINTER(FramePassAffineArgs)],
+        "xvcgpu_cu_info_from_affine_choice": [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int,
+                                              C.c_int, _vp],
+        "xvcgpu_frame_pass_affine": [_vp, C.POINTER(FramePassArgs), C.POINTER(FramePassAffineArgs),
+                                     _vp, C.c_int],
     }
     if "xvcgpu_me_plan_destroy" not in allow_missing or hasattr(lib, "xvcgpu_me_plan_destroy"):
         lib.xvcgpu_me_plan_destroy.restype = None

@@ -438,9 +438,10 @@ template <int NW>
 __device__ __forceinline__ void
 affine_me_body(const PlaneView &orig, const PlaneView &ref_arg, const PlaneView &ref_other_arg,
                int bd, const xvcgpu_affine_me_block *blocks, int n, xvcgpu_affine_me_result *out,
-               const RefTable *refs = nullptr, const uint8_t *slots = nullptr) {
+               const RefTable *refs = nullptr, const uint8_t *slots = nullptr, int job = -1) {
   __shared__ AffineMeShared<NW> s;
-  const int bi = blockIdx.x;
+  // (job >= 0: the job index handed in - affine_me_listed_kernel, k_fp_affine.h)
+  const int bi = job >= 0 ? job : (int)blockIdx.x;
   if (bi >= n) return;
   // (the *_refs form: slots[2 * job] = the searched picture, [2 * job + 1] = the other list's)
   int slot_s = 0, slot_o = 0;

@@ -33,6 +33,7 @@
 #include "k_cs_engine.h"
 #include "k_fp_bi_refs.h"
 #include "k_aqp.h"
+#include "k_fp_affine.h"
 #include "xvcgpu_internal.h"
 
 namespace {
@@ -2784,6 +2785,149 @@ xvcgpu_status xvcgpu_frame_pass_aqp(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_arg
   if (!q) return XVCGPU_INVALID_ARGUMENT;
   const xvcgpu_status st = plan ? fp_plan_check(ctx, a, plan) : XVCGPU_OK;
   return st != XVCGPU_OK ? st : frame_pass_impl(ctx, a, phases, plan, q);
+}
+
+/* ---- the P frame pass with affine motion (k_fp_affine.h) ---- */
+xvcgpu_status xvcgpu_fp_affine_boot(xvcgpu_ctx *ctx, const xvcgpu_me_result *d_results,
+                                    const int32_t *d_order, int n_listed, int pic_w,
+                                    int pic_h, xvcgpu_affine_me_block *d_affine) {
+  if (!ctx || n_listed < 0 || pic_w <= 0 || pic_h <= 0 ||
+      (n_listed && (!d_results || !d_order || !d_affine)))
+    return XVCGPU_INVALID_ARGUMENT;
+  if (n_listed == 0) return XVCGPU_OK;
+  // (the caller's word that the list names jobs of d_affine: no bound but int's)
+  hipLaunchKernelGGL(fp_affine_boot_kernel, dim3((n_listed + 255) / 256), dim3(256), 0,
+                     ctx->stream, d_results, d_order, n_listed, 0x7fffffff, pic_w, pic_h,
+                     d_affine);
+  CHECK_LAUNCH(ctx, "fp_affine_boot");
+  return XVCGPU_OK;
+}
+
+xvcgpu_status xvcgpu_affine_me_listed(xvcgpu_ctx *ctx, const xvcgpu_picture *orig,
+                                      const xvcgpu_picture *ref,
+                                      const xvcgpu_affine_me_block *d_blocks, int n,
+                                      const int32_t *d_order, const int32_t n_class[3],
+                                      xvcgpu_affine_me_result *d_results) {
+  if (!ctx || !orig || !ref || n < 0 || !n_class) return XVCGPU_INVALID_ARGUMENT;
+  if (orig->v.bd != ref->v.bd || orig->v.c[0].w != ref->v.c[0].w ||
+      orig->v.c[0].h != ref->v.c[0].h)
+    return XVCGPU_INVALID_ARGUMENT;
+  long long listed = 0;
+  for (int k = 0; k < 3; k++) {
+    if (n_class[k] < 0) return fail(ctx, XVCGPU_INVALID_ARGUMENT, "affine_me_listed: n_class");
+    listed += n_class[k];
+  }
+  if (listed > n) return fail(ctx, XVCGPU_INVALID_ARGUMENT, "affine_me_listed: n_class names more jobs than n");
+  if (listed && (!d_blocks || !d_order || !d_results)) return XVCGPU_INVALID_ARGUMENT;
+  // one instance per CU height (a wave per 8 rows of the block), over its run of the list
+  int first = 0;
+#define AFF_LISTED(NW, K)                                                                  \
+  if (n_class[K]) {                                                                        \
+    hipLaunchKernelGGL(affine_me_listed_kernel<NW>, dim3(n_class[K]), dim3(64 * NW), 0,    \
+                       ctx->stream, orig->v.c[0], ref->v.c[0], ref->v.bd, d_blocks, n,     \
+                       d_order + first, n_class[K], d_results);                            \
+    first += n_class[K];                                                                   \
+  }
+  AFF_LISTED(2, 0)
+  AFF_LISTED(4, 1)
+  AFF_LISTED(8, 2)
+#undef AFF_LISTED
+  CHECK_LAUNCH(ctx, "affine_me_listed");
+  return XVCGPU_OK;
+}
+
+xvcgpu_status xvcgpu_fp_affine_choice(xvcgpu_ctx *ctx, const xvcgpu_me_block *d_me,
+                                      const xvcgpu_me_result *d_results, int n_cus,
+                                      const xvcgpu_frame_pass_affine_args *f) {
+  if (!ctx || !f || n_cus < 0) return XVCGPU_INVALID_ARGUMENT;
+  if (n_cus && (!d_me || !d_results)) return XVCGPU_INVALID_ARGUMENT;
+  if (n_cus && (!f->d_affine || !f->d_affine_results || !f->d_choice || !f->d_inter))
+    return fail(ctx, XVCGPU_INVALID_ARGUMENT,
+                "fp_affine_choice: d_affine, d_affine_results, d_choice and d_inter");
+  if (n_cus == 0) return XVCGPU_OK;
+  hipLaunchKernelGGL(fp_affine_choice_kernel, dim3((n_cus + 255) / 256), dim3(256), 0,
+                     ctx->stream, d_me, d_results, n_cus, f->d_affine, f->d_affine_results,
+                     f->side_bits, f->d_choice, f->d_inter);
+  CHECK_LAUNCH(ctx, "fp_affine_choice");
+  return XVCGPU_OK;
+}
+
+xvcgpu_status xvcgpu_cu_info_from_affine_choice(
+    xvcgpu_ctx *ctx, const xvcgpu_me_block *d_me, const xvcgpu_fp_affine_result *d_choice,
+    const int32_t *d_nnz, const int32_t *d_luma_tx_index, int n, int qp_y, int qp_c,
+    int ref_poc, xvcgpu_cu_info *d_cus_own) {
+  if (!ctx || n < 0 || (n && (!d_me || !d_choice || !d_nnz || !d_cus_own)))
+    return XVCGPU_INVALID_ARGUMENT;
+  if (n == 0) return XVCGPU_OK;
+  hipLaunchKernelGGL(cu_info_from_affine_choice_kernel, dim3((n + 255) / 256), dim3(256), 0,
+                     ctx->stream, d_me, d_choice, d_nnz, d_luma_tx_index, n, qp_y, qp_c,
+                     ref_poc, d_cus_own);
+  CHECK_LAUNCH(ctx, "cu_info_from_affine_choice");
+  return XVCGPU_OK;
+}
+
+xvcgpu_status xvcgpu_frame_pass_affine(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_args *a,
+                                       const xvcgpu_frame_pass_affine_args *f,
+                                       const xvcgpu_me_plan *plan, int phases) {
+  if (!f) return XVCGPU_INVALID_ARGUMENT;
+  xvcgpu_status st = plan ? fp_plan_check(ctx, a, plan) : XVCGPU_OK;
+  FramePassForm r;
+  if (st == XVCGPU_OK) st = frame_pass_resolve(ctx, a, phases, plan, &r);
+  if (st != XVCGPU_OK) return st;
+  const int n = a->n_cus;
+  int listed = 0;
+#define FPA_NEED(cond, what) \
+  if (!(cond)) return fail(ctx, XVCGPU_INVALID_ARGUMENT, "frame_pass_affine: " what)
+  FPA_NEED(phases & XVC_FP_ENCODE, "phases: the second search belongs to XVC_FP_ENCODE");
+  FPA_NEED(n == a->n_cus_total && a->db_y_begin == 0 && a->db_y_end >= a->rec->h &&
+               a->dbh_y_end >= a->rec->h && a->ssd_y_begin == 0 && a->ssd_y_end >= a->rec->h,
+           "whole pictures only (no row shard)");
+  if (n > 0) {
+    FPA_NEED(a->form == XVC_FP_FORM_FWD_TRANSFORM || a->form == XVC_FP_FORM_RESIDUAL ||
+                 a->form == XVC_FP_FORM_RESIDUAL_RDOQ,
+             "the form must be one with a prediction picture: FWD_TRANSFORM, RESIDUAL or "
+             "RESIDUAL_RDOQ");
+    FPA_NEED(f->d_affine && f->d_affine_results && f->d_choice && f->d_inter,
+             "d_affine, d_affine_results, d_choice and d_inter");
+    FPA_NEED(f->n_class[0] >= 0 && f->n_class[1] >= 0 && f->n_class[2] >= 0 &&
+                 (long long)f->n_class[0] + f->n_class[1] + f->n_class[2] <= n,
+             "n_class: the d_order counts are negative or name more than n_cus CUs");
+    listed = f->n_class[0] + f->n_class[1] + f->n_class[2];
+    FPA_NEED(listed == 0 || f->d_order, "d_order");
+    FPA_NEED(a->rec->w == a->orig->w && a->rec->h == a->orig->h && a->rec->bd == a->orig->bd &&
+                 a->ref->w == a->orig->w && a->ref->h == a->orig->h && a->ref->bd == a->orig->bd,
+             "ref and rec must be pictures of orig's size and depth");
+    FPA_NEED(a->pred->w == a->orig->w && a->pred->h == a->orig->h && a->pred->bd == a->orig->bd,
+             "pred must be a picture of orig's size and depth");
+    FPA_NEED(!plan || plan->first[XVCGPU_ME_PLAN_UNSUPPORTED] == plan->first[XVCGPU_ME_PLAN_LIC16],
+             "the plan holds LIC jobs");
+  }
+#undef FPA_NEED
+  xvcgpu_picture *const rec = r.fused_tail ? a->scratch_rec : a->rec;
+  if (r.form) {
+    st = fp_search(ctx, a, a->ref, a->d_me, a->d_results, plan);
+    if (st != XVCGPU_OK) return st;   // (nothing behind a search that was refused)
+    if (listed) {
+      hipLaunchKernelGGL(fp_affine_boot_kernel, dim3((listed + 255) / 256), dim3(256), 0,
+                         ctx->stream, a->d_results, f->d_order, listed, n, a->orig->w,
+                         a->orig->h, f->d_affine);
+      CHECK_LAUNCH(ctx, "fp_affine_boot");
+      st = xvcgpu_affine_me_listed(ctx, a->orig, a->ref, f->d_affine, n, f->d_order, f->n_class,
+                                   f->d_affine_results);
+    }
+    if (st == XVCGPU_OK) st = xvcgpu_fp_affine_choice(ctx, a->d_me, a->d_results, n, f);
+    // (the prediction reads its `rec` for LIC jobs only: there are none)
+    const xvcgpu_picture *const refs[1] = {a->ref};
+    if (st == XVCGPU_OK)
+      st = xvcgpu_inter_pred_batch(ctx, refs, 1, a->rec, a->pred, f->d_inter, 3 * n);
+    if (st == XVCGPU_OK) st = fp_residual(ctx, a, rec, r.form);
+    if (st == XVCGPU_OK)
+      st = xvcgpu_cu_info_from_affine_choice(ctx, a->d_me, f->d_choice, a->d_nnz,
+                                             a->d_luma_tx_index, n, a->qp_y, a->qp_c, a->ref_poc,
+                                             a->d_cus_own);
+  }
+  if (st == XVCGPU_OK) st = fp_tail(ctx, a, phases, r.fused_tail, 0);
+  return st;
 }
 
 /* ---- several pictures per call: every kernel launched once for all of them ---- */

@@ -218,6 +218,7 @@ class FramePass {
   // and transform blocks (RESIDUAL), which is the one that reads a QP per block; its
   // transform blocks are made here where the grid's fused form had none.
   void SetAdaptiveQp(int aqp_strength) {
+    if (affine_) throw Error(XVCGPU_INVALID_ARGUMENT, "SetAdaptiveQp: not together with SetAffine");
     aqp_.reset(new AdaptiveQpArrays(ctx_, w_, h_, bd_, qp_, aqp_strength, n_cus_));
     if (!d_tx_) {
       std::vector<xvcgpu_tx_block> tx;
@@ -232,6 +233,84 @@ class FramePass {
     }
     form_ = XVC_FP_FORM_RESIDUAL;
   }
+  // What a pass with affine motion takes beside the flat pass's jobs, on the host
+  // (pipeline.FrameDescriptors.affine_jobs / affine_order: the same bytes): one job per CU
+  // in CU order with the plain job's lambda16 and predictor (mvp_x, mvp_y at every corner),
+  // the indices of the capable CUs - w and h each 16, 32 or 64 (CodingUnit::CanUseAffine,
+  // coding_unit.h:251-257) - grouped by CU height 16, 32, 64 in CU order, and the args
+  // block with the counts and side_bits (its pointers null).
+  static xvcgpu_frame_pass_affine_args AffineJobs(const std::vector<CuRect> &rects,
+                                                  uint32_t lambda16, int mvp_x, int mvp_y,
+                                                  uint32_t side_bits,
+                                                  std::vector<xvcgpu_affine_me_block> *jobs,
+                                                  std::vector<int32_t> *order) {
+    xvcgpu_frame_pass_affine_args f = xvcgpu_frame_pass_affine_args();
+    f.side_bits = side_bits;
+    jobs->clear();
+    order->clear();
+    for (size_t i = 0; i < rects.size(); i++) {
+      xvcgpu_affine_me_block b = xvcgpu_affine_me_block();
+      b.x = static_cast<int16_t>(rects[i].x);
+      b.y = static_cast<int16_t>(rects[i].y);
+      b.w = static_cast<uint8_t>(rects[i].w);
+      b.h = static_cast<uint8_t>(rects[i].h);
+      b.lambda16 = lambda16;
+      for (int k = 0; k < 3; k++) {
+        b.mvp[k][0] = mvp_x;
+        b.mvp[k][1] = mvp_y;
+      }
+      jobs->push_back(b);
+    }
+    for (int cls = 0; cls < 3; cls++)
+      for (size_t i = 0; i < rects.size(); i++) {
+        const int w = rects[i].w, h = rects[i].h;
+        if ((w == 16 || w == 32 || w == 64) && h == (16 << cls)) {
+          order->push_back(static_cast<int32_t>(i));
+          f.n_class[cls]++;
+        }
+      }
+    return f;
+  }
+
+  // From now on every Run searches the CUs with both sides above 8 a second time with the
+  // three-corner affine model, bootstrapped from the translational vector, and keeps the
+  // cheaper state (InterSearch::CompressInter, inter_search.cc:74-99;
+  // xvcgpu_frame_pass_affine).  The pass takes the form with a prediction picture and
+  // transform blocks (RESIDUAL); they are made here where the grid's fused form had none.
+  // Not together with SetAdaptiveQp.
+  void SetAffine(uint32_t side_bits = 1) {
+    if (aqp_) throw Error(XVCGPU_INVALID_ARGUMENT, "SetAffine: not together with SetAdaptiveQp");
+    std::vector<xvcgpu_affine_me_block> jobs;
+    std::vector<int32_t> order;
+    affine_args_ = AffineJobs(rects_, Lambda16(qp_), 0, 0, side_bits, &jobs, &order);
+    if (order.empty()) order.push_back(0);   // (no empty device array; the counts say none)
+    d_affine_.reset(new DeviceArray<xvcgpu_affine_me_block>(ctx_, jobs));
+    d_order_.reset(new DeviceArray<int32_t>(ctx_, order));
+    d_affine_res_.reset(new DeviceArray<xvcgpu_affine_me_result>(ctx_, jobs.size()));
+    d_choice_.reset(new DeviceArray<xvcgpu_fp_affine_result>(ctx_, jobs.size()));
+    d_inter_.reset(new DeviceArray<xvcgpu_inter_block>(ctx_, 3 * jobs.size()));
+    affine_args_.d_affine = d_affine_->data();
+    affine_args_.d_order = d_order_->data();
+    affine_args_.d_affine_results = d_affine_res_->data();
+    affine_args_.d_choice = d_choice_->data();
+    affine_args_.d_inter = d_inter_->data();
+    if (!d_tx_) {
+      std::vector<xvcgpu_tx_block> tx;
+      std::vector<int32_t> luma;
+      for (size_t i = 0; i < rects_.size(); i++) {
+        luma.push_back(static_cast<int32_t>(3 * i));
+        for (int c = 0; c < 3; c++) tx.push_back(TxBlockOf(rects_[i], c, c ? qp_c_ : qp_));
+      }
+      d_tx_.reset(new DeviceArray<xvcgpu_tx_block>(ctx_, tx));
+      d_luma_.reset(new DeviceArray<int32_t>(ctx_, luma));
+      pred_.reset(new Picture(ctx_, w_, h_, bd_));
+    }
+    form_ = XVC_FP_FORM_RESIDUAL;
+    affine_ = true;
+  }
+  // the last Run's record per CU (synchronises)
+  std::vector<xvcgpu_fp_affine_result> AffineChoice() const { return d_choice_->ToHost(); }
+
   // the last Run's delta per CTU (raster order) and {qp_y, qp_c} per CU (synchronise)
   std::vector<int8_t> CtuDeltaQp() const { return aqp_->CtuDeltaQp(); }
   std::vector<int8_t> CuQp() const { return aqp_->CuQp(); }
@@ -268,11 +347,15 @@ class FramePass {
     a.form = form_;
     const int phases = XVC_FP_ENCODE | XVC_FP_DEBLOCK_V | XVC_FP_DEBLOCK_H | XVC_FP_PAD |
                        XVC_FP_SSD;
-    if (plan_ || aqp_) {   // the residual form's arguments
+    if (plan_ || aqp_ || affine_) {   // the residual form's arguments
       a.pred = pred_->get();
       a.d_tx = d_tx_->data();
       a.n_tx = 3 * n_cus_;
       a.d_luma_tx_index = d_luma_->data();
+    }
+    if (affine_) {
+      ctx_.Check(xvcgpu_frame_pass_affine(ctx_.get(), &a, &affine_args_, plan_, phases));
+      return;
     }
     if (aqp_) {
       ctx_.Check(xvcgpu_frame_pass_aqp(ctx_.get(), &a, aqp_->args(), plan_, phases));
@@ -328,6 +411,13 @@ class FramePass {
   xvcgpu_me_plan *plan_;
   std::vector<CuRect> rects_;   // the CUs, in list order
   std::unique_ptr<AdaptiveQpArrays> aqp_;
+  bool affine_ = false;
+  xvcgpu_frame_pass_affine_args affine_args_;
+  std::unique_ptr<DeviceArray<xvcgpu_affine_me_block>> d_affine_;
+  std::unique_ptr<DeviceArray<int32_t>> d_order_;
+  std::unique_ptr<DeviceArray<xvcgpu_affine_me_result>> d_affine_res_;
+  std::unique_ptr<DeviceArray<xvcgpu_fp_affine_result>> d_choice_;
+  std::unique_ptr<DeviceArray<xvcgpu_inter_block>> d_inter_;
   std::unique_ptr<DeviceArray<xvcgpu_tx_block>> d_tx_;
   std::unique_ptr<DeviceArray<int32_t>> d_luma_;
   std::unique_ptr<Picture> pred_;

@@ -169,7 +169,65 @@ class _AqpArrays:
             b.free()
 
 
+class _AffineArrays:
+    """What a pass with affine motion holds beside the flat pass's state: the arrays of
+    xvcgpu_frame_pass_affine_args (allocated once; every run writes the work arrays)."""
+
+    def __init__(self, ctx, desc, mvp=None, side_bits=1):
+        self.ctx, self.n_cus, self.side_bits = ctx, desc.n_cus, side_bits
+        self.jobs, self.order, self.n_class = desc.affine_jobs(mvp)
+        n = max(1, desc.n_cus)
+        self.d_affine = ctx.buffer(self.jobs) if desc.n_cus else ctx.alloc(api.AFFINE_ME_DTYPE.itemsize)
+        self.d_affine_res = ctx.buffer(np.zeros(n, api.AFFINE_ME_RESULT_DTYPE))
+        self.d_order = ctx.buffer(self.order) if len(self.order) else None
+        self.d_choice = ctx.buffer(np.zeros(n, api.FP_AFFINE_RESULT_DTYPE))
+        self.d_inter = ctx.buffer(np.zeros(3 * n, api.INTER_DTYPE))
+
+    def args(self):
+        f = api.FramePassAffineArgs()
+        f.d_affine, f.d_affine_results = self.d_affine.ptr, self.d_affine_res.ptr
+        f.d_order = self.d_order.ptr if self.d_order is not None else None
+        f.n_class[:] = self.n_class
+        f.side_bits = self.side_bits
+        f.d_choice, f.d_inter = self.d_choice.ptr, self.d_inter.ptr
+        return f
+
+    def choice(self):
+        return self.d_choice.to_array(api.FP_AFFINE_RESULT_DTYPE, self.n_cus)
+
+    def affine_results(self):
+        return self.d_affine_res.to_array(api.AFFINE_ME_RESULT_DTYPE, self.n_cus)
+
+    def affine_blocks(self):
+        return self.d_affine.to_array(api.AFFINE_ME_DTYPE, self.n_cus)
+
+    def inter_jobs(self):
+        return self.d_inter.to_array(api.INTER_DTYPE, 3 * self.n_cus)
+
+    def free(self):
+        for b in (self.d_affine, self.d_affine_res, self.d_order, self.d_choice, self.d_inter):
+            if b is not None:
+                b.free()
+
+
 _AQP_FORMS = ("fwd_transform", "residual", "residual_rdoq")
+
+
+_AFFINE_SIDES = (16, 32, 64)
+
+
+def affine_order(me):
+    """The order list of xvcgpu_frame_pass_affine_args for the jobs `me` (api.ME_DTYPE):
+    (d_order int32 - the indices of the CUs the second, affine SearchMotion run takes,
+    grouped by CU height 16, 32, 64 and in CU order inside a group -, n_class [3]).  A CU is
+    capable if w and h are each 16, 32 or 64 (CodingUnit::CanUseAffine, coding_unit.h:251-257)
+    and its job carries neither ME_FULLPEL_MV nor ME_USE_LIC.  The same list as
+    xvc_gpu::FramePass::SetAffine makes."""
+    ok = np.isin(me["w"], _AFFINE_SIDES) & np.isin(me["h"], _AFFINE_SIDES) & \
+        ((me["fullpel_mv"] & 3) == 0)
+    groups = [np.flatnonzero(ok & (me["h"] == h)) for h in _AFFINE_SIDES]
+    return (np.concatenate(groups).astype(np.int32) if len(me) else np.zeros(0, np.int32),
+            [len(g) for g in groups])
 
 
 def cu_partition(width, height, cu=16, xcd_tiles=False):
@@ -326,6 +384,22 @@ class FrameDescriptors:
         self.cus_per_row = (width + cu - 1) // cu
         self.cu_size = cu
 
+    def affine_jobs(self, mvp=None):
+        """What a pass with affine motion (xvcgpu_frame_pass_affine) takes beside these
+        descriptors: (one api.AFFINE_ME_DTYPE job per own CU in CU order - x, y, w, h and
+        lambda16 of the plain job, mvp [n, 3, 2] or, None, the plain job's mvp at every
+        corner; flags and bootstrap are the device's -, d_order, n_class: affine_order)."""
+        jobs = np.zeros(self.n_cus, api.AFFINE_ME_DTYPE)
+        for k in ("x", "y", "w", "h", "lambda16"):
+            jobs[k] = self.me[k]
+        if mvp is None:
+            jobs["mvp"][:, :, 0] = self.me["mvp_x"][:, None]
+            jobs["mvp"][:, :, 1] = self.me["mvp_y"][:, None]
+        else:
+            jobs["mvp"] = np.asarray(mvp, np.int32).reshape(self.n_cus, 3, 2)
+        order, n_class = affine_order(self.me)
+        return jobs, order, n_class
+
 
 def run_multi(passes, origs, refs, recs, ref_pocs=None):
     """The frame passes of len(passes) independent pictures with every kernel
@@ -335,6 +409,8 @@ def run_multi(passes, origs, refs, recs, ref_pocs=None):
     other contexts on it).  Passes over a partition (FramePass(partition=...)) are not
     batched: with one among them every pass is run by its own single call."""
     n = len(passes)
+    if any(getattr(p, "affine", None) is not None for p in passes):
+        raise ValueError("run_multi: a pass with affine motion has no multi-picture form")
     if any(p.plan is not None for p in passes):
         for i, p in enumerate(passes):
             p.run(origs[i], refs[i], recs[i], ref_pocs[i] if ref_pocs is not None else 0)
@@ -375,15 +451,25 @@ class FramePass:
     gets qp + its delta, derived on the device from orig in front of the search and written
     into this object's job arrays; whole pictures, forms `fwd_transform`, `residual` and
     `residual_rdoq` (else ValueError).  ctu_delta_qp() and cu_qp() read the last run's map
-    back."""
+    back.
+
+    affine=True: the pass with affine motion (xvcgpu_frame_pass_affine): every CU with both
+    sides above 8 is searched a second time with the three-corner model, bootstrapped from
+    its translational vector, and keeps the cheaper state (InterSearch::CompressInter).
+    Whole pictures, the forms with a prediction picture (`fwd_transform`, `residual`,
+    `residual_rdoq`; else ValueError), not together with aqp_strength and not through
+    run_multi.  affine_mvp: the jobs' corner predictors [n_cus, 3, 2]; None: the plain
+    job's mvp at every corner.  side_bits: 1, a picture with one list.  affine_choice()
+    reads the last run's records back."""
 
     def __init__(self, ctx, width, height, bitdepth=10, qp=32, cu=16,
                  search_range=96, row_range=None, fused=True, keep_levels=False,
                  rdoq=False, rdoq_packed=None, xcd_tiles=False, partition=None, form=None,
-                 aqp_strength=None):
+                 aqp_strength=None, affine=False, affine_mvp=None, side_bits=1):
         self.ctx = ctx
         self.plan = None
         self.aqp = None
+        self.affine = None
         self.rdoq = rdoq
         # RDOQ keeps only a few lanes of a wave busy per block, so its own kernel
         # packs several blocks into a wave (xvcgpu_quant_rdo_batch) between the
@@ -425,6 +511,15 @@ class FramePass:
                 raise ValueError("aqp_strength: whole pictures only (no row_range)")
             aqp_table(qp, bitdepth, aqp_strength, width)    # (a refused strength: before
             #                                                  anything is allocated)
+        if affine:
+            if aqp_strength is not None:
+                raise ValueError("affine: not together with aqp_strength (out of scope)")
+            if self.form not in _AQP_FORMS:
+                raise ValueError("affine: the form %r predicts inside its kernels; a pass with "
+                                 "affine motion runs %s (fused=False, keep_levels=True or "
+                                 "form=\"fwd_transform\")" % (self.form, ", ".join(_AQP_FORMS)))
+            if d.row_range != (0, d.h):
+                raise ValueError("affine: whole pictures only (no row_range)")
         self.d_rdoq_ctx = ctx.buffer(d.rdoq_contexts) if rdoq else None
         self.d_rdoq_prm = ctx.buffer(d.rdoq_params) if rdoq else None
         self.d_me = ctx.buffer(d.me)
@@ -482,6 +577,8 @@ class FramePass:
             ctx._check(ctx.lib.xvcgpu_quant_rdo_reserve(ctx.h, len(d.tx), self.n_levels))
         if aqp_strength is not None:
             self.aqp = _AqpArrays(ctx, d, bitdepth, aqp_strength)
+        if affine:
+            self.affine = _AffineArrays(ctx, d, affine_mvp, side_bits)
 
     @property
     def d_cus_own(self):
@@ -544,6 +641,12 @@ class FramePass:
                 self.ctx.h, C.byref(a), C.byref(q), self.plan.h if self.plan is not None else None,
                 phases))
             return
+        if self.affine is not None:
+            f = self.affine.args()
+            self.ctx._check(self.ctx.lib.xvcgpu_frame_pass_affine(
+                self.ctx.h, C.byref(a), C.byref(f), self.plan.h if self.plan is not None else None,
+                phases))
+            return
         if self.plan is not None:
             self.ctx._check(self.ctx.lib.xvcgpu_frame_pass_planned(self.ctx.h, C.byref(a),
                                                                    self.plan.h, phases))
@@ -562,6 +665,8 @@ class FramePass:
         "quant_rdo" is the class lists and the walk: rdoq_lists_kernel (one launch; batches
         above XVCGPU_RDOQ_ONE_LAUNCH_LISTS_MAX_BLOCKS: rdoq_count_kernel + rdoq_scatter_kernel,
         xvcgpu_quant_rdo_set_list_form) -> quant_rdo_packed4_kernel [-> quant_rdo_packed_kernel]."""
+        if self.affine is not None:     # (these are the flat pass's launches)
+            raise ValueError("a pass with affine motion runs through run() / run_phases() only")
         ctx, d, lib = self.ctx, self.desc, self.ctx.lib
         n, T, bd, form = d.n_cus, len(d.tx), self.bd, self.form
         out = self.scratch if fused_tail else rec
@@ -677,10 +782,17 @@ class FramePass:
         """Adaptive QP: the last run's (qp_y, qp_c) per CU, [n_cus, 2] int8."""
         return self.aqp.cu_qp()
 
+    def affine_choice(self):
+        """Affine motion: the last run's api.FP_AFFINE_RESULT_DTYPE record per CU."""
+        return self.affine.choice()
+
     def destroy(self):
         if self.aqp is not None:
             self.aqp.free()
             self.aqp = None
+        if self.affine is not None:
+            self.affine.free()
+            self.affine = None
         for b in (self.d_me, self.d_tx, self.d_luma_idx, self.d_map, self.d_res,
                   self.d_nnz, self.d_cus, self.d_ssd, self.d_levels, self.d_level_off,
                   self.d_rdoq_ctx, self.d_rdoq_prm, self.d_coeffs):
