@@ -1376,6 +1376,58 @@ xvcgpu_status xvcgpu_frame_pass_bi_refs_aqp(
     xvcgpu_ctx *ctx, const xvcgpu_frame_pass_bi_refs_args *b, const xvcgpu_aqp_args *q,
     const xvcgpu_me_plan *const plans[2][XVC_CS_MAX_REFS], int phases);
 
+/* ---- the frame pass of a B picture with only back references ---------------------- *
+ * Every inter picture of a low-delay encode is a B picture whose two lists hold earlier
+ * pictures only (PictureData::DetermineForceBipredL1MvdZero).  SearchMotion then codes list 1
+ * of a bi-directional CU without a vector difference, and differs from the pass above so
+ * (inter_search.cc):
+ *   - list 1, uni-directional (:470-471, :496-524): the candidate of picture r is the job's
+ *     mvp itself, kept unclipped, priced by EvalStartMvp (:967-997) = SAD(orig, luma
+ *     prediction at ClipMv(mvp)) + ((GetMvpBits(0, 2) * lambda16) >> 16) = SAD + (lambda16 >>
+ *     16); the best on strict < in index order is cost_list[1] / best_ref[1].  A re-used
+ *     picture is then done (neither searched nor priced from list 0's result); a unique one
+ *     is searched as above and priced into cost_l1_unique / best_ref_l1_unique only.
+ *   - SearchBiIterative (:410-413): one iteration, search_list = 0 whatever the costs say:
+ *     every picture k of list 0 is refined against the mvp of d_me[1][best_ref[1]],
+ *     bootstrapped from list 0's own vector of k.
+ *   - the bits of a bi-directional state: list 1 adds RefIdxBits + 1 and no vector-difference
+ *     bits (GetForceMvdZero).
+ *   - ChooseUniOrBi(cost_l0, cost_l1_unique, cost_bi) as above; a bi-directional CU's mv[1]
+ *     is that mvp, a list-1 CU's the unique picture's searched vector.
+ * xvcgpu_frame_pass_bi_back is xvcgpu_frame_pass_bi_refs (q NULL) or
+ * xvcgpu_frame_pass_bi_refs_aqp (q given: the apply launch in front reaches lambda16 of every
+ * d_me[l][r], which the predictor cost reads) with xvcgpu_fp_bi_back_mvp_cost in front of
+ * the fold and the two folds below in place of steps 2 and 4; the searches, the refinement
+ * launches, the prediction, the residual pipeline, xvcgpu_cu_info_from_choice_refs and the
+ * tail are used as they are.  The args block is the same and must carry force_l1_mvd_zero =
+ * 1: a block with 0 is refused naming the field (the block holds no current POC, so the flag
+ * is the caller's word).  Every check of the pass above (the flag's aside) and a missing
+ * d_l1_mvp_cost are refused before the first launch; after the checks the call only enqueues.
+ * The record stays xvcgpu_fp_bi_refs_result with search_list = 0 and cost_uni[1][r] the
+ * predictor's cost.
+ *
+ * xvcgpu_fp_bi_back_mvp_cost: one launch over all (CU, list-1 picture), one wave each:
+ * d_l1_mvp_cost[i * XVC_CS_MAX_REFS + r] = the price above of d_me[1][r][i] on
+ * refs[slot[1][r]] (reads p.orig, refs, n_refs, the tables); r >= num_ref[1]: UINT32_MAX.
+ * Every CU shape with w, h in {4, 8, 16, 32, 64} is taken; any other gets UINT32_MAX.
+ * xvcgpu_fp_bi_back_uni_fold: list 0 as xvcgpu_fp_bi_refs_uni_fold; list 1 from
+ * d_l1_mvp_cost; job [i * Rmax + k], k < num_ref[0]: blk = d_me[0][k][i], boot_mv = list 0's
+ * vector of k, other_mv = the mvp of d_me[1][best_ref[1]][i], slot bytes {slot[0][k],
+ * slot[1][best_ref[1]]}; k >= num_ref[0]: XVC_FP_BI_NO_JOB.  A CU with an unsupported search
+ * result or predictor cost: the record all ones, no job.
+ * xvcgpu_fp_bi_back_choice: xvcgpu_fp_bi_refs_choice with the bits and vectors above. */
+xvcgpu_status xvcgpu_fp_bi_back_mvp_cost(xvcgpu_ctx *ctx,
+                                         const xvcgpu_frame_pass_bi_refs_args *a,
+                                         uint32_t *d_l1_mvp_cost);
+xvcgpu_status xvcgpu_fp_bi_back_uni_fold(xvcgpu_ctx *ctx,
+                                         const xvcgpu_frame_pass_bi_refs_args *a,
+                                         const uint32_t *d_l1_mvp_cost);
+xvcgpu_status xvcgpu_fp_bi_back_choice(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_bi_refs_args *a);
+xvcgpu_status xvcgpu_frame_pass_bi_back(
+    xvcgpu_ctx *ctx, const xvcgpu_frame_pass_bi_refs_args *a, uint32_t *d_l1_mvp_cost,
+    const xvcgpu_aqp_args *q /* NULL: one QP */,
+    const xvcgpu_me_plan *const plans[2][XVC_CS_MAX_REFS], int phases);
+
 /* ---- the P frame pass with affine motion ---------------------------------------- *
  * InterSearch::CompressInter (inter_search.cc:74-99): every CU that CanUseAffine is searched
  * twice, translational and with the three-corner model, and keeps the cheaper state.  The

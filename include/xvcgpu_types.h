@@ -641,7 +641,8 @@ typedef struct xvcgpu_frame_pass_bi_refs_args {
   int8_t same_poc_in_l0[XVC_CS_MAX_REFS];   /* list-1 picture r: the list-0 index of the
                                              * same picture (re-used: not searched), or -1 */
   uint8_t force_l1_mvd_zero;                /* PictureData::DetermineForceBipredL1MvdZero;
-                                             * set: refused (out of scope)               */
+                                             * set: refused by xvcgpu_frame_pass_bi_refs,
+                                             * wanted (1) by xvcgpu_frame_pass_bi_back   */
   int32_t n_refs;                           /* 1 .. XVC_FP_BI_MAX_REF_PICS               */
   const struct xvcgpu_picture *refs[XVC_FP_BI_MAX_REF_PICS]; /* the distinct pictures    */
   uint8_t slot[2][XVC_CS_MAX_REFS];         /* (list, picture) -> index into refs; a

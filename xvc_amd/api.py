@@ -275,6 +275,8 @@ SYMBOLS = [
     "xvcgpu_bipred_search_refs_planned", "xvcgpu_frame_pass_bi_refs",
     "xvcgpu_aqp_apply", "xvcgpu_cu_info_set_qp", "xvcgpu_frame_pass_aqp",
     "xvcgpu_frame_pass_bi_refs_aqp",
+    "xvcgpu_fp_bi_back_mvp_cost", "xvcgpu_fp_bi_back_uni_fold", "xvcgpu_fp_bi_back_choice",
+    "xvcgpu_frame_pass_bi_back",
     "xvcgpu_fp_affine_boot", "xvcgpu_affine_me_listed", "xvcgpu_fp_affine_choice",
     "xvcgpu_cu_info_from_affine_choice", "xvcgpu_frame_pass_affine",
 ]
@@ -493,6 +495,12 @@ def load_library(allow_missing=()):
         "xvcgpu_frame_pass_aqp": [_vp, C.POINTER(FramePassArgs), C.POINTER(AqpArgs), _vp, C.c_int],
         "xvcgpu_frame_pass_bi_refs_aqp": [_vp, C.POINTER(FramePassBiRefsArgs), C.POINTER(AqpArgs),
                                           _vp, C.c_int],
+        "xvcgpu_fp_bi_back_mvp_cost": [_vp, C.POINTER(FramePassBiRefsArgs), _vp],
+        "xvcgpu_fp_bi_back_uni_fold": [_vp, C.POINTER(FramePassBiRefsArgs), _vp],
+        "xvcgpu_fp_bi_back_choice": [_vp, C.POINTER(FramePassBiRefsArgs)],
+        # (q: a pointer to AqpArgs, or None for one QP)
+        "xvcgpu_frame_pass_bi_back": [_vp, C.POINTER(FramePassBiRefsArgs), _vp,
+                                      C.POINTER(AqpArgs), _vp, C.c_int],
         "xvcgpu_fp_affine_boot": [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp],
         "xvcgpu_affine_me_listed": [_vp, _vp, _vp, _vp, C.c_int, _vp, C.POINTER(C.c_int32), _vp],
         "xvcgpu_fp_affine_choice": [_vp, _vp, _vp, C.c_int, C.POINTER(FramePassAffineArgs)],

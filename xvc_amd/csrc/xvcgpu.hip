@@ -32,6 +32,7 @@
 #include "k_cu_state.h"
 #include "k_cs_engine.h"
 #include "k_fp_bi_refs.h"
+#include "k_fp_bi_back.h"
 #include "k_aqp.h"
 #include "k_fp_affine.h"
 #include "xvcgpu_internal.h"
@@ -3290,9 +3291,10 @@ xvcgpu_status xvcgpu_bipred_search_refs_planned(xvcgpu_ctx *ctx, const xvcgpu_pi
 
 /* ---- the frame pass of a B picture (k_fp_bi_refs.h) ---- */
 // The tables of the args block checked (*what names the field of a refusal) and turned into
-// the kernels' form
+// the kernels' form.  back: the entries of k_fp_bi_back.h, which run the rule of a picture
+// with only back references and take no other block
 static bool fp_bi_refs_tables(const xvcgpu_frame_pass_bi_refs_args *b, FpBiRefsDev *t,
-                              const char **what) {
+                              const char **what, bool back = false) {
 #define FPR_NEED(cond, text) \
   if (!(cond)) {             \
     *what = text;            \
@@ -3302,8 +3304,11 @@ static bool fp_bi_refs_tables(const xvcgpu_frame_pass_bi_refs_args *b, FpBiRefsD
   for (int l = 0; l < 2; l++)
     FPR_NEED(b->num_ref[l] >= 1 && b->num_ref[l] <= XVC_CS_MAX_REFS,
              "num_ref must be 1 .. XVC_CS_MAX_REFS per list");
-  FPR_NEED(!b->force_l1_mvd_zero,
+  FPR_NEED(back || !b->force_l1_mvd_zero,
            "force_l1_mvd_zero: pictures with only back references are out of scope");
+  FPR_NEED(!back || b->force_l1_mvd_zero == 1,
+           "force_l1_mvd_zero must be 1: this entry runs the rule of a picture with only back "
+           "references");
   FPR_NEED(b->n_refs >= 1 && b->n_refs <= XVC_FP_BI_MAX_REF_PICS,
            "n_refs must be 1 .. XVC_FP_BI_MAX_REF_PICS");
   for (int r = 0; r < b->num_ref[1]; r++) {
@@ -3384,11 +3389,16 @@ xvcgpu_status xvcgpu_cu_info_from_choice_refs(xvcgpu_ctx *ctx,
   return XVCGPU_OK;
 }
 
-// q: null = one QP (xvcgpu_frame_pass_bi_refs), else xvcgpu_frame_pass_bi_refs_aqp
+// q: null = one QP (xvcgpu_frame_pass_bi_refs), else xvcgpu_frame_pass_bi_refs_aqp.
+// entry: the name in front of a refusal.  back: xvcgpu_frame_pass_bi_back - the folds of
+// k_fp_bi_back.h, with the predictor-cost launch into d_l1_mvp_cost in front of them.
 static xvcgpu_status frame_pass_bi_refs_impl(xvcgpu_ctx *ctx,
                                              const xvcgpu_frame_pass_bi_refs_args *b,
                                              const xvcgpu_me_plan *const plans[2][XVC_CS_MAX_REFS],
-                                             int phases, const xvcgpu_aqp_args *q) {
+                                             int phases, const xvcgpu_aqp_args *q,
+                                             const char *entry = "frame_pass_bi_refs",
+                                             bool back = false,
+                                             uint32_t *d_l1_mvp_cost = nullptr) {
   if (!ctx || !b || !b->p.rec) return XVCGPU_INVALID_ARGUMENT;
   // the P pass's block with list 0's first picture in the fields the shared helpers read
   xvcgpu_frame_pass_args pa = b->p;
@@ -3396,8 +3406,12 @@ static xvcgpu_status frame_pass_bi_refs_impl(xvcgpu_ctx *ctx,
   const int n = a->n_cus;
   FpBiRefsDev t;
   const xvcgpu_me_plan *plan0 = nullptr;
-#define FPB_NEED(cond, what) \
-  if (!(cond)) return fail(ctx, XVCGPU_INVALID_ARGUMENT, "frame_pass_bi_refs: " what)
+#define FPB_NEED(cond, what)                               \
+  if (!(cond)) {                                           \
+    char msg_[240];                                        \
+    snprintf(msg_, sizeof(msg_), "%s: %s", entry, what);   \
+    return fail(ctx, XVCGPU_INVALID_ARGUMENT, msg_);       \
+  }
   FPB_NEED(n == a->n_cus_total && a->db_y_begin == 0 && a->db_y_end >= a->rec->h &&
                a->dbh_y_end >= a->rec->h && a->ssd_y_begin == 0 && a->ssd_y_end >= a->rec->h,
            "whole pictures only (no row shard)");
@@ -3407,11 +3421,12 @@ static xvcgpu_status frame_pass_bi_refs_impl(xvcgpu_ctx *ctx,
              "the form must be one with a prediction picture: FWD_TRANSFORM, RESIDUAL or "
              "RESIDUAL_RDOQ");
     const char *what = nullptr;
-    if (!fp_bi_refs_tables(b, &t, &what)) {
-      char msg[200];
-      snprintf(msg, sizeof(msg), "frame_pass_bi_refs: %s", what);
+    if (!fp_bi_refs_tables(b, &t, &what, back)) {
+      char msg[240];
+      snprintf(msg, sizeof(msg), "%s: %s", entry, what);
       return fail(ctx, XVCGPU_INVALID_ARGUMENT, msg);
     }
+    FPB_NEED(!back || d_l1_mvp_cost, "d_l1_mvp_cost");
     FPB_NEED(a->orig, "orig");
     for (int k = 0; k < b->n_refs; k++)
       FPB_NEED(b->refs[k] && b->refs[k]->w == a->orig->w && b->refs[k]->h == a->orig->h &&
@@ -3464,7 +3479,10 @@ static xvcgpu_status frame_pass_bi_refs_impl(xvcgpu_ctx *ctx,
         st = fp_search(ctx, a, b->refs[b->slot[l][q]], b->d_me[l][q], b->d_results[l][q],
                        plan0 ? plans[l][q] : nullptr);
       }
-    if (st == XVCGPU_OK) st = xvcgpu_fp_bi_refs_uni_fold(ctx, b);
+    if (st == XVCGPU_OK && back) st = xvcgpu_fp_bi_back_mvp_cost(ctx, b, d_l1_mvp_cost);
+    if (st == XVCGPU_OK)
+      st = back ? xvcgpu_fp_bi_back_uni_fold(ctx, b, d_l1_mvp_cost)
+                : xvcgpu_fp_bi_refs_uni_fold(ctx, b);
     // SearchBiIterative's one step of every CU into every picture of its searched list
     if (st == XVCGPU_OK && plan0)
       st = xvcgpu_bipred_search_refs_planned(ctx, a->orig, b->refs, b->n_refs, plan0, t.rmax,
@@ -3473,7 +3491,8 @@ static xvcgpu_status frame_pass_bi_refs_impl(xvcgpu_ctx *ctx,
          cls *= 2)
       st = xvcgpu_bipred_search_refs(ctx, a->orig, b->refs, b->n_refs, b->d_bi_jobs,
                                      b->d_bi_slots, n * t.rmax, b->d_bi_results, cls);
-    if (st == XVCGPU_OK) st = xvcgpu_fp_bi_refs_choice(ctx, b);
+    if (st == XVCGPU_OK)
+      st = back ? xvcgpu_fp_bi_back_choice(ctx, b) : xvcgpu_fp_bi_refs_choice(ctx, b);
     // (the prediction reads its `rec` for LIC jobs only: there are none)
     if (st == XVCGPU_OK)
       st = xvcgpu_inter_pred_batch(ctx, b->refs, b->n_refs, a->rec, a->pred, b->d_inter, 3 * n);
@@ -3496,6 +3515,74 @@ xvcgpu_status xvcgpu_frame_pass_bi_refs_aqp(
     const xvcgpu_me_plan *const plans[2][XVC_CS_MAX_REFS], int phases) {
   if (!q) return XVCGPU_INVALID_ARGUMENT;
   return frame_pass_bi_refs_impl(ctx, b, plans, phases, q);
+}
+
+/* ---- the frame pass of a B picture with only back references (k_fp_bi_back.h) ---- */
+xvcgpu_status xvcgpu_fp_bi_back_mvp_cost(xvcgpu_ctx *ctx,
+                                         const xvcgpu_frame_pass_bi_refs_args *b,
+                                         uint32_t *d_l1_mvp_cost) {
+  if (!ctx || !b || b->p.n_cus < 0) return XVCGPU_INVALID_ARGUMENT;
+  FpBiRefsDev t;
+  const char *what = nullptr;
+  if (!fp_bi_refs_tables(b, &t, &what, true)) return fail(ctx, XVCGPU_INVALID_ARGUMENT, what);
+  if (!d_l1_mvp_cost || !b->p.orig)
+    return fail(ctx, XVCGPU_INVALID_ARGUMENT, "fp_bi_back_mvp_cost: d_l1_mvp_cost and p.orig");
+  RefTable refs;
+  const xvcgpu_status st = ref_table_of(ctx, b->p.orig, b->refs, b->n_refs, &refs);
+  if (st != XVCGPU_OK) return st;
+  const int n = b->p.n_cus;
+  if (n == 0) return XVCGPU_OK;
+  FpBiBackL1 l1;
+  memset(&l1, 0, sizeof(l1));
+  l1.num_ref = t.num_ref[1];
+  for (int r = 0; r < t.num_ref[1]; r++) {
+    l1.me[r] = t.me[1][r];
+    l1.slot[r] = t.slot[1][r];
+  }
+  const int waves = n * l1.num_ref;
+  hipLaunchKernelGGL(fp_bi_back_mvp_cost_kernel, dim3((waves + 1) / 2), dim3(128), 0, ctx->stream,
+                     b->p.orig->v.c[0], refs, l1, b->p.orig->bd, n, d_l1_mvp_cost);
+  CHECK_LAUNCH(ctx, "fp_bi_back_mvp_cost");
+  return XVCGPU_OK;
+}
+
+xvcgpu_status xvcgpu_fp_bi_back_uni_fold(xvcgpu_ctx *ctx,
+                                         const xvcgpu_frame_pass_bi_refs_args *b,
+                                         const uint32_t *d_l1_mvp_cost) {
+  if (!ctx || !b || b->p.n_cus < 0) return XVCGPU_INVALID_ARGUMENT;
+  FpBiRefsDev t;
+  const char *what = nullptr;
+  if (!fp_bi_refs_tables(b, &t, &what, true)) return fail(ctx, XVCGPU_INVALID_ARGUMENT, what);
+  if (!d_l1_mvp_cost)
+    return fail(ctx, XVCGPU_INVALID_ARGUMENT, "fp_bi_back_uni_fold: d_l1_mvp_cost");
+  const int n = b->p.n_cus;
+  if (n == 0) return XVCGPU_OK;
+  hipLaunchKernelGGL(fp_bi_back_uni_fold_kernel, dim3((n + 255) / 256), dim3(256), 0,
+                     ctx->stream, t, n, d_l1_mvp_cost, b->d_bi_jobs, b->d_bi_slots, b->d_choice);
+  CHECK_LAUNCH(ctx, "fp_bi_back_uni_fold");
+  return XVCGPU_OK;
+}
+
+xvcgpu_status xvcgpu_fp_bi_back_choice(xvcgpu_ctx *ctx,
+                                       const xvcgpu_frame_pass_bi_refs_args *b) {
+  if (!ctx || !b || b->p.n_cus < 0) return XVCGPU_INVALID_ARGUMENT;
+  FpBiRefsDev t;
+  const char *what = nullptr;
+  if (!fp_bi_refs_tables(b, &t, &what, true)) return fail(ctx, XVCGPU_INVALID_ARGUMENT, what);
+  const int n = b->p.n_cus;
+  if (n == 0) return XVCGPU_OK;
+  hipLaunchKernelGGL(fp_bi_back_choice_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream,
+                     t, n, b->d_bi_results, b->d_choice, b->d_inter);
+  CHECK_LAUNCH(ctx, "fp_bi_back_choice");
+  return XVCGPU_OK;
+}
+
+xvcgpu_status xvcgpu_frame_pass_bi_back(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_bi_refs_args *b,
+                                        uint32_t *d_l1_mvp_cost, const xvcgpu_aqp_args *q,
+                                        const xvcgpu_me_plan *const plans[2][XVC_CS_MAX_REFS],
+                                        int phases) {
+  return frame_pass_bi_refs_impl(ctx, b, plans, phases, q, "frame_pass_bi_back", true,
+                                 d_l1_mvp_cost);
 }
 
 xvcgpu_status xvcgpu_mc_metric_batch_refs(xvcgpu_ctx *ctx, const xvcgpu_picture *orig,

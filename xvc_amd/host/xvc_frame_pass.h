@@ -445,11 +445,22 @@ class FramePassBiRefs {
  public:
   // The picture's POC and its lists' POCs; what the pass needs beyond them is derived:
   // same_poc_in_l0 (ReferencePictureLists::GetSamePocMappingFor), the table of distinct
-  // pictures and force_l1_mvd_zero (PictureData::DetermineForceBipredL1MvdZero), which is
-  // out of scope and refused.
+  // pictures and force_l1_mvd_zero (PictureData::DetermineForceBipredL1MvdZero).
+  // low_delay = false: lists that lie wholly before cur_poc are refused, as before.
+  // low_delay = true: the pass of a picture with only back references
+  // (xvcgpu_frame_pass_bi_back: list 1's candidate is the job's predictor, priced on the
+  // device; list 0 is refined against it; no vector difference for list 1 of a
+  // bi-directional CU); lists with a later picture are refused.
   struct RefLists {
     int cur_poc;
     std::vector<int> poc[2];
+    bool low_delay;
+    RefLists() : cur_poc(0), low_delay(false) {}
+    RefLists(int cur, const std::vector<int> &l0, const std::vector<int> &l1, bool ld = false)
+        : cur_poc(cur), low_delay(ld) {
+      poc[0] = l0;
+      poc[1] = l1;
+    }
   };
 
   FramePassBiRefs(const Context &ctx, int width, int height, int bitdepth, int qp,
@@ -517,7 +528,7 @@ class FramePassBiRefs {
     a.d_luma_tx_index = d_luma_->data();
     a.form = XVC_FP_FORM_RESIDUAL;
     b.n_refs = static_cast<int32_t>(distinct_.size());
-    b.force_l1_mvd_zero = 0;
+    b.force_l1_mvd_zero = low_delay_ ? 1 : 0;
     const xvcgpu_me_plan *plans[2][XVC_CS_MAX_REFS] = {};
     for (int l = 0; l < 2; l++) {
       if (pics[l].size() != static_cast<size_t>(num_ref_[l]))
@@ -547,6 +558,11 @@ class FramePassBiRefs {
     b.d_inter = d_inter_->data();
     const int phases = XVC_FP_ENCODE | XVC_FP_DEBLOCK_V | XVC_FP_DEBLOCK_H | XVC_FP_PAD |
                        XVC_FP_SSD;
+    if (low_delay_) {
+      ctx_.Check(xvcgpu_frame_pass_bi_back(ctx_.get(), &b, d_l1_mvp_cost_->data(),
+                                           aqp_ ? aqp_->args() : nullptr, plans, phases));
+      return;
+    }
     if (aqp_) {
       ctx_.Check(xvcgpu_frame_pass_bi_refs_aqp(ctx_.get(), &b, aqp_->args(), plans, phases));
       return;
@@ -555,7 +571,7 @@ class FramePassBiRefs {
   }
 
   // From now on every Run codes with adaptive QP (FramePass::SetAdaptiveQp; the form is
-  // RESIDUAL already): xvcgpu_frame_pass_bi_refs_aqp.
+  // RESIDUAL already): xvcgpu_frame_pass_bi_refs_aqp, or xvcgpu_frame_pass_bi_back with q.
   void SetAdaptiveQp(int aqp_strength) {
     aqp_.reset(new AdaptiveQpArrays(ctx_, w_, h_, bd_, qp_, aqp_strength, n_cus_));
   }
@@ -571,6 +587,18 @@ class FramePassBiRefs {
   // what SearchMotion ended with per CU, and the CU records the filter read
   std::vector<xvcgpu_fp_bi_refs_result> Choices() const { return d_choice_->ToHost(); }
   std::vector<xvcgpu_cu_info> CuInfo() const { return d_cus_->ToHost(); }
+  // low_delay: the predictor cost per (CU, list-1 picture), [n_cus][XVC_CS_MAX_REFS]
+  std::vector<uint32_t> L1MvpCost() const { return d_l1_mvp_cost_->ToHost(); }
+  bool low_delay() const { return low_delay_; }
+  // bytes of the work arrays between the launches, in the order of the args block and
+  // d_l1_mvp_cost last (0 without low_delay)
+  std::vector<size_t> WorkArrayBytes() const {
+    const size_t n = static_cast<size_t>(n_cus_), jobs = n * rmax_;
+    const size_t v[] = {jobs * sizeof(xvcgpu_bi_block), jobs * sizeof(xvcgpu_me_result), 2 * jobs,
+                        n * sizeof(xvcgpu_fp_bi_refs_result), 3 * n * sizeof(xvcgpu_inter_block),
+                        low_delay_ ? n * XVC_CS_MAX_REFS * sizeof(uint32_t) : 0};
+    return std::vector<size_t>(v, v + 6);
+  }
   int num_cus() const { return n_cus_; }
   int same_poc_in_l0(int ref_idx) const { return same_[ref_idx]; }
 
@@ -601,7 +629,12 @@ class FramePassBiRefs {
         slot_[l][r] = static_cast<int>(k);
       }
     }
-    if (only_back)
+    low_delay_ = lists.low_delay;
+    if (low_delay_ && !only_back)
+      throw Error(XVCGPU_INVALID_ARGUMENT,
+                  "FramePassBiRefs: low_delay takes only lists that lie wholly before the "
+                  "picture (force_l1_mvd_zero)");
+    if (only_back && !low_delay_)
       throw Error(XVCGPU_INVALID_ARGUMENT,
                   "FramePassBiRefs: a picture with only back references (force_l1_mvd_zero) is "
                   "out of this pass's scope");
@@ -657,6 +690,7 @@ class FramePassBiRefs {
     d_bi_slots_.reset(new DeviceArray<uint8_t>(ctx_, 2 * n * rmax_));
     d_choice_.reset(new DeviceArray<xvcgpu_fp_bi_refs_result>(ctx_, n));
     d_inter_.reset(new DeviceArray<xvcgpu_inter_block>(ctx_, 3 * n));
+    if (low_delay_) d_l1_mvp_cost_.reset(new DeviceArray<uint32_t>(ctx_, n * XVC_CS_MAX_REFS));
     d_map_.reset(new DeviceArray<int32_t>(ctx_, map));
     d_tx_.reset(new DeviceArray<xvcgpu_tx_block>(ctx_, tx));
     d_luma_.reset(new DeviceArray<int32_t>(ctx_, luma));
@@ -685,7 +719,9 @@ class FramePassBiRefs {
 
   const Context &ctx_;
   int h_, bd_, qp_, qp_c_, n_cus_, map_stride_, max_cu_, rmax_, w_;
+  bool low_delay_;
   std::unique_ptr<AdaptiveQpArrays> aqp_;
+  std::unique_ptr<DeviceArray<uint32_t>> d_l1_mvp_cost_;
   int num_ref_[2], poc_[2][XVC_CS_MAX_REFS], slot_[2][XVC_CS_MAX_REFS], same_[XVC_CS_MAX_REFS];
   std::vector<int> distinct_;
   xvcgpu_me_plan *plan_[2][XVC_CS_MAX_REFS];

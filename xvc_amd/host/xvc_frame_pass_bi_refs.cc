@@ -8,17 +8,15 @@
 
 #include "xvc_frame_pass.h"
 
-extern "C" {
+namespace {
 
-// pocs[l * 3 + r], ref_pics[l * 3 + r] (NULL beyond num_ref[l]); blocks[(l * 3 + r) * n + i]:
-// the search jobs per (list, picture), n = the grid's CUs (NULL: the class's own jobs).
-// out_choice[n], out_cus[n], out_ssd[2] after the pass has run (synchronises).
-int xvc_host_frame_pass_bi_refs(xvcgpu_ctx *ctx, int width, int height, int bitdepth, int qp,
-                                int cur_poc, const int32_t *num_ref, const int32_t *pocs,
-                                xvcgpu_picture *orig, xvcgpu_picture *const *ref_pics,
-                                xvcgpu_picture *rec, const xvcgpu_me_block *blocks, int n,
-                                xvcgpu_fp_bi_refs_result *out_choice, xvcgpu_cu_info *out_cus,
-                                uint64_t *out_ssd) {
+// low_delay: RefLists::low_delay; aqp_strength < 0: one QP; out_l1_mvp_cost[n * 3]: NULL or
+// the predictor costs of a low_delay pass
+int RunBiRefs(xvcgpu_ctx *ctx, int width, int height, int bitdepth, int qp, int cur_poc,
+              bool low_delay, int aqp_strength, const int32_t *num_ref, const int32_t *pocs,
+              xvcgpu_picture *orig, xvcgpu_picture *const *ref_pics, xvcgpu_picture *rec,
+              const xvcgpu_me_block *blocks, int n, xvcgpu_fp_bi_refs_result *out_choice,
+              xvcgpu_cu_info *out_cus, uint64_t *out_ssd, uint32_t *out_l1_mvp_cost) {
   if (!ctx || !num_ref || !pocs || !orig || !ref_pics || !rec || !out_choice || !out_cus ||
       !out_ssd)
     return XVCGPU_INVALID_ARGUMENT;
@@ -26,12 +24,14 @@ int xvc_host_frame_pass_bi_refs(xvcgpu_ctx *ctx, int width, int height, int bitd
     xvc_gpu::Context c(ctx);
     xvc_gpu::FramePassBiRefs::RefLists lists;
     lists.cur_poc = cur_poc;
+    lists.low_delay = low_delay;
     for (int l = 0; l < 2; l++) {
       if (num_ref[l] < 1 || num_ref[l] > XVC_CS_MAX_REFS) return XVCGPU_INVALID_ARGUMENT;
       lists.poc[l].assign(pocs + XVC_CS_MAX_REFS * l, pocs + XVC_CS_MAX_REFS * l + num_ref[l]);
     }
     xvc_gpu::FramePassBiRefs pass(c, width, height, bitdepth, qp, lists);
     if (pass.num_cus() != n) return XVCGPU_INVALID_ARGUMENT;
+    if (aqp_strength >= 0) pass.SetAdaptiveQp(aqp_strength);
     xvc_gpu::Picture o(c, orig), r(c, rec);
     // one view per handle: the lists name a re-used picture by the same object
     std::vector<std::unique_ptr<xvc_gpu::Picture>> views;
@@ -59,10 +59,44 @@ int xvc_host_frame_pass_bi_refs(xvcgpu_ctx *ctx, int width, int height, int bitd
     const std::vector<xvcgpu_cu_info> cus = pass.CuInfo();
     std::memcpy(out_choice, choice.data(), choice.size() * sizeof(choice[0]));
     std::memcpy(out_cus, cus.data(), cus.size() * sizeof(cus[0]));
+    if (out_l1_mvp_cost && low_delay) {
+      const std::vector<uint32_t> cost = pass.L1MvpCost();
+      std::memcpy(out_l1_mvp_cost, cost.data(), cost.size() * sizeof(cost[0]));
+    }
     return XVCGPU_OK;
   } catch (const xvc_gpu::Error &e) {
     return e.status;
   }
+}
+
+}  // namespace
+
+extern "C" {
+
+// pocs[l * 3 + r], ref_pics[l * 3 + r] (NULL beyond num_ref[l]); blocks[(l * 3 + r) * n + i]:
+// the search jobs per (list, picture), n = the grid's CUs (NULL: the class's own jobs).
+// out_choice[n], out_cus[n], out_ssd[2] after the pass has run (synchronises).
+int xvc_host_frame_pass_bi_refs(xvcgpu_ctx *ctx, int width, int height, int bitdepth, int qp,
+                                int cur_poc, const int32_t *num_ref, const int32_t *pocs,
+                                xvcgpu_picture *orig, xvcgpu_picture *const *ref_pics,
+                                xvcgpu_picture *rec, const xvcgpu_me_block *blocks, int n,
+                                xvcgpu_fp_bi_refs_result *out_choice, xvcgpu_cu_info *out_cus,
+                                uint64_t *out_ssd) {
+  return RunBiRefs(ctx, width, height, bitdepth, qp, cur_poc, false, -1, num_ref, pocs, orig,
+                   ref_pics, rec, blocks, n, out_choice, out_cus, out_ssd, nullptr);
+}
+
+// The same with RefLists::low_delay = true (lists that lie wholly before cur_poc), with
+// adaptive QP where aqp_strength >= 0; out_l1_mvp_cost[n * XVC_CS_MAX_REFS] (may be NULL).
+int xvc_host_frame_pass_bi_back(xvcgpu_ctx *ctx, int width, int height, int bitdepth, int qp,
+                                int cur_poc, int aqp_strength, const int32_t *num_ref,
+                                const int32_t *pocs, xvcgpu_picture *orig,
+                                xvcgpu_picture *const *ref_pics, xvcgpu_picture *rec,
+                                const xvcgpu_me_block *blocks, int n,
+                                xvcgpu_fp_bi_refs_result *out_choice, xvcgpu_cu_info *out_cus,
+                                uint64_t *out_ssd, uint32_t *out_l1_mvp_cost) {
+  return RunBiRefs(ctx, width, height, bitdepth, qp, cur_poc, true, aqp_strength, num_ref, pocs,
+                   orig, ref_pics, rec, blocks, n, out_choice, out_cus, out_ssd, out_l1_mvp_cost);
 }
 
 }  // extern "C"

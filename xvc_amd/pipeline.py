@@ -841,14 +841,22 @@ class BiRefsFramePass:
     table and force_l1_mvd_zero (ref_list_tables); a picture with only back references is
     refused here.  run(orig, refs, rec): refs = [[list 0's pictures], [list 1's]] in the
     lists' order, the same object where the lists name the same POC.  me[l][r] / d_me[l][r]:
-    the search jobs per (list, picture), copies of the descriptors until set_jobs."""
+    the search jobs per (list, picture), copies of the descriptors until set_jobs.
+
+    low_delay=True: the pass of a picture whose references all lie before it
+    (xvcgpu_frame_pass_bi_back; every inter picture of a low-delay encode) - list 1's
+    candidate per picture is the job's predictor itself, priced on the device into
+    d_l1_mvp_cost (l1_mvp_cost()), list 0 is refined against it, a bi-directional CU codes
+    list 1 without a vector difference.  It accepts only such lists."""
 
     def __init__(self, ctx, width, height, bitdepth=10, qp=32, cu=16, rdoq=False,
                  rdoq_packed=None, keep_levels=False, partition=None, cur_poc=8,
                  ref_pocs=((4,), (12,)), search_range=96, side_bits=(3, 3, 5),
-                 aqp_strength=None):
+                 aqp_strength=None, low_delay=False):
         self.ctx = ctx
         self.aqp = None
+        self.low_delay = bool(low_delay)
+        self.d_l1_mvp_cost = None
         if aqp_strength is not None:    # (a refused strength: before anything is allocated)
             aqp_table(qp, bitdepth, aqp_strength, width)
         self.cur_poc, self.side_bits = cur_poc, tuple(side_bits)
@@ -857,7 +865,10 @@ class BiRefsFramePass:
         if not all(1 <= k <= api.CS_MAX_REFS for k in self.num_ref):
             raise ValueError("ref_pocs: 1 .. %d pictures per list" % api.CS_MAX_REFS)
         self.same, self.distinct, self.slot, force = ref_list_tables(cur_poc, self.ref_pocs)
-        if force:
+        if low_delay and not force:
+            raise ValueError("ref_pocs %r with low_delay: every reference must lie before POC "
+                             "%d (force_l1_mvd_zero)" % (self.ref_pocs, cur_poc))
+        if force and not low_delay:
             raise ValueError("ref_pocs %r lie all before POC %d: a picture with only back "
                              "references (force_l1_mvd_zero) is out of this pass's scope"
                              % (self.ref_pocs, cur_poc))
@@ -882,6 +893,8 @@ class BiRefsFramePass:
         self.d_bi_slots = ctx.alloc(2 * n * self.rmax)
         self.d_choice = ctx.alloc(api.FP_BI_REFS_RESULT_DTYPE.itemsize * n)
         self.d_inter = ctx.alloc(api.INTER_DTYPE.itemsize * 3 * n)
+        if low_delay:
+            self.d_l1_mvp_cost = ctx.alloc(4 * api.CS_MAX_REFS * n)
         self.plans = [[None] * self.num_ref[l] for l in range(2)]
         if aqp_strength is not None:    # (every form of this pass is one adaptive QP runs)
             self.aqp = _AqpArrays(ctx, d, bitdepth, aqp_strength)
@@ -920,7 +933,7 @@ class BiRefsFramePass:
         a.n_refs = len(pics)
         for k, pic in enumerate(pics):
             a.refs[k] = pic.h_pic if pic is not None else None
-        a.force_l1_mvd_zero = 0
+        a.force_l1_mvd_zero = int(self.low_delay)
         for r in range(api.CS_MAX_REFS):
             a.same_poc_in_l0[r] = self.same[r] if r < self.num_ref[1] else -1
         for l in range(2):
@@ -951,6 +964,12 @@ class BiRefsFramePass:
         if not fused_tail:
             a.p.scratch_rec = None
         phases = api.FP_ENCODE | api.FP_DEBLOCK_V | api.FP_DEBLOCK_H | api.FP_PAD | api.FP_SSD
+        if self.low_delay:
+            q = self.aqp.args() if self.aqp is not None else None
+            self.ctx._check(self.ctx.lib.xvcgpu_frame_pass_bi_back(
+                self.ctx.h, C.byref(a), self.d_l1_mvp_cost.ptr,
+                C.byref(q) if q is not None else None, self.plan_handles(planned), phases))
+            return
         if self.aqp is not None:
             q = self.aqp.args()
             self.ctx._check(self.ctx.lib.xvcgpu_frame_pass_bi_refs_aqp(
@@ -988,7 +1007,15 @@ class BiRefsFramePass:
             for r in range(self.num_ref[l]):
                 if self.searched[l][r]:
                     steps.append(("me_search_l%d_r%d" % (l, r), search(l, r)))
-        steps.append(("uni_fold", lambda: chk(lib.xvcgpu_fp_bi_refs_uni_fold(ctx.h, C.byref(a)))))
+        if self.low_delay:
+            cost = self.d_l1_mvp_cost.ptr
+            steps += [
+                ("l1_mvp_cost", lambda: chk(lib.xvcgpu_fp_bi_back_mvp_cost(ctx.h, C.byref(a),
+                                                                           cost))),
+                ("uni_fold", lambda: chk(lib.xvcgpu_fp_bi_back_uni_fold(ctx.h, C.byref(a), cost)))]
+        else:
+            steps.append(("uni_fold", lambda: chk(lib.xvcgpu_fp_bi_refs_uni_fold(ctx.h,
+                                                                                 C.byref(a)))))
         if planned:
             first = next(q for q in self.plans[0] if q is not None)
             steps.append(("bipred_planned", lambda: chk(lib.xvcgpu_bipred_search_refs_planned(
@@ -997,8 +1024,9 @@ class BiRefsFramePass:
         else:
             steps += [("bipred_c%d" % cls, refine(cls)) for cls in (16, 32, 64)
                       if cls <= d.cu_size]
+        choice = lib.xvcgpu_fp_bi_back_choice if self.low_delay else lib.xvcgpu_fp_bi_refs_choice
         steps += [
-            ("choice", lambda: chk(lib.xvcgpu_fp_bi_refs_choice(ctx.h, C.byref(a)))),
+            ("choice", lambda: chk(choice(ctx.h, C.byref(a)))),
             ("inter_pred", lambda: chk(lib.xvcgpu_inter_pred_batch(
                 ctx.h, handles, len(pics), rec.h_pic, p.pred.h_pic, self.d_inter.ptr, 3 * n)))]
         # the form's residual pipeline: the P pass's launches between its prediction and
@@ -1029,6 +1057,12 @@ class BiRefsFramePass:
                 self.d_bi_res.to_array(api.MERES_DTYPE, d.n_cus * self.rmax).reshape(-1, self.rmax),
                 self.d_bi_slots.to_array(np.uint8, 2 * d.n_cus * self.rmax).reshape(-1, self.rmax, 2))
 
+    def l1_mvp_cost(self):
+        """low_delay: the last run's predictor cost per (CU, list-1 picture), [n_cus,
+        CS_MAX_REFS] uint32 (UINT32_MAX beyond list 1's pictures)."""
+        return self.d_l1_mvp_cost.to_array(np.uint32, api.CS_MAX_REFS * self.desc.n_cus) \
+            .reshape(-1, api.CS_MAX_REFS)
+
     def ctu_delta_qp(self):
         """Adaptive QP: the last run's delta per CTU, [rows, columns] int8."""
         return self.aqp.ctu_delta_qp()
@@ -1042,6 +1076,9 @@ class BiRefsFramePass:
             self.aqp.free()
             self.aqp = None
         bufs = [self.d_bi_jobs, self.d_bi_res, self.d_bi_slots, self.d_choice, self.d_inter]
+        if self.d_l1_mvp_cost is not None:
+            bufs.append(self.d_l1_mvp_cost)
+            self.d_l1_mvp_cost = None
         for l in range(2):
             bufs += self.d_me[l] + [b for b in self.d_res[l] if b is not None]
             for plan in self.plans[l]:
