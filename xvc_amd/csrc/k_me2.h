@@ -408,11 +408,27 @@ __device__ __forceinline__ uint32_t me2_pack_pos(int x, int y) {
 // leaves it unchanged (two v_pk instructions and a compare instead of a branch per
 // direction).  Full-pel positions are far inside int16 (|mv| < 8192 + the range).
 struct Me2Pattern {
-  int meta0, meta1;  // (rng << 8) | ((d1 + d2) & 0xff), for winner look-up
+  // what a hit records, for the winner look-up: dx, dy (10 bits each, signed), d1 + d2
+  // (4 bits, signed), log2 of rng (4 bits), round (4 bits) - one readlane per look-up
+  uint32_t ent0, ent1;
   int off0, off1;    // (dy << 16) | (dx & 0xffff)
   uint32_t lo0, hi0, lo1, hi1;   // (y bound << 16) | (x bound & 0xffff)
-  int round0, round1;
 };
+
+// The same box for a candidate given by its offset alone.  Every candidate of the search
+// tests the bounds on the side(s) it moved to - the pattern's entries (tz_pattern_cand:
+// d1 / d2 follow the signs of dx / dy) and the two candidates of the neighbour step.
+__device__ __forceinline__ void me2_offset_box(const MeCtx &c, int dx, int dy, uint32_t &lo,
+                                               uint32_t &hi) {
+  lo = me2_pack_pos(dx < 0 ? c.min_x : -32768, dy < 0 ? c.min_y : -32768);
+  hi = me2_pack_pos(dx > 0 ? c.max_x : 32767, dy > 0 ? c.max_y : 32767);
+}
+
+// Inside iff clamping the packed position to the box leaves it unchanged.
+__device__ __forceinline__ bool me2_in_box(sp_v2s q, uint32_t lo, uint32_t hi) {
+  return sp_u(__builtin_elementwise_min(__builtin_elementwise_max(q, sp_s2(lo)), sp_s2(hi))) ==
+         sp_u(q);
+}
 
 __device__ __forceinline__ void me2_pattern_box(const MeCtx &c, const TzCand &a, uint32_t &lo,
                                                 uint32_t &hi) {
@@ -422,15 +438,19 @@ __device__ __forceinline__ void me2_pattern_box(const MeCtx &c, const TzCand &a,
   hi = me2_pack_pos(r ? c.max_x : 32767, d ? c.max_y : 32767);
 }
 
+__device__ __forceinline__ uint32_t me2_pattern_entry(const TzCand &a) {
+  return ((uint32_t)a.dx & 0x3ffu) | (((uint32_t)a.dy & 0x3ffu) << 10) |
+         (((uint32_t)(a.d1 + a.d2) & 15u) << 20) | ((uint32_t)(31 - __clz((int)a.rng)) << 24) |
+         ((uint32_t)a.round << 28);
+}
+
 __device__ __forceinline__ Me2Pattern me2_load_pattern(const MeCtx &c, const TzCand *tzp) {
   const int lane = ME2_LANE;
   const TzCand a = tzp[lane];
   const TzCand b = tzp[lane + 64 < TZ_MAX_CANDS ? lane + 64 : 0];
   Me2Pattern p;
-  p.round0 = a.round;
-  p.round1 = b.round;
-  p.meta0 = ((int)a.rng << 8) | ((a.d1 + a.d2) & 0xff);
-  p.meta1 = ((int)b.rng << 8) | ((b.d1 + b.d2) & 0xff);
+  p.ent0 = me2_pattern_entry(a);
+  p.ent1 = me2_pattern_entry(b);
   p.off0 = ((int)a.dy << 16) | ((int)a.dx & 0xffff);
   p.off1 = ((int)b.dy << 16) | ((int)b.dx & 0xffff);
   me2_pattern_box(c, a, p.lo0, p.hi0);
@@ -438,18 +458,19 @@ __device__ __forceinline__ Me2Pattern me2_load_pattern(const MeCtx &c, const TzC
   return p;
 }
 
-// Pattern entry `idx` (wave-uniform) as seen from centre (bx,by).
+// Pattern entry `idx` (wave-uniform) as seen from centre (bx,by): one readlane of the
+// packed entry (the half of the table is chosen per lane, the index is uniform), the fields
+// by scalar bit-field extracts.
 __device__ __forceinline__ void me2_pattern_at(const Me2Pattern &p, int idx, int bx,
                                                int by, int &x, int &y, int &pos,
-                                               int &rng) {
-  const int l = idx & 63;
-  const int o0 = __builtin_amdgcn_readlane(p.off0, l), o1 = __builtin_amdgcn_readlane(p.off1, l);
-  const int m0 = __builtin_amdgcn_readlane(p.meta0, l), m1 = __builtin_amdgcn_readlane(p.meta1, l);
-  const int o = (idx >> 6) ? o1 : o0, m = (idx >> 6) ? m1 : m0;
-  x = bx + (int)(int16_t)(o & 0xffff);
-  y = by + (o >> 16);
-  pos = (int)(int8_t)(m & 0xff);
-  rng = m >> 8;
+                                               int &rng, int &round) {
+  const uint32_t e =
+      (uint32_t)__builtin_amdgcn_readlane((int)((idx >> 6) ? p.ent1 : p.ent0), idx & 63);
+  x = bx + ((int)(e << 22) >> 22);
+  y = by + ((int)(e << 12) >> 22);
+  pos = (int)(e << 8) >> 28;
+  rng = 1 << ((e >> 24) & 15u);
+  round = (int)(e >> 28);
 }
 
 // Evaluate pattern entries [lo, total) of the diamond list around (bx,by):
@@ -466,10 +487,7 @@ __device__ __forceinline__ int me2_eval_diamonds(const MeCtx &c, SH &s,
   const sp_v2s ctr = sp_s2(me2_pack_pos(bx, by));
   const sp_v2s q0 = ctr + sp_s2((uint32_t)p.off0), q1 = ctr + sp_s2((uint32_t)p.off1);
   const uint32_t pk0 = sp_u(q0), pk1 = sp_u(q1);
-  const bool in0 = sp_u(__builtin_elementwise_min(__builtin_elementwise_max(q0, sp_s2(p.lo0)),
-                                                  sp_s2(p.hi0))) == pk0;
-  const bool in1 = sp_u(__builtin_elementwise_min(__builtin_elementwise_max(q1, sp_s2(p.lo1)),
-                                                  sp_s2(p.hi1))) == pk1;
+  const bool in0 = me2_in_box(q0, p.lo0, p.hi0), in1 = me2_in_box(q1, p.lo1, p.hi1);
   const int x0 = (int)(int16_t)(pk0 & 0xffffu), y0 = (int)pk0 >> 16;
   const int x1 = (int)(int16_t)(pk1 & 0xffffu), y1 = (int)pk1 >> 16;
   const bool v0 = (unsigned)(lane - lo) < (unsigned)(total - lo) && in0;
@@ -1088,9 +1106,8 @@ me2_search_job(Shared &s, const PicView &orig, const PicView &ref, const xvcgpu_
     }
 
     ME2_TRACE(2);  // predictor pass
-    int total = 0, n_rounds = 0;
-    for (int r = 1; r <= range; r *= 2) { total += tz_pattern_count(r); n_rounds++; }
-    const Me2Pattern pat = me2_load_pattern(c, tz_pattern);
+    const int n_rounds = tz_pattern_rounds(range), total = tz_pattern_prefix(n_rounds);
+    Me2Pattern pat = me2_load_pattern(c, tz_pattern);
 
     // initial raster around the fixed base with per-round early termination.
     // The reference stops after 3 consecutive rounds without a hit, so at any
@@ -1098,84 +1115,85 @@ me2_search_job(Shared &s, const PicView &orig, const PicView &ref, const xvcgpu_
     // those are evaluated (one sweep), folded, and the horizon is extended only
     // if one of them hit.  The common case is ranges 1,2,4 then 8,16 - the 32
     // far candidates of ranges 32 and 64 (cold cache lines) are never read.
+    // The rounds of a sweep are folded at once.  Indices rise with the round and the
+    // reference takes a later candidate only when it is strictly cheaper, so the lowest
+    // key of the sweep is the hit of the last round that hits (no round behind it can:
+    // it would have to be cheaper still), that hit is the state the round-by-round fold
+    // ends with, and the rounds behind it are the dry ones.  A sweep never holds more
+    // rounds than the stop rule is sure to look at, so the count reaches 3 only at its end.
     {
-      uint32_t k0 = ME2_NOKEY, k1 = ME2_NOKEY;
       const int bx = st.bx, by = st.by;
-      int no_match = 0, r_eval = 0, idx_eval = 0;
-      for (int r = 0; r < n_rounds; r++) {
-        if (r >= r_eval) {
-          int hi = r + (3 - no_match);
-          hi = hi < n_rounds ? hi : n_rounds;
-          int idx_hi = idx_eval;
-          for (int q = r_eval; q < hi; q++) idx_hi += tz_pattern_count(1 << q);
-          uint32_t f0, f1;
-          const int ne = me2_eval_diamonds(c, s, pat, bx, by, idx_eval, idx_hi, st.cost, f0, f1, q16);
-          (void)ne;
-          ME2_COUNT(0, 1); ME2_COUNT(1, (ne + 15) >> 4); ME2_COUNT(4, ne);
-          if (f0 != ME2_NOKEY) k0 = f0;
-          if (f1 != ME2_NOKEY) k1 = f1;
-          r_eval = hi;
-          idx_eval = idx_hi;
-        }
-        uint32_t k = ME2_NOKEY;
-        if (pat.round0 == r && k0 < k) k = k0;
-        if (pat.round1 == r && k1 < k) k = k1;
-        k = wave_min_key(k);
-        bool changed = false;
+      int no_match = 0, r_eval = 0;
+      while (r_eval < n_rounds) {
+        int hi = r_eval + (3 - no_match);
+        hi = hi < n_rounds ? hi : n_rounds;
+        uint32_t f0, f1;
+        const int ne = me2_eval_diamonds(c, s, pat, bx, by, tz_pattern_prefix(r_eval),
+                                         tz_pattern_prefix(hi), st.cost, f0, f1, q16);
+        (void)ne;
+        ME2_COUNT(0, 1); ME2_COUNT(1, (ne + 15) >> 4); ME2_COUNT(4, ne);
+        const uint32_t k = wave_min_key(f0 < f1 ? f0 : f1);
         if (k != ME2_NOKEY && (k >> 7) < st.cost) {
-          int x, y, pos, rng;
-          me2_pattern_at(pat, (int)(k & 127), bx, by, x, y, pos, rng);
+          int x, y, pos, rng, round;
+          me2_pattern_at(pat, (int)(k & 127), bx, by, x, y, pos, rng, round);
           st.cost = k >> 7; st.bx = x; st.by = y; st.last_pos = pos; st.last_range = rng;
-          changed = true;
+          no_match = hi - 1 - round;
+        } else {
+          no_match += hi - r_eval;
         }
-        if (changed) no_match = 0;
-        else if (++no_match >= 3) break;
+        r_eval = hi;
+        if (no_match >= 3) break;
       }
     }
     // neighbour refinement (2 candidates), shared by raster and refinement
     auto neighbor = [&]() {
-      const int r = 1, bx = st.bx, by = st.by;
-      int x[2], y[2], d1[2], d2[2];
-      bool any = true;
-      switch (st.last_pos) {
-        case TZ_UP + TZ_LEFT: x[0]=bx-r;y[0]=by;d1[0]=TZ_LEFT;d2[0]=0; x[1]=bx;y[1]=by-r;d1[1]=TZ_UP;d2[1]=0; break;
-        case TZ_UP: x[0]=bx-r;y[0]=by-r;d1[0]=TZ_UP;d2[0]=TZ_LEFT; x[1]=bx+r;y[1]=by-r;d1[1]=TZ_UP;d2[1]=TZ_RIGHT; break;
-        case TZ_UP + TZ_RIGHT: x[0]=bx;y[0]=by-r;d1[0]=TZ_UP;d2[0]=0; x[1]=bx+r;y[1]=by;d1[1]=TZ_RIGHT;d2[1]=0; break;
-        case TZ_LEFT: x[0]=bx-r;y[0]=by+r;d1[0]=TZ_DOWN;d2[0]=TZ_LEFT; x[1]=bx-r;y[1]=by-r;d1[1]=TZ_UP;d2[1]=TZ_LEFT; break;
-        case TZ_RIGHT: x[0]=bx+r;y[0]=by-r;d1[0]=TZ_UP;d2[0]=TZ_RIGHT; x[1]=bx+r;y[1]=by+r;d1[1]=TZ_DOWN;d2[1]=TZ_RIGHT; break;
-        case TZ_DOWN + TZ_LEFT: x[0]=bx-r;y[0]=by;d1[0]=TZ_LEFT;d2[0]=0; x[1]=bx;y[1]=by+r;d1[1]=TZ_DOWN;d2[1]=0; break;
-        case TZ_DOWN: x[0]=bx-r;y[0]=by+r;d1[0]=TZ_DOWN;d2[0]=TZ_LEFT; x[1]=bx+r;y[1]=by+r;d1[1]=TZ_DOWN;d2[1]=TZ_RIGHT; break;
-        case TZ_DOWN + TZ_RIGHT: x[0]=bx+r;y[0]=by;d1[0]=TZ_RIGHT;d2[0]=0; x[1]=bx;y[1]=by+r;d1[1]=TZ_DOWN;d2[1]=0; break;
-        default: any = false; break;
-      }
-      if (!any) return;
+      // The two candidates of a last_pos (TzSearch::FullpelNeighborPointSearch,
+      // inter_tz_search.cc:212-258) as offsets, nibbles (dx + 1) | (dy + 1) << 2 of a constant per
+      // candidate, case last_pos + 4 (the positive ones one lower: 0 is no case) -
+      //   UP+LEFT (-1,0) (0,-1)    UP (-1,-1) (1,-1)     UP+RIGHT (0,-1) (1,0)
+      //   LEFT (-1,1) (-1,-1)      RIGHT (1,-1) (1,1)
+      //   DOWN+LEFT (-1,0) (0,1)   DOWN (-1,1) (1,1)     DOWN+RIGHT (1,0) (0,1)
+      // Each tests the bounds on the side(s) it moved to and records d1 + d2 = dx + 3 dy
+      // (me2_offset_box; TZ_LEFT / RIGHT = -+1, TZ_UP / DOWN = -+3).  One candidate per lane
+      // group - a quad where quads evaluate, else a lane -, so nothing branches on the case.
+      if (st.last_pos == 0) return;
       ME2_COUNT(3, 1);
-      const bool v0 = tz_inside(c, d1[0], x[0], y[0]) && (d2[0] == 0 || tz_inside(c, d2[0], x[0], y[0]));
-      const bool v1 = tz_inside(c, d1[1], x[1], y[1]) && (d2[1] == 0 || tz_inside(c, d2[1], x[1], y[1]));
-      uint32_t n0, n1;
+      const int bx = st.bx, by = st.by;
+      const int j = use_q16 ? lane >> 2 : lane, l1 = use_q16 ? 4 : 1;
+      const uint32_t sh = 4u * (uint32_t)(st.last_pos + 4 - (st.last_pos > 0 ? 1 : 0));
+      const uint32_t nib = ((j == 0 ? 0x68428104u : 0x9A9A0621u) >> sh) & 15u;
+      const int dx = (int)(nib & 3u) - 1, dy = (int)(nib >> 2) - 1;
+      uint32_t lo, hi;
+      me2_offset_box(c, dx, dy, lo, hi);
+      const sp_v2s q = sp_s2(me2_pack_pos(bx, by)) + sp_s2(me2_pack_pos(dx, dy));
+      const bool mine = j < 2 && me2_in_box(q, lo, hi);
+      const uint32_t pos = sp_u(q);
+      const int nx = (int)(int16_t)(pos & 0xffffu), ny = (int)pos >> 16;
+      uint32_t dist;
       if (use_q16) {
-        const int qi = lane >> 2;
-        const bool mine = qi == 0 ? v0 : (qi == 1 ? v1 : false);
-        const int nx = qi == 0 ? x[0] : x[1], ny = qi == 0 ? y[0] : y[1];
-        const uint32_t pk = mine ? me2_pack_pos(nx, ny) : ME2_NOPOS;
-        const uint32_t cc = me_cost(c, me2_quad_sad<4>(c, q16, me2_ref_base(c), pk), nx, ny);
-        n0 = (uint32_t)__builtin_amdgcn_readlane((int)cc, 0);
-        n1 = (uint32_t)__builtin_amdgcn_readlane((int)cc, 4);
+        dist = me2_quad_sad<4>(c, q16, me2_ref_base(c), mine ? pos : ME2_NOPOS);
       } else {
         wave_sync();
-        if (lane == 0) s.cost[0] = v0 ? me2_pack_pos(x[0], y[0]) : ME2_NOPOS;
-        if (lane == 1) s.cost[1] = v1 ? me2_pack_pos(x[1], y[1]) : ME2_NOPOS;
+        if (lane < 2) s.cost[lane] = mine ? pos : ME2_NOPOS;
         wave_sync();
         me2_eval_positions(c, s.cost, s.orig, 2, q16);
         wave_sync();
-        if (lane == 0 && v0) s.cost[0] = me_cost(c, s.cost[0], x[0], y[0]);
-        if (lane == 1 && v1) s.cost[1] = me_cost(c, s.cost[1], x[1], y[1]);
-        wave_sync();
-        n0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)s.cost[0]);
-        n1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)s.cost[1]);
+        dist = s.cost[lane & 1];
       }
-      if (v0 && n0 < st.cost) { st.cost = n0; st.bx = x[0]; st.by = y[0]; st.last_pos = d1[0] + d2[0]; st.last_range = r; }
-      if (v1 && n1 < st.cost) { st.cost = n1; st.bx = x[1]; st.by = y[1]; st.last_pos = d1[1] + d2[1]; st.last_range = r; }
+      const uint32_t cc = me_cost(c, dist, nx, ny);
+      const unsigned long long vm = __ballot(mine);
+      const uint32_t n0 = (uint32_t)__builtin_amdgcn_readlane((int)cc, 0);
+      const uint32_t n1 = (uint32_t)__builtin_amdgcn_readlane((int)cc, l1);
+      int win = -1;
+      if ((vm & 1ull) != 0 && n0 < st.cost) { st.cost = n0; win = 0; }
+      if (((vm >> l1) & 1ull) != 0 && n1 < st.cost) { st.cost = n1; win = l1; }
+      if (win >= 0) {
+        const uint32_t wp = (uint32_t)__builtin_amdgcn_readlane((int)pos, win);
+        st.bx = (int)(int16_t)(wp & 0xffffu);
+        st.by = (int)wp >> 16;
+        st.last_pos = (st.bx - bx) + 3 * (st.by - by);
+        st.last_range = 1;
+      }
     };
     ME2_TRACE(3);  // raster
     if (st.last_range == 1) { st.last_range = 0; neighbor(); }
@@ -1259,6 +1277,9 @@ me2_search_job(Shared &s, const PicView &orig, const PicView &ref, const xvcgpu_
         st.bx = fs_min_x + (gi % nx) * 5;
         st.by = fs_min_y + (gi / nx) * 5;
       }
+      // read again here, where one job in thousands comes by: the pattern's registers are
+      // free inside the grid loop (its spills: -16 .. -24 B of scratch in every instance)
+      pat = me2_load_pattern(c, tz_pattern);
     }
     ME2_TRACE(5);  // grid
     // iterative refinement: all diamonds around the current best, one fold
@@ -1271,8 +1292,8 @@ me2_search_job(Shared &s, const PicView &orig, const PicView &ref, const xvcgpu_
       ME2_COUNT(0, 1); ME2_COUNT(1, (ne + 15) >> 4); ME2_COUNT(4, ne); ME2_COUNT(2, 1);
       const uint32_t k = wave_min_key(k0 < k1 ? k0 : k1);
       if (k != ME2_NOKEY && (k >> 7) < st.cost) {
-        int x, y, pos, rng;
-        me2_pattern_at(pat, (int)(k & 127), bx, by, x, y, pos, rng);
+        int x, y, pos, rng, round;
+        me2_pattern_at(pat, (int)(k & 127), bx, by, x, y, pos, rng, round);
         st.cost = k >> 7; st.bx = x; st.by = y; st.last_pos = pos; st.last_range = rng;
       }
       if (st.last_range == 1) { st.last_range = 0; neighbor(); }
@@ -1491,8 +1512,8 @@ me_search_wave_kernel(PicView orig, PicView ref,
 // The exact-shape jobs of the 16 class (16x16, 16x8), both phases, in a kernel of their own
 // for a job list that is (almost) all such CUs - a picture's frame pass: with the block
 // size compiled in the job fits 96 registers, five waves per SIMD instead of four (6864 B
-// LDS, scratch 164 B / lane: 77 spilled VGPRs; the any-size me_search_wave_kernel<16, 3>:
-// 128 registers, four waves, scratch 140 B / lane; hipcc
+// LDS, scratch 140 B / lane: 69 spilled VGPRs; the any-size me_search_wave_kernel<16, 3>:
+// 128 registers, four waves, scratch 116 B / lane; hipcc
 // -Rpass-analysis=kernel-resource-usage, gfx950); the
 // spilled registers sit in the step-5 grid loop, which one job in thousands runs (with
 // the any-size instance in the same kernel the allocator spilled the lane number and

@@ -34,6 +34,22 @@ TZ_HD inline int tz_pattern_count(int range) {
   return range == 1 ? 4 : (range <= 8 ? 8 : 16);
 }
 
+// Entries in front of round q (the diamonds of ranges 1 .. 2^(q-1)): 0, 4, 12, 20, 28, 44,
+// ... - the sum of tz_pattern_count over those rounds in closed form.
+TZ_HD inline int tz_pattern_prefix(int q) {
+  return q <= 0 ? 0 : (q <= 4 ? 8 * q - 4 : 16 * q - 36);
+}
+
+// Rounds a search of `range` examines (ranges 1, 2, 4 ... <= range).
+TZ_HD inline int tz_pattern_rounds(int range) {
+  return range > 0 ? 32 - __builtin_clz((unsigned)range) : 0;
+}
+
+// Round of entry idx: the inverse of tz_pattern_prefix.
+TZ_HD inline int tz_pattern_round_of(int idx) {
+  return idx < 4 ? 0 : (idx < 28 ? 1 + ((idx - 4) >> 3) : 4 + ((idx - 28) >> 4));
+}
+
 // k-th candidate of the diamond of `range` in issue order.
 TZ_HD inline TzCand tz_pattern_cand(int range, int k) {
   TzCand c;
