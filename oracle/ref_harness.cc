@@ -578,7 +578,10 @@ void xr_deblock_picture(int bd, int pic_w, int pic_h, int bipred,
                         uint16_t *const planes[3], const ptrdiff_t strides[3],
                         const int32_t *l0_pocs, int n0, const int32_t *l1_pocs,
                         int n1) {
-  (void)subblock_size; /* reference default: 4 */
+  /* 4 is the reference's default (kSubblockSizeExt); 8 is what it filters on under
+   * Restrictions::disable_ext_deblock_subblock_size_4 - thread-local state of the
+   * reference, flipped around the filter below */
+  assert(subblock_size == 4 || subblock_size == 8);
   PictureData pic_data(ChromaFormat::k420, pic_w, pic_h, bd);
   pic_data.SetNalType(bipred ? NalUnitType::kBipredictedPicture
                              : NalUnitType::kPredictedPicture);
@@ -628,8 +631,14 @@ void xr_deblock_picture(int bd, int pic_w, int pic_h, int bipred,
 
   YuvPicture rec(ChromaFormat::k420, pic_w, pic_h, bd, true, 0, 0);
   FillPic(&rec, const_cast<const uint16_t *const *>(planes), strides);
-  DeblockingFilter df(&pic_data, &rec, beta_offset, tc_offset);
-  df.DeblockPicture();
+  Restrictions &r = Restrictions::GetRW();
+  const bool saved = r.disable_ext_deblock_subblock_size_4;
+  r.disable_ext_deblock_subblock_size_4 = subblock_size == 8;
+  {
+    DeblockingFilter df(&pic_data, &rec, beta_offset, tc_offset);
+    df.DeblockPicture();
+  }
+  r.disable_ext_deblock_subblock_size_4 = saved;
   ReadPic(rec, planes, strides, false);
 }
 

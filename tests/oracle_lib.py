@@ -504,5 +504,29 @@ class Lib:
         return rec, coeff, n
 
 
+_ref_checked = False
+
+
 def have_ref():
-    return os.path.exists(REF_SO)
+    """True where the reference harness has been built.  The first call brings it up to
+    date with oracle/ref_harness.cc and ref_stream.cc (make, where the reference's sources
+    lie; its harness objects are named after their content): a library left by a build of
+    another revision answers the same xr_* calls with another meaning."""
+    global _ref_checked
+    if not os.path.exists(REF_SO):
+        return False
+    if not _ref_checked:
+        import fcntl
+        try:        # one builder at a time (build_oracle); a tree that cannot be written
+            lock = open(REF_SO + ".lock", "w")      # to is checked all the same
+            fcntl.flock(lock, fcntl.LOCK_EX)
+        except OSError:
+            lock = None
+        try:
+            subprocess.check_call(["make", "-s", "-j8", "-C", ORACLE_DIR, "refresh"],
+                                  stdout=subprocess.DEVNULL)
+        finally:
+            if lock:
+                lock.close()
+        _ref_checked = True
+    return True

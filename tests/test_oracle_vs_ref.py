@@ -275,8 +275,16 @@ def test_quant_dequant(libs, bd):
 @pytest.mark.parametrize("bd", [8, 10, 12, 9, 11])
 @pytest.mark.parametrize("bipred", [0, 1])
 def test_deblock(libs, bd, bipred):
+    """Sub-block size 4 (the reference's default) and 8 (what it filters on under
+    Restrictions::disable_ext_deblock_subblock_size_4), the latter on the same kind of
+    partition: CUs down to 4x4 under the 8-sample grid."""
     xo, xr = libs
-    rng = np.random.default_rng(41 + bd + bipred)
+    for sub in (4, 8):
+        _deblock_against_ref(xo, xr, bd, bipred, sub)
+
+
+def _deblock_against_ref(xo, xr, bd, bipred, sub):
+    rng = np.random.default_rng(41 + bd + bipred + (0 if sub == 4 else 1000))
     total_changed = 0
     for (pw, ph) in [(64, 64), (136, 72), (200, 136)]:
         for trial in range(3):
@@ -300,14 +308,14 @@ def test_deblock(libs, bd, bipred):
             pr = [p.copy() for p in planes]
             po = [p.copy() for p in planes]
             beta, tc = [(0, 0), (2, -2), (-4, 4)][trial]
-            xr.deblock(bd, pw, ph, bipred, beta, tc, 4, cus, cmap, pr, borders, l0, l1)
-            xo.deblock(bd, pw, ph, bipred, beta, tc, 4, cus, cmap, po, borders)
+            xr.deblock(bd, pw, ph, bipred, beta, tc, sub, cus, cmap, pr, borders, l0, l1)
+            xo.deblock(bd, pw, ph, bipred, beta, tc, sub, cus, cmap, po, borders)
             changed = 0
             for c in range(3):
                 b = borders[c]
                 w, h = (pw, ph) if c == 0 else (pw // 2, ph // 2)
                 assert np.array_equal(pr[c][b:b + h, b:b + w], po[c][b:b + h, b:b + w]), \
-                    (pw, ph, trial, c)
+                    (sub, pw, ph, trial, c)
                 changed += int((pr[c] != planes[c]).sum())
             total_changed += changed
     assert total_changed > 0     # the filters did change samples
