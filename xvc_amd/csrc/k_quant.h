@@ -39,6 +39,7 @@ struct BlockQuant {
   bool bias;               // the odd log-size sum
   int tshift;              // the transform's scaling left to the quantiser
   int scale;               // forward: kFwdQuantScales[qp % 6] (x 181)
+  int scale_idx;           // which of the twelve forward scales: qp % 6, + 6 with the bias
   int shift;               // 14 + qp / 6 + tshift
   int size_bias_shift, size_bias_offset;
   int fq_shift;            // shift + size_bias_shift: what a magnitude * scale is shifted by
@@ -101,6 +102,7 @@ __device__ __forceinline__ BlockQuant block_quant(int w, int h, int qp, int bd, 
   q.bias = (lsum & 1) != 0;
   q.tshift = 15 - bd - (lsum >> 1);
   q.scale = kFwdQuantScales[qpb % 6] * (q.bias ? 181 : 1);
+  q.scale_idx = qpb % 6 + (q.bias ? 6 : 0);
   q.shift = 14 + qpb / 6 + q.tshift;
   q.size_bias_shift = q.bias ? 7 : 0;
   q.size_bias_offset = q.bias ? 64 : 0;
@@ -114,6 +116,50 @@ __device__ __forceinline__ BlockQuant block_quant(int w, int h, int qp, int bd, 
 }
 __device__ __forceinline__ BlockQuant block_quant(const xvcgpu_tx_block &b, int bd) {
   return block_quant(b.w, b.h, b.qp, bd, tx_block_flags(b.intra_pic).intra_pic);
+}
+
+// ---- the magnitudes at which the plain quantiser's level steps -------------------
+// fwd(a) >= 1 <=> a >= t1 and fwd(a) >= 2 <=> a >= t2 for magnitudes up to 32767 (fwd is
+// monotonic there: scale < 2^fq_shift): t_m = ceil(m * fq_offset / scale), m = 1 and 3.
+// They depend on the scale (twelve of them) and on fq_shift alone, so they are a table
+// made at compile time: one scalar load where the QP is the wave's.  A magnitude of 32768
+// reaches fwd as -32768 (the classification's `codes` and the proofs' callers cast to
+// short): it codes <=> 32768 * scale > fq_offset, which t1 answers too - t1 is 32769 where
+// 32768 * scale == fq_offset.  Thresholds above 65535 are entered as 65535 (no magnitude
+// gets there), as are those of an fq_shift outside the table.
+#define RQ_THR_SHIFTS 48
+struct RqLevelThrTable {
+  unsigned short t[12][RQ_THR_SHIFTS][2];
+};
+constexpr RqLevelThrTable rq_make_level_thr_table() {
+  constexpr int fwd[6] = {26214, 23302, 20560, 18396, 16384, 14564};   // kFwdQuantScales
+  RqLevelThrTable r{};
+  for (int i = 0; i < 12; i++) {
+    const unsigned long long scale = (unsigned long long)(fwd[i % 6] * (i < 6 ? 1 : 181));
+    for (int s = 0; s < RQ_THR_SHIFTS; s++) {
+      for (int m = 0; m < 2; m++) {
+        unsigned long long t = 65535;
+        if (s >= 1) {
+          const unsigned long long target = (m ? 3ull : 1ull) << (s - 1);   // m * fq_offset
+          t = (target + scale - 1) / scale;
+          if (m == 0 && t == 32768 && t * scale == target) t = 32769;
+          if (t > 65535) t = 65535;
+        }
+        r.t[i][s][m] = (unsigned short)t;
+      }
+    }
+  }
+  return r;
+}
+__constant__ RqLevelThrTable kRqLevelThr = rq_make_level_thr_table();
+struct RqLevelThr {
+  int t1, t2;
+};
+__device__ __forceinline__ RqLevelThr rq_level_thresholds(const BlockQuant &bq) {
+  if (bq.fq_shift < 0 || bq.fq_shift >= RQ_THR_SHIFTS) return {65535, 65535};
+  const uint32_t v =
+      *reinterpret_cast<const uint32_t *>(kRqLevelThr.t[bq.scale_idx][bq.fq_shift]);
+  return {(int)(v & 0xffff), (int)(v >> 16)};
 }
 
 // ---- the shifts of the four 1-D transform stages ---------------------------------

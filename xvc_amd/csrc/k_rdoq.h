@@ -984,6 +984,62 @@ rdoq_classify_kernel(int bd, const xvcgpu_tx_block *blocks, int n, const int16_t
 #define RQ_PROVE_BLOCKS 16
 #define RQ_PROVE_MAX_CANDS 16
 
+// What the context costs of a candidate with magnitude a come to: sig1 = the cheapest
+// significance "1" it can meet (0 where the flag may be inferred), flag_min = the cheapest
+// greater-1 bin, lp = the bits of a last position there, cbf0 / cbf1 = the bins of the
+// block's cbf.
+template <bool NARROW>
+__device__ __forceinline__ void rq_prove_price(const BlockQuant &bq, long long lambda, int a,
+                                               unsigned sig1, unsigned flag_min, unsigned lp,
+                                               unsigned cbf0, unsigned cbf1, long long &gain,
+                                               long long &gain_last, long long &rhs) {
+  auto price = [&](unsigned bits) -> long long {
+    if (NARROW)
+      return (long long)(((unsigned long long)bits * (unsigned long long)(unsigned)lambda) >> 16);
+    return rq_bit_cost(bits, lambda);
+  };
+  // a squared error |e| <= 65535 fits 32 bits (BlockQuant::dist's value)
+  auto dist = [&](int e) -> long long {
+    return (long long)((unsigned long long)((unsigned)e * (unsigned)e)) << bq.cost_scale;
+  };
+  const int q = bq.fwd(a);
+  const unsigned lvl_min = RQ_BYPASS + flag_min;   // sign + the cheapest continuation
+  long long d_best = dist(a - bq.dequant(q));
+  if (q > 1) {
+    const long long d1 = dist(a - bq.dequant(q - 1));
+    d_best = d1 < d_best ? d1 : d_best;
+  }
+  const long long zd = bq.zero_dist(a);
+  const long long coded = d_best + price(sig1 + lvl_min);
+  const long long coded_last = d_best + price(lvl_min);
+  gain = zd - (coded < zd ? coded : zd);
+  gain_last = zd - coded_last;
+  rhs = price(cbf1) - price(cbf0) + price(lp);
+}
+
+// A position's place in the scan: sub-block in the grid's scan, offset in the sub-block's
+// (the inverse of the 4x4 scan: position y * 4 + x -> scan offset, 16 nibbles).  W, H >
+// 0: the block is exactly that.
+template <int W, int H>
+__device__ __forceinline__ int rq_prove_scan_index(int scan_order, int w, int h, int x, int y) {
+  constexpr unsigned long long inv0 = rq_pack_scan4_inv(0), inv1 = rq_pack_scan4_inv(1),
+                               inv2 = rq_pack_scan4_inv(2);
+  const unsigned long long inv = scan_order == 0 ? inv0 : (scan_order == 1 ? inv1 : inv2);
+  const int kk = (int)((inv >> (4 * (((y & 3) << 2) | (x & 3)))) & 15ull);
+  int sb;
+  if constexpr (W >= 4 && H >= 4 && (W >> 2) * (H >> 2) <= 16) {
+    // the diagonal scan of this grid as a constant
+    constexpr int GW = W >> 2, GH = H >> 2;
+    constexpr unsigned long long kSb = rq_pack_sb_scan(GW, GH);
+    const int sx = x >> 2, sy = y >> 2;
+    sb = scan_order == 0 ? (int)((kSb >> (4 * (sy * GW + sx))) & 15ull)
+                         : (scan_order == 1 ? sy * GW + sx : sx * GH + sy);
+  } else {
+    sb = d_sb_scan_index(scan_order, w >> 2, h >> 2, x >> 2, y >> 2);
+  }
+  return (sb << 4) + kk;
+}
+
 // the smallest magnitude that quantises to a level: a * scale >= 2^(shift - 1)
 __device__ __forceinline__ int rq_prove_threshold(const BlockQuant &bq) {
   long long t = (long long)((double)bq.fq_offset / (double)bq.scale);
@@ -1169,67 +1225,209 @@ rdoq_prove_zero_kernel(int bd, const xvcgpu_tx_block *blocks, int n, const int16
 
 // The same proof where the coefficients of a block lie in LDS (the forward
 // transform of the frame pass, k_tx2.h: C[x][y] at c[x * h + y]): G lanes per
-// block, 64 / G blocks per wave; `cands` = the block's q > 0 coefficients already
-// collected by the caller (count n_c, positions (y << 8) | x), wrap = a magnitude
-// of 32768 was seen.  Returns true (to every lane of the group) when QuantRdo is
-// bound to return 0.  The wave's LDS: the snapshot's costs, staged on first use.
+// block, 64 / G blocks per wave; the block's q > 0 coefficients are collected by the
+// caller through rq_prove_collect (count nq, positions (y << 8) | x in xy).  Returns
+// true (to every lane of the group) when QuantRdo is bound to return 0.  The wave's LDS:
+// the candidates' positions, scan indices and gains, and - for the shapes without a
+// table of their own (rq_prove_tables) - the snapshot's costs, staged on first use.
 struct RqProveLds {
   __attribute__((aligned(16))) unsigned cb[2 * sizeof(xvcgpu_rdoq_contexts)];
-  long long gain[2][RQ_PROVE_MAX_CANDS];
-  int idx[2][RQ_PROVE_MAX_CANDS];
+  __attribute__((aligned(16))) long long gain[2][RQ_PROVE_MAX_CANDS];
+  __attribute__((aligned(16))) int idx[2][RQ_PROVE_MAX_CANDS];
   unsigned short xy[2][RQ_PROVE_MAX_CANDS];
-  int n[2];
-  int fail[2];
   int staged_ctx;   // snapshot whose costs cb holds (-1: none yet)
 };
 
+// The candidates of the block at c: position i (C[x][y] at i = x * h + y) is entered by
+// the lane that holds a magnitude of at least thr.t1 there - its slot is the group's
+// count so far plus the hits in the lanes below it, from the ballot: no atomic, no
+// count in LDS.  `hit`: this lane's coefficient codes; nq: the group's running count
+// (the same in all its lanes).  Only the first RQ_PROVE_MAX_CANDS are kept; a trip
+// without a hit in the wave costs a ballot and a branch.
 template <int G>
+__device__ __forceinline__ void rq_prove_collect(RqProveLds *pv, bool hit, int i, int h, int lgh,
+                                                 int &nq) {
+  static_assert(G == 64 || G == 32, "a wave or half a wave per block");
+  const unsigned long long hits = __ballot(hit);
+  if (!hits) return;   // (wave-uniform)
+  const unsigned lo = (unsigned)hits, hi = (unsigned)(hits >> 32);
+  int below, total;
+  if (G == 64) {
+    below = (int)__builtin_amdgcn_mbcnt_hi(hi, __builtin_amdgcn_mbcnt_lo(lo, 0u));
+    total = __popc(lo) + __popc(hi);
+  } else {
+    const bool up = (threadIdx.x & 32) != 0;
+    below = up ? (int)__builtin_amdgcn_mbcnt_hi(hi, 0u) : (int)__builtin_amdgcn_mbcnt_lo(lo, 0u);
+    total = up ? __popc(hi) : __popc(lo);
+  }
+  const int slot = nq + below;
+  if (pv && hit && slot < RQ_PROVE_MAX_CANDS)
+    pv->xy[(threadIdx.x & 63) / G][slot] = (unsigned short)(((i & (h - 1)) << 8) | (i >> lgh));
+  nq += total;
+}
+
+// The context costs any candidate of a wave of S x S blocks (S = 16 or 8; all luma or all
+// chroma) can ask for, one entry per lane, in rows of eight lanes:
+//   rows 0, 1  lane t: the bits of a last position in group t of the x / y axis
+//   rows 2-4   lane t: the cheapest significance "1" over the counts 0 .. t, for the sets
+//              of x + y < 2, < 5 and beyond (rq_sig_ctx_base); lane 6 of row 2 holds the
+//              cbf context instead (its bins in zero / one)
+//   rows 5-7   lane t: the cheapest greater-1 bin (or a bypass bin) over the last
+//              position's context and those of the counts 1 .. t, for x + y < 3, < 10 and
+//              beyond (rq_greater_start)
+// A lane reads the state of its ONE context from the snapshot and its two costs from the
+// table of bit costs - no snapshot staged in LDS -, the prefix sums (rows 0, 1) and minima
+// run along the rows by DPP; a candidate then fetches four entries by lane index.
+struct RqProveRow {
+  unsigned t, zero, one;
+};
+template <int S>
+__device__ __forceinline__ RqProveRow rq_prove_tables(const xvcgpu_rdoq_contexts *snap, bool luma,
+                                                      bool intra_cu) {
+  static_assert(S == 16 || S == 8, "last-position groups 0 .. 7 fit a row");
+  constexpr int LS = S == 16 ? 4 : 3;
+  const int wl = (int)(threadIdx.x & 63), t = wl & 7, row = wl >> 3;
+  const int gmax = rq_last_pos_group(S - 1), gc = gmax - 1;
+  const int tc = t < 5 ? t : 5;
+  int ctx;   // this lane's context: its byte in the snapshot
+  if (row < 2) {
+    ctx = rq_last_pos_ctx(luma, S, S, t < gc ? t : gc, row == 0) >> 1;
+  } else if (row < 5) {
+    ctx = (rq_sig_ctx_base(luma, row == 2 ? 0 : (row == 3 ? 2 : 5), LS) >> 1) + tc;
+    if (wl == 22)
+      ctx = !luma ? RQ_OFF(cbf_chroma) : (intra_cu ? RQ_OFF(cbf_luma) : RQ_OFF(root_cbf));
+  } else {
+    const int g1 = rq_greater1_off(luma);
+    ctx = t == 0 ? g1 : g1 + rq_greater_start(luma, row == 5 ? 0 : (row == 6 ? 3 : 10)) + tc;
+  }
+  const unsigned st = reinterpret_cast<const unsigned char *>(snap)[ctx] & 127u;
+  const unsigned zero = gEntropyBits[st], one = gEntropyBits[st ^ 1u];
+  const bool sum = row < 2;
+  const unsigned own = row < 5 ? one : (zero < one ? zero : one);
+  unsigned v = own;
+  // inclusive scan along the row's eight lanes (row_shr: the lane 1, 2, 4 below)
+  auto step = [&](unsigned got, int s) {
+    if (t >= s) v = sum ? v + got : (got < v ? got : v);
+  };
+  step((unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false), 1);
+  step((unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, false), 2);
+  step((unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, false), 4);
+  unsigned tv;
+  if (sum)   // GetLastPosBits: the ones below the group, its zero unless it is the last, the suffix
+    tv = v - own + (t < gmax ? zero : 0u) + (t > 3 ? (unsigned)((t - 2) >> 1) * RQ_BYPASS : 0u);
+  else if (row < 5)
+    tv = v;
+  else
+    tv = v < RQ_BYPASS ? v : RQ_BYPASS;
+  return {tv, zero, one};
+}
+
+// nq: the group's candidates as rq_prove_collect counted them (0: the block is not
+// live), thr: rq_level_thresholds(bq); w, h: the block's size (W, H > 0: exactly that, a
+// constant).  The exact 16x16 and 8x8 instances (the forward kernel's: a wave holds luma
+// blocks or chroma blocks, never both) take their context costs from rq_prove_tables and
+// every lane runs the candidate's arithmetic, masked at the end; any other shape stages the
+// snapshot in pv.cb and runs rq_prove_candidate in the candidates' lanes.  A candidate
+// with a magnitude of 32768 fails its block (such a magnitude is a candidate wherever
+// anything is).
+template <int G, int W, int H>
 __device__ __forceinline__ bool rq_prove_zero_lds(RqProveLds &pv, const xvcgpu_tx_block &b,
-                                                  int bd,
+                                                  int w, int h, const BlockQuant &bq,
+                                                  const RqLevelThr &thr,
                                                   const xvcgpu_rdoq_contexts *rq_ctx,
-                                                  const xvcgpu_rdoq_params &prm,
-                                                  const int16_t *c, bool live) {
+                                                  const xvcgpu_rdoq_params *rq_prm, int bi,
+                                                  const int16_t *c, int nq) {
   const int wl = (int)(threadIdx.x & 63), lane = wl & (G - 1), grp = wl / G;
-  const int w = b.w, h = b.h;
-  const int nq = pv.n[grp];
-  bool tried = live && nq >= 1 && nq <= RQ_PROVE_MAX_CANDS && !pv.fail[grp] && w >= 4 && h >= 4 &&
-               w <= 32 && h <= 32;
+  const unsigned long long group = G == 64 ? ~0ull : (((1ull << G) - 1) << (wl & ~(G - 1)));
+  bool tried = nq >= 1 && nq <= RQ_PROVE_MAX_CANDS && w >= 4 && h >= 4 && w <= 32 && h <= 32;
   // the wave's snapshot: the first trying group's
   const unsigned long long tm = __ballot(tried);
   if (!tm) return false;
+  const xvcgpu_rdoq_params prm = rq_prm[bi];
   const int wave_ctx = __shfl((int)prm.ctx_index, __ffsll((long long)tm) - 1, 64);
   tried = tried && (int)prm.ctx_index == wave_ctx;
-  if (pv.staged_ctx != wave_ctx) {
-    wave_sync();
-    rq_stage_costs(gEntropyBits, &rq_ctx[wave_ctx], pv.cb, wl, 64);
-    if (wl == 0) pv.staged_ctx = wave_ctx;
-    wave_sync();
-  }
-  const BlockQuant bq = block_quant(b, bd);
-  auto qat = [&](int x, int y) {
-    if (x >= w || y >= h) return 0;
-    return bq.fwd((short)d_abs((int)c[x * h + y]));
-  };
-  long long gain_last = 0, rhs = 0;
-  int my_idx = 0;
+  wave_sync();   // the candidates' positions are in place
+  long long gain = 0, gain_last = 0, rhs = 0;
+  int my_idx = 0x7fffffff;   // (a lane without a candidate: in front of nobody)
+  bool over = false;         // the magnitude that wraps
   const bool cand = tried && lane < nq;
-  if (cand) {
-    const int x = pv.xy[grp][lane] & 255, y = pv.xy[grp][lane] >> 8;
-    const int a = (short)d_abs((int)c[x * h + y]);
-    long long gain;
-    rq_prove_candidate(bq, b, prm, pv.cb, x, y, a, qat, gain, gain_last, rhs, my_idx);
+  if constexpr (W == H && (W == 16 || W == 8)) {
+    // the magnitude at a position, 0 outside the block: a neighbour quantises to a level /
+    // to more than 1 from thr.t1 / thr.t2 on
+    auto mag = [&](int x, int y) {
+      if (x >= W || y >= H) return 0;
+      return d_abs((int)c[x * H + y]);
+    };
+    // lambda fits 32 bits (every real one does): a price is a 32 x 32 -> 64 bit product; one
+    // of more than 32 bits anywhere in the wave: the 64-bit prices for all of it
+    const bool narrow = __ballot(cand && (unsigned long long)prm.lambda > 0xffffffffull) == 0;
+    const int scan_order = tx_block_flags(b.intra_pic).scan_order;
+    const bool luma = __builtin_amdgcn_readfirstlane((int)(b.comp == 0)) != 0;
+    const RqProveRow row =
+        rq_prove_tables<W>(&rq_ctx[wave_ctx], luma, (prm.flags & XVC_RDOQ_INTRA_CU) != 0);
+    const unsigned xy = cand ? pv.xy[grp][lane] : 0u;   // (the others: position (0, 0))
+    const int x = (int)(xy & 255u), y = (int)(xy >> 8);
+    const int a = d_abs((int)c[x * H + y]);
+    over = a == 32768;
+    const int m0 = mag(x + 1, y), m1 = mag(x + 2, y), m2 = mag(x + 1, y + 1), m3 = mag(x, y + 1),
+              m4 = mag(x, y + 2);
+    const int cnt =
+        (m0 >= thr.t1) + (m1 >= thr.t1) + (m2 >= thr.t1) + (m3 >= thr.t1) + (m4 >= thr.t1);
+    const int cnt1 =
+        (m0 >= thr.t2) + (m1 >= thr.t2) + (m2 >= thr.t2) + (m3 >= thr.t2) + (m4 >= thr.t2);
+    const int posxy = x + y;
+    const int scls = (posxy >= 2) + (posxy >= 5), gcls = (posxy >= 3) + (posxy >= 10);
+    unsigned sig1 = __shfl(row.t, 16 + 8 * scls + cnt, 64);
+    const unsigned flag_min = __shfl(row.t, 40 + 8 * gcls + rq_greater_nn(cnt1, false), 64);
+    const unsigned lp = __shfl(row.t, rq_last_pos_group(scan_order == 2 ? y : x), 64) +
+                        __shfl(row.t, 8 + rq_last_pos_group(scan_order == 2 ? x : y), 64);
+    const unsigned cbf0 = __shfl(row.zero, 22, 64), cbf1 = __shfl(row.one, 22, 64);
+    if (((x | y) & 3) == 0 && (x | y) != 0) sig1 = 0;   // k = 0 behind the first sub-block
+    if (narrow)
+      rq_prove_price<true>(bq, prm.lambda, a, sig1, flag_min, lp, cbf0, cbf1, gain, gain_last, rhs);
+    else
+      rq_prove_price<false>(bq, prm.lambda, a, sig1, flag_min, lp, cbf0, cbf1, gain, gain_last,
+                            rhs);
+    if (cand) my_idx = rq_prove_scan_index<W, H>(scan_order, W, H, x, y);
+  } else {
+    if (pv.staged_ctx != wave_ctx) {
+      rq_stage_costs(gEntropyBits, &rq_ctx[wave_ctx], pv.cb, wl, 64);
+      if (wl == 0) pv.staged_ctx = wave_ctx;
+      wave_sync();
+    }
+    auto qat = [&](int x, int y) {
+      if (x >= w || y >= h) return 0;
+      return bq.fwd((short)d_abs((int)c[x * h + y]));
+    };
+    if (cand) {
+      const int x = pv.xy[grp][lane] & 255, y = pv.xy[grp][lane] >> 8;
+      const int a = d_abs((int)c[x * h + y]);
+      over = a == 32768;
+      rq_prove_candidate(bq, b, prm, pv.cb, x, y, a, qat, gain, gain_last, rhs, my_idx);
+    }
+  }
+  // all sixteen rows of a trying group are written, so the sum below reads them four at
+  // a time and asks only for the scan index
+  if (tried && lane < RQ_PROVE_MAX_CANDS) {
     pv.idx[grp][lane] = my_idx;
     pv.gain[grp][lane] = gain;
   }
   wave_sync();
+  bool bad = false;
   if (cand) {
     long long before = 0;
-    for (int j = 0; j < nq; j++)
-      if (pv.idx[grp][j] < my_idx) before += pv.gain[grp][j];
-    if (before + gain_last >= rhs) pv.fail[grp] = 1;
+    for (int j = 0; j < nq; j += 4) {
+      const int4 id = *reinterpret_cast<const int4 *>(&pv.idx[grp][j]);
+      const longlong2 g01 = *reinterpret_cast<const longlong2 *>(&pv.gain[grp][j]);
+      const longlong2 g23 = *reinterpret_cast<const longlong2 *>(&pv.gain[grp][j + 2]);
+      before += id.x < my_idx ? g01.x : 0ll;
+      before += id.y < my_idx ? g01.y : 0ll;
+      before += id.z < my_idx ? g23.x : 0ll;
+      before += id.w < my_idx ? g23.y : 0ll;
+    }
+    bad = over || before + gain_last >= rhs;
   }
-  wave_sync();
-  return tried && !pv.fail[grp];
+  return tried && (__ballot(bad) & group) == 0;
 }
 
 // The class lists from the per-block classes, without atomics (a few thousand

@@ -30,7 +30,8 @@ __device__ __forceinline__ unsigned long long d_scan4_table(int order) {
 }
 // Index of sub-block (sx, sy) in the scan over a gw x gh grid of sub-blocks
 // (TransformHelper::DeriveSubblockScan, transform.cc:1639-1683).
-__device__ __forceinline__ int d_sb_scan_index(int order, int gw, int gh, int sx, int sy) {
+// (constexpr: also evaluated at compile time, rq_pack_sb_scan below)
+__attribute__((always_inline)) constexpr int sb_scan_index(int order, int gw, int gh, int sx, int sy) {
   if (order == 1) return sy * gw + sx;
   if (order == 2) return sx * gh + sy;
   const int s = sx + sy;
@@ -42,6 +43,18 @@ __device__ __forceinline__ int d_sb_scan_index(int order, int gw, int gh, int sx
     idx += c + 1;
   }
   return idx + ((s < gh - 1 ? s : gh - 1) - sy);
+}
+__device__ __forceinline__ int d_sb_scan_index(int order, int gw, int gh, int sx, int sy) {
+  return sb_scan_index(order, gw, gh, sx, sy);
+}
+// The diagonal scan's index of every sub-block of a gw x gh grid of at most sixteen, as
+// nibbles: sub-block (sx, sy) at nibble sy * gw + sx.
+constexpr unsigned long long rq_pack_sb_scan(int gw, int gh) {
+  unsigned long long r = 0;
+  for (int sy = 0; sy < gh; sy++)
+    for (int sx = 0; sx < gw; sx++)
+      r |= (unsigned long long)sb_scan_index(0, gw, gh, sx, sy) << (4 * (sy * gw + sx));
+  return r;
 }
 
 // One 4x4 sub-block, by one thread.  IDX(x, y) maps a coefficient position

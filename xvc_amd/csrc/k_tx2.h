@@ -238,39 +238,52 @@ __device__ __forceinline__ int tx2_job(Tx2Shared &sh, const xvcgpu_tx_block &b, 
       if (fc && fc->cls) {
         // the classification pass of the RDO quantiser (rdoq_classify_kernel, k_rdoq.h)
         // on the coefficients at hand: does any of them quantise to a level at all?
+        // A magnitude codes from the block's threshold on (one compare; the thresholds are
+        // one load from a table, a scalar one where the QP is the wave's).  The coefficients
+        // that code are the candidates of the all-zero proof: C[x][y] at s.c[x * h + y].
         const BlockQuant q = quant();
-        bool any = false;
+        const RqLevelThr thr = rq_level_thresholds(q);
         RqProveLds *pv = fc->pv;
-        const int grp = ME2_LANE / G;
-        if (pv) {
-          if (lane == 0) {
-            pv->n[grp] = 0;
-            pv->fail[grp] = 0;
+        int nq = 0;          // the block's coefficients that code
+        auto look = [&](int i, int cf) {
+          rq_prove_collect<G>(pv, i < n_el && d_abs(cf) >= thr.t1, i, h, lgh, nq);
+        };
+        if constexpr (NE > 0) {
+          // the exact shapes: a lane's coefficients side by side, one read
+          constexpr int PER = NE / G;
+          static_assert(PER * G == NE && (PER == 2 || PER == 4), "16x16 by a wave, 8x8 by half");
+          if constexpr (PER == 4) {
+            const uint2 v = *reinterpret_cast<const uint2 *>(s.c + 4 * lane);
+            look(4 * lane, (int)(short)(v.x & 0xffff));
+            look(4 * lane + 1, (int)v.x >> 16);
+            look(4 * lane + 2, (int)(short)(v.y & 0xffff));
+            look(4 * lane + 3, (int)v.y >> 16);
+          } else {
+            const uint32_t v = *reinterpret_cast<const uint32_t *>(s.c + 2 * lane);
+            look(2 * lane, (int)(short)(v & 0xffff));
+            look(2 * lane + 1, (int)v >> 16);
           }
-          wave_sync();
-        }
-        lane_loop<NE, G>(lane, n_el, [&](int i) {
-          const int a = (short)d_abs((int)s.c[i]);
-          const bool nz = q.codes(a);
-          any |= nz;
-          if (pv && nz) {   // a candidate of the all-zero proof: C[x][y] at s.c[x * h + y]
-            const int slot = atomicAdd(&pv->n[grp], 1);
-            if (slot < RQ_PROVE_MAX_CANDS)
-              pv->xy[grp][slot] = (unsigned short)(((i & (h - 1)) << 8) | (i >> lgh));
-            if (a < 0) pv->fail[grp] = 1;   // a magnitude of 32768: no proof
+        } else {
+          // (every lane of the group takes every trip: the ballots count all of them)
+          for (int i0 = 0; i0 < n_el; i0 += G) {
+            const int i = i0 + lane;
+            look(i, i < n_el ? (int)s.c[i] : 0);
           }
-        });
-        const unsigned long long group =
-            G == 64 ? ~0ull : (((1ull << G) - 1) << (ME2_LANE & ~(G - 1)));
-        bool live = (__ballot(any) & group) != 0;
-        if (pv) {
-          wave_sync();
-          if (rq_prove_zero_lds<G>(*pv, b, bd, fc->rq_ctx, fc->rq_prm[bi], s.c, live)) live = false;
         }
+        bool live = nq != 0;
+        if (pv && rq_prove_zero_lds<G, FW, FH>(*pv, b, w, h, q, thr, fc->rq_ctx, fc->rq_prm, bi,
+                                               s.c, nq))
+          live = false;
         if (lane == 0) fc->cls[bi] = live ? (signed char)rq_class_of(b) : (signed char)-1;
         if (!live) {   // its levels are zeros; the coefficients are not needed again
           int16_t *z = fc->levels + level_off[bi];
-          lane_loop<NE, G>(lane, n_el, [&](int i) { z[i] = 0; });
+          // 16 bytes per store where the block starts on 16 bytes and is whole vectors
+          if ((n_el & 7) == 0 && (reinterpret_cast<uintptr_t>(z) & 15) == 0)
+            lane_loop<NE, 8 * G>(lane * 8, n_el, [&](int i) {
+              *reinterpret_cast<uint4 *>(z + i) = make_uint4(0u, 0u, 0u, 0u);
+            });
+          else
+            lane_loop<NE, G>(lane, n_el, [&](int i) { z[i] = 0; });
           if (lane == 0 && fc->nnz) fc->nnz[bi] = 0;
           return 0;
         }
