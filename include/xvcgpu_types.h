@@ -230,7 +230,11 @@ typedef struct xvcgpu_copy_block {
  * Positions / sizes are in samples of `comp`.  The neighbour fields are what
  * IntraPrediction::DetermineNeighbors (:688-705) derives from the CU map:
  * which already reconstructed neighbours exist (the prediction reads the
- * reconstruction picture around the block). */
+ * reconstruction picture around the block).  As DetermineNeighbors guarantees,
+ * above_right > 0 requires XVC_INTRA_HAS_ABOVE and below_left > 0 requires
+ * XVC_INTRA_HAS_LEFT: the reference looks at either extent only inside its
+ * side's branch, the device reads the declared extent regardless, so a job that
+ * breaks this is predicted differently by the two. */
 #define XVC_INTRA_HAS_ABOVE_LEFT 1
 #define XVC_INTRA_HAS_ABOVE 2
 #define XVC_INTRA_HAS_LEFT 4

@@ -94,6 +94,8 @@ def random_jobs(rng, pic_w, pic_h, comp, n, sizes=(4, 8, 16, 32, 64)):
             room = max(0, min(w, pic_h - (y + h)))
             bl = int(rng.choice([0, room, int(rng.integers(0, room // step + 1)) * step]))
         j["x"], j["y"], j["w"], j["h"], j["comp"] = x, y, w, h, comp
+        # what DetermineNeighbors guarantees (include/xvcgpu_types.h)
+        assert (ar == 0 or nb & HAS_ABOVE) and (bl == 0 or nb & HAS_LEFT)
         j["neighbors"], j["above_right"], j["below_left"] = nb, ar, bl
         j["mode"] = int(rng.integers(0, NUM_MODES))
     return jobs
@@ -121,3 +123,21 @@ def lm_chroma(lib, prefix, bd, comp, x, y, w, h, planes):
         ph, pw = planes[0].shape
         f(bd, comp, x, y, w, h, pw, ph, pp, ss, C.cast(out.ctypes.data, u16p), w)
     return out
+
+
+def pred_jobs(lib, prefix, bd, jobs, rec_plane, pred_plane, pic_w, pic_h):
+    """The prediction of every job (mutually disjoint blocks of one component) written into
+    pred_plane at the block's place; (pic_w, pic_h): the luma picture's size."""
+    f = getattr(lib.dll, prefix + "_intra_pred_block")
+    f.restype = None
+    jobs = np.ascontiguousarray(jobs, INTRA_DTYPE)
+    rp, rs = _p(rec_plane)
+    pp, ps = _p(pred_plane)
+    if prefix == "xo":
+        f.argtypes = [C.c_int, C.c_void_p, u16p, pd, u16p, pd]
+        for i in range(len(jobs)):
+            f(bd, jobs.ctypes.data + i * INTRA_DTYPE.itemsize, rp, rs, pp, ps)
+    else:
+        f.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, u16p, pd, u16p, pd]
+        for i in range(len(jobs)):
+            f(bd, jobs.ctypes.data + i * INTRA_DTYPE.itemsize, pic_w, pic_h, rp, rs, pp, ps)
