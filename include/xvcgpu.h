@@ -1489,6 +1489,74 @@ xvcgpu_status xvcgpu_frame_pass_affine(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_
                                        const xvcgpu_frame_pass_affine_args *f,
                                        const xvcgpu_me_plan *plan, int phases);
 
+/* ---- the B frame pass with affine motion ---------------------------------------- *
+ * CompressInter's second SearchMotion run (three-corner model, both lists, the
+ * SearchBiIterative step on affine vectors) behind the plain run of
+ * xvcgpu_frame_pass_bi_refs; k_fp_bi_affine.h; nothing is read back.  xvcgpu_types.h:
+ * xvcgpu_fp_bi_affine_result, xvcgpu_frame_pass_bi_affine_args.  E = 2 * Rmax, Rmax =
+ * max(num_ref); uni-directional job [i * E + l * Rmax + r], refinement job [i * Rmax + k].
+ * The four small entries take the pass's two blocks and read the tables of `a`
+ * (num_ref, same_poc_in_l0, slot, ref_poc, d_me, d_results, side bits, d_choice, d_inter).
+ *
+ * xvcgpu_fp_bi_affine_boot: one thread per (listed CU, e < E).  A job whose first slot byte
+ * is XVC_FP_BI_NO_JOB is not touched; else bootstrap = the plain result's vector of (l, r)
+ * through ClipMv at all three corners and flags = XVC_AFFINE_ME_HAS_BOOTSTRAP, or, for a
+ * plain result of XVCGPU_ME_UNSUPPORTED, flags = XVC_AFFINE_ME_NO_JOB and bootstrap zero.
+ * xvcgpu_affine_me_listed_refs: affine_me over the jobs of the listed CUs, per_cu jobs per
+ * CU, every picture in one launch per non-empty height class (NW = 2, 4, 8 for heights 16,
+ * 32, 64): workgroup g of class c takes job d_order[first_c + g / per_cu] * per_cu + g %
+ * per_cu; the searched plane is refs[d_slots[2 job]], with XVC_AFFINE_ME_BIPRED the other
+ * list's refs[d_slots[2 job + 1]].  A first slot byte >= n_refs, or XVC_AFFINE_ME_NO_JOB:
+ * the result is not touched.  Results equal xvcgpu_affine_me_batch_refs' record for record.
+ * xvcgpu_fp_bi_affine_uni_fold: one thread per CU.  A CU counts as searched where d_me[0][0]
+ * says it is capable and every job of its E that names a picture carries
+ * XVC_AFFINE_ME_HAS_BOOTSTRAP.  Per (l, r) in index order: dist and vectors are the search's,
+ * for a re-used list-1 entry list 0's of same_poc_in_l0[r]; cost = dist + (((side_bits_uni[l]
+ * + RefIdxBits(num_ref[l], r) + 1 + the exp-Golomb bits of corner 0's and corner 1's
+ * quarter-sample difference to that job's mvp) * lambda16) >> 16), 64-bit product kept in 32
+ * bits; best per list on strict <, cost_l1_unique over the unique pictures; search_list =
+ * cost_0 <= cost_1 ? 1 : 0.  Writes the fold's fields of d_choice[i] and the CU's Rmax
+ * refinement jobs: the (s, k) job's x, y, w, h, lambda16, mvp; bootstrap = the affine vectors
+ * of (s, k); other_mv = the winner of list 1 - s; flags HAS_BOOTSTRAP | BIPRED; slot bytes
+ * {slot[s][k], slot[1-s][best_ref[1-s]]}, XVC_FP_BI_NO_JOB first for k >= num_ref[s].  A CU
+ * that was not searched: no-job slots only.
+ * xvcgpu_fp_bi_affine_choice: one thread per CU.  k in picture order from UINT32_MAX on
+ * strict <; bits = side_bits_bi + for both lists RefIdxBits + 1 + the corner bits against
+ * that (l, r) job's mvp; ChooseUniOrBi(cost_l0, cost_l1_unique, cost_bi) as
+ * xvcgpu_fp_bi_refs_choice; affine only where cost_affine < a->d_choice[i].cost.  Writes
+ * f->d_choice[i]; where affine wins rewrites a->d_inter[3 i + comp] (XVC_INTER_AFFINE, ref[l]
+ * = the slot or -1, three corners per used list), else leaves them.
+ * xvcgpu_cu_info_from_bi_affine_choice: xvcgpu_cu_info_from_choice_refs with corners (an
+ * affine CU's used list: UL, UR, DL and DR = UR + DL - UL).
+ *
+ * xvcgpu_frame_pass_bi_refs_affine: launches 1-4 of xvcgpu_frame_pass_bi_refs unchanged ->
+ * boot -> the listed search over the E jobs -> uni fold -> the listed search over the
+ * refinement jobs -> choice -> xvcgpu_inter_pred_batch -> the residual pipeline of the form
+ * -> the record kernel -> the B tail.  Every check of xvcgpu_frame_pass_bi_refs (a set
+ * force_l1_mvd_zero, the _from_me forms, part of a picture, plans with LIC jobs) and of `f`
+ * (a missing array, n_class) happens before the first launch; then the call only enqueues. */
+xvcgpu_status xvcgpu_fp_bi_affine_boot(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_bi_refs_args *a,
+                                       const xvcgpu_frame_pass_bi_affine_args *f);
+xvcgpu_status xvcgpu_affine_me_listed_refs(xvcgpu_ctx *ctx, const xvcgpu_picture *orig,
+                                           const xvcgpu_picture *const *refs, int n_refs,
+                                           const xvcgpu_affine_me_block *d_blocks,
+                                           const uint8_t *d_slots, int n_cus, int per_cu,
+                                           const int32_t *d_order, const int32_t n_class[3],
+                                           xvcgpu_affine_me_result *d_results);
+xvcgpu_status xvcgpu_fp_bi_affine_uni_fold(xvcgpu_ctx *ctx,
+                                           const xvcgpu_frame_pass_bi_refs_args *a,
+                                           const xvcgpu_frame_pass_bi_affine_args *f);
+xvcgpu_status xvcgpu_fp_bi_affine_choice(xvcgpu_ctx *ctx,
+                                         const xvcgpu_frame_pass_bi_refs_args *a,
+                                         const xvcgpu_frame_pass_bi_affine_args *f);
+xvcgpu_status xvcgpu_cu_info_from_bi_affine_choice(xvcgpu_ctx *ctx,
+                                                   const xvcgpu_frame_pass_bi_refs_args *a,
+                                                   const xvcgpu_frame_pass_bi_affine_args *f);
+xvcgpu_status xvcgpu_frame_pass_bi_refs_affine(
+    xvcgpu_ctx *ctx, const xvcgpu_frame_pass_bi_refs_args *a,
+    const xvcgpu_frame_pass_bi_affine_args *f,
+    const xvcgpu_me_plan *const plans[2][XVC_CS_MAX_REFS], int phases);
+
 /* ---- tables (host side, no GPU needed) ---------------------------------- *
  * The 8-bit-fraction transform matrices the kernels use (transform_data.cc:
  * 109-796), for table-equality tests. out: size*size int16 row-major. */

@@ -780,6 +780,54 @@ typedef struct xvcgpu_frame_pass_affine_args {
   xvcgpu_inter_block *d_inter;               /* 3 * n_cus: the prediction jobs Y, U, V   */
 } xvcgpu_frame_pass_affine_args;
 
+/* ---- the B frame pass with affine motion (xvcgpu_frame_pass_bi_refs_affine) -------- *
+ * CompressInter's second SearchMotion run over both lists (inter_search.cc:74-99 with
+ * SearchRefIdx<true> :484-572 and SearchBiIterative on affine vectors :394-435), behind
+ * xvcgpu_frame_pass_bi_refs' plain run.  What the pass ends with for one CU: the chosen
+ * state (use_affine 0: the plain choice's, its vector at every corner) and the affine run's
+ * costs as xvcgpu_fp_bi_refs_result words the plain run's.  Unused entries hold UINT32_MAX
+ * as a cost, -1 as an index and 0 as a vector.  A CU that is not capable or was not
+ * searched: use_affine 0, cost_affine UINT32_MAX, the affine run's fields unused.  A CU whose
+ * plain search has no kernel instance: every byte 0xff. */
+typedef struct xvcgpu_fp_bi_affine_result {
+  int32_t use_affine;
+  int32_t inter_dir;          /* the chosen state's: 0 L0, 1 L1, 2 bi                    */
+  int32_t ref_idx[2];         /* ... picture per list; -1: list unused                   */
+  int32_t mv[2][3][2];        /* ... corners UL, UR, DL per list; the unused list zero   */
+  uint32_t cost;              /* the chosen state's                                      */
+  uint32_t cost_plain;        /* xvcgpu_fp_bi_refs_result.cost of the plain run          */
+  uint32_t cost_affine;       /* the affine run's ChooseUniOrBi cost; UINT32_MAX: none   */
+  int32_t search_list;        /* the affine run's refined list; -1: none                 */
+  uint32_t cost_list[2];      /* the affine run's SearchRefIdx cost per list             */
+  uint32_t cost_l1_unique;
+  uint32_t cost_bi;
+  int32_t best_ref[2];
+  int32_t best_ref_l1_unique;
+  uint32_t cost_uni[2][XVC_CS_MAX_REFS];
+  uint32_t bi_cost[XVC_CS_MAX_REFS];
+} xvcgpu_fp_bi_affine_result;
+
+/* What xvcgpu_frame_pass_bi_refs_affine takes beside xvcgpu_frame_pass_bi_refs' block; every
+ * array is the caller's.  E = 2 * Rmax, Rmax = max(num_ref).  d_uni: job [i * E + l * Rmax +
+ * r] is CU i into picture r of list l - the caller fills x, y, w, h, lambda16 and mvp (an
+ * input: no AMVP derivation), flags 0; the device writes flags and bootstrap.  d_uni_slots:
+ * two bytes per job {slot[l][r], 255}, the first XVC_FP_BI_NO_JOB for r >= num_ref[l] and
+ * for a list-1 picture with same_poc_in_l0[r] >= 0 (the caller's).  d_bi, d_bi_results,
+ * d_bi_slots: the CU's Rmax refinement jobs [i * Rmax + k], written by the device.  d_order,
+ * n_class: as xvcgpu_frame_pass_affine_args, made from d_me[0][0]. */
+typedef struct xvcgpu_frame_pass_bi_affine_args {
+  xvcgpu_affine_me_block *d_uni;             /* n_cus * E                                */
+  xvcgpu_affine_me_result *d_uni_results;    /* n_cus * E                                */
+  const uint8_t *d_uni_slots;                /* 2 * n_cus * E                            */
+  xvcgpu_affine_me_block *d_bi;              /* n_cus * Rmax                             */
+  xvcgpu_affine_me_result *d_bi_results;     /* n_cus * Rmax                             */
+  uint8_t *d_bi_slots;                       /* 2 * n_cus * Rmax                         */
+  const int32_t *d_order;                    /* n_class[0] + n_class[1] + n_class[2]     */
+  int32_t n_class[3];
+  int32_t reserved;
+  xvcgpu_fp_bi_affine_result *d_choice;      /* n_cus                                    */
+} xvcgpu_frame_pass_bi_affine_args;
+
 /* ---- C1, decision half: the folds of CompressAndEvalTransform and of
  * CompressAndEvalCbf (transform_encoder.cc:53-201, inter_search.cc:261-365).
  * Distortions come from the device's own kernels; the bits an alternative costs

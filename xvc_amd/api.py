@@ -208,6 +208,26 @@ class FramePassAffineArgs(C.Structure):
 
 assert C.sizeof(FramePassAffineArgs) == 56
 
+# xvcgpu_fp_bi_affine_result: CompressInter's two SearchMotion runs for one CU of a B picture
+FP_BI_AFFINE_RESULT_DTYPE = np.dtype([
+    ("use_affine", "<i4"), ("inter_dir", "<i4"), ("ref_idx", "<i4", (2,)),
+    ("mv", "<i4", (2, 3, 2)), ("cost", "<u4"), ("cost_plain", "<u4"), ("cost_affine", "<u4"),
+    ("search_list", "<i4"), ("cost_list", "<u4", (2,)), ("cost_l1_unique", "<u4"),
+    ("cost_bi", "<u4"), ("best_ref", "<i4", (2,)), ("best_ref_l1_unique", "<i4"),
+    ("cost_uni", "<u4", (2, CS_MAX_REFS)), ("bi_cost", "<u4", (CS_MAX_REFS,))])
+assert FP_BI_AFFINE_RESULT_DTYPE.itemsize == 144
+
+
+class FramePassBiAffineArgs(C.Structure):
+    """xvcgpu_frame_pass_bi_affine_args (include/xvcgpu_types.h)"""
+    _fields_ = [("d_uni", C.c_void_p), ("d_uni_results", C.c_void_p), ("d_uni_slots", C.c_void_p),
+                ("d_bi", C.c_void_p), ("d_bi_results", C.c_void_p), ("d_bi_slots", C.c_void_p),
+                ("d_order", C.c_void_p), ("n_class", C.c_int32 * 3), ("reserved", C.c_int32),
+                ("d_choice", C.c_void_p)]
+
+
+assert C.sizeof(FramePassBiAffineArgs) == 80
+
 # xvcgpu_fp_bi_refs_result: what SearchMotion ends with for one CU of a B picture
 FP_BI_REFS_RESULT_DTYPE = np.dtype([
     ("inter_dir", "<i4"), ("search_list", "<i4"), ("ref_idx", "<i4", (2,)),
@@ -279,6 +299,9 @@ SYMBOLS = [
     "xvcgpu_frame_pass_bi_back",
     "xvcgpu_fp_affine_boot", "xvcgpu_affine_me_listed", "xvcgpu_fp_affine_choice",
     "xvcgpu_cu_info_from_affine_choice", "xvcgpu_frame_pass_affine",
+    "xvcgpu_fp_bi_affine_boot", "xvcgpu_affine_me_listed_refs", "xvcgpu_fp_bi_affine_uni_fold",
+    "xvcgpu_fp_bi_affine_choice", "xvcgpu_cu_info_from_bi_affine_choice",
+    "xvcgpu_frame_pass_bi_refs_affine",
 ]
 
 _vp = C.c_void_p
@@ -508,6 +531,18 @@ def load_library(allow_missing=()):
                                               C.c_int, _vp],
         "xvcgpu_frame_pass_affine": [_vp, C.POINTER(FramePassArgs), C.POINTER(FramePassAffineArgs),
                                      _vp, C.c_int],
+        "xvcgpu_fp_bi_affine_boot": [_vp, C.POINTER(FramePassBiRefsArgs),
+                                     C.POINTER(FramePassBiAffineArgs)],
+        "xvcgpu_affine_me_listed_refs": [_vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp,
+                                         C.POINTER(C.c_int32), _vp],
+        "xvcgpu_fp_bi_affine_uni_fold": [_vp, C.POINTER(FramePassBiRefsArgs),
+                                         C.POINTER(FramePassBiAffineArgs)],
+        "xvcgpu_fp_bi_affine_choice": [_vp, C.POINTER(FramePassBiRefsArgs),
+                                       C.POINTER(FramePassBiAffineArgs)],
+        "xvcgpu_cu_info_from_bi_affine_choice": [_vp, C.POINTER(FramePassBiRefsArgs),
+                                                 C.POINTER(FramePassBiAffineArgs)],
+        "xvcgpu_frame_pass_bi_refs_affine": [_vp, C.POINTER(FramePassBiRefsArgs),
+                                             C.POINTER(FramePassBiAffineArgs), _vp, C.c_int],
     }
     if "xvcgpu_me_plan_destroy" not in allow_missing or hasattr(lib, "xvcgpu_me_plan_destroy"):
         lib.xvcgpu_me_plan_destroy.restype = None

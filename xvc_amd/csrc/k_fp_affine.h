@@ -37,6 +37,14 @@ __device__ __forceinline__ bool fp_affine_capable(const xvcgpu_me_block &b) {
          !(b.fullpel_mv & (XVC_ME_FULLPEL_MV | XVC_ME_USE_LIC));
 }
 
+// The exp-Golomb bits of corner 0's and corner 1's quarter-sample difference to the job's
+// predictor (SetMvd<MotionVector3> :1034-1048, GetInterPredBits :1097-1101)
+__device__ __forceinline__ uint32_t fp_affine_mvd_bits(const int32_t mvp[3][2],
+                                                       const int32_t mv[3][2]) {
+  return d_mvd_bits(mvp[0][0], mvp[0][1], mv[0][0], mv[0][1], 0) +
+         d_mvd_bits(mvp[1][0], mvp[1][1], mv[1][0], mv[1][1], 0);
+}
+
 // grid: ceil(n_listed / 256); block: 256.  n_cus bounds the indices of `order`.
 __global__ void __launch_bounds__(256)
 fp_affine_boot_kernel(const xvcgpu_me_result *res, const int32_t *order, int n_listed,
@@ -105,9 +113,7 @@ fp_affine_choice_kernel(const xvcgpu_me_block *me, const xvcgpu_me_result *res, 
     const xvcgpu_affine_me_block j = jobs[i];
     if (fp_affine_capable(b) && (j.flags & XVC_AFFINE_ME_HAS_BOOTSTRAP)) {
       const xvcgpu_affine_me_result r = ares[i];
-      const uint32_t bits = side_bits + 1 +
-                            d_mvd_bits(j.mvp[0][0], j.mvp[0][1], r.mv[0][0], r.mv[0][1], 0) +
-                            d_mvd_bits(j.mvp[1][0], j.mvp[1][1], r.mv[1][0], r.mv[1][1], 0);
+      const uint32_t bits = side_bits + 1 + fp_affine_mvd_bits(j.mvp, r.mv);
       c.cost_affine = fp_bi_cost(r.dist, bits, j.lambda16);
       c.dist_affine = r.dist;
       c.iterations = r.iterations;

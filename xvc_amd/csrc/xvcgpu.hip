@@ -35,6 +35,7 @@
 #include "k_fp_bi_back.h"
 #include "k_aqp.h"
 #include "k_fp_affine.h"
+#include "k_fp_bi_affine.h"
 #include "xvcgpu_internal.h"
 
 namespace {
@@ -3389,6 +3390,161 @@ xvcgpu_status xvcgpu_cu_info_from_choice_refs(xvcgpu_ctx *ctx,
   return XVCGPU_OK;
 }
 
+/* ---- the B frame pass with affine motion (k_fp_bi_affine.h) ---- */
+// What is wrong with the affine run's block for n CUs, or null
+static const char *fp_bi_affine_check(const xvcgpu_frame_pass_bi_affine_args *f, int n) {
+  if (!f->d_uni || !f->d_uni_results || !f->d_uni_slots)
+    return "affine: d_uni, d_uni_results and d_uni_slots";
+  if (!f->d_bi || !f->d_bi_results || !f->d_bi_slots)
+    return "affine: d_bi, d_bi_results and d_bi_slots";
+  if (!f->d_choice) return "affine: d_choice";
+  if (f->n_class[0] < 0 || f->n_class[1] < 0 || f->n_class[2] < 0 ||
+      (long long)f->n_class[0] + f->n_class[1] + f->n_class[2] > n)
+    return "affine: n_class: the d_order counts are negative or name more than n_cus CUs";
+  if (f->n_class[0] + f->n_class[1] + f->n_class[2] > 0 && !f->d_order) return "affine: d_order";
+  return nullptr;
+}
+
+// The tables and arrays of both blocks as the small kernels read them
+static xvcgpu_status fp_bi_affine_dev(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_bi_refs_args *b,
+                                      const xvcgpu_frame_pass_bi_affine_args *f, FpBiRefsDev *t,
+                                      FpBiAffineDev *d) {
+  if (!ctx || !b || !f || b->p.n_cus < 0) return XVCGPU_INVALID_ARGUMENT;
+  const char *what = nullptr;
+  if (!fp_bi_refs_tables(b, t, &what)) return fail(ctx, XVCGPU_INVALID_ARGUMENT, what);
+  what = fp_bi_affine_check(f, b->p.n_cus);
+  if (what) return fail(ctx, XVCGPU_INVALID_ARGUMENT, what);
+  d->uni = f->d_uni;
+  d->uni_res = f->d_uni_results;
+  d->uni_slots = f->d_uni_slots;
+  d->bi = f->d_bi;
+  d->bi_res = f->d_bi_results;
+  d->bi_slots = f->d_bi_slots;
+  d->choice = f->d_choice;
+  return XVCGPU_OK;
+}
+
+xvcgpu_status xvcgpu_fp_bi_affine_boot(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_bi_refs_args *b,
+                                       const xvcgpu_frame_pass_bi_affine_args *f) {
+  FpBiRefsDev t;
+  FpBiAffineDev d;
+  const xvcgpu_status st = fp_bi_affine_dev(ctx, b, f, &t, &d);
+  if (st != XVCGPU_OK) return st;
+  if (!b->p.orig) return fail(ctx, XVCGPU_INVALID_ARGUMENT, "fp_bi_affine_boot: p.orig");
+  const int listed = f->n_class[0] + f->n_class[1] + f->n_class[2];
+  if (listed == 0) return XVCGPU_OK;
+  const long long threads = (long long)listed * 2 * t.rmax;
+  hipLaunchKernelGGL(fp_bi_affine_boot_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256),
+                     0, ctx->stream, t, d, f->d_order, listed, b->p.n_cus, b->p.orig->w,
+                     b->p.orig->h);
+  CHECK_LAUNCH(ctx, "fp_bi_affine_boot");
+  return XVCGPU_OK;
+}
+
+xvcgpu_status xvcgpu_affine_me_listed_refs(xvcgpu_ctx *ctx, const xvcgpu_picture *orig,
+                                           const xvcgpu_picture *const *refs, int n_refs,
+                                           const xvcgpu_affine_me_block *d_blocks,
+                                           const uint8_t *d_slots, int n_cus, int per_cu,
+                                           const int32_t *d_order, const int32_t n_class[3],
+                                           xvcgpu_affine_me_result *d_results) {
+  if (!ctx || !orig || n_cus < 0 || !n_class || per_cu < 1 || per_cu > 2 * XVC_CS_MAX_REFS)
+    return XVCGPU_INVALID_ARGUMENT;
+  long long listed = 0;
+  for (int k = 0; k < 3; k++) {
+    if (n_class[k] < 0) return fail(ctx, XVCGPU_INVALID_ARGUMENT, "affine_me_listed_refs: n_class");
+    listed += n_class[k];
+  }
+  if (listed > n_cus)
+    return fail(ctx, XVCGPU_INVALID_ARGUMENT,
+                "affine_me_listed_refs: n_class names more CUs than n_cus");
+  if ((long long)n_cus * per_cu > 0x7fffffff) return XVCGPU_INVALID_ARGUMENT;
+  if (listed && (!d_blocks || !d_slots || !d_order || !d_results)) return XVCGPU_INVALID_ARGUMENT;
+  RefTable t;
+  const xvcgpu_status st = ref_table_of(ctx, orig, refs, n_refs, &t);
+  if (st != XVCGPU_OK) return st;
+  // one instance per CU height over its run of the list, every picture of a CU in the launch
+  int first = 0;
+#define AFF_LISTED_REFS(NW, K)                                                               \
+  if (n_class[K]) {                                                                          \
+    hipLaunchKernelGGL(affine_me_listed_refs_kernel<NW>, dim3(n_class[K] * per_cu),          \
+                       dim3(64 * NW), 0, ctx->stream, orig->v.c[0], t, d_slots, orig->bd,    \
+                       d_blocks, d_order + first, n_class[K] * per_cu, per_cu, n_cus,        \
+                       d_results);                                                           \
+    first += n_class[K];                                                                     \
+  }
+  AFF_LISTED_REFS(2, 0)
+  AFF_LISTED_REFS(4, 1)
+  AFF_LISTED_REFS(8, 2)
+#undef AFF_LISTED_REFS
+  CHECK_LAUNCH(ctx, "affine_me_listed_refs");
+  return XVCGPU_OK;
+}
+
+xvcgpu_status xvcgpu_fp_bi_affine_uni_fold(xvcgpu_ctx *ctx,
+                                           const xvcgpu_frame_pass_bi_refs_args *b,
+                                           const xvcgpu_frame_pass_bi_affine_args *f) {
+  FpBiRefsDev t;
+  FpBiAffineDev d;
+  const xvcgpu_status st = fp_bi_affine_dev(ctx, b, f, &t, &d);
+  if (st != XVCGPU_OK) return st;
+  const int n = b->p.n_cus;
+  if (n == 0) return XVCGPU_OK;
+  hipLaunchKernelGGL(fp_bi_affine_uni_fold_kernel, dim3((n + 255) / 256), dim3(256), 0,
+                     ctx->stream, t, d, n);
+  CHECK_LAUNCH(ctx, "fp_bi_affine_uni_fold");
+  return XVCGPU_OK;
+}
+
+xvcgpu_status xvcgpu_fp_bi_affine_choice(xvcgpu_ctx *ctx,
+                                         const xvcgpu_frame_pass_bi_refs_args *b,
+                                         const xvcgpu_frame_pass_bi_affine_args *f) {
+  FpBiRefsDev t;
+  FpBiAffineDev d;
+  const xvcgpu_status st = fp_bi_affine_dev(ctx, b, f, &t, &d);
+  if (st != XVCGPU_OK) return st;
+  const int n = b->p.n_cus;
+  if (n == 0) return XVCGPU_OK;
+  hipLaunchKernelGGL(fp_bi_affine_choice_kernel, dim3((n + 255) / 256), dim3(256), 0,
+                     ctx->stream, t, d, n, b->d_choice, b->d_inter);
+  CHECK_LAUNCH(ctx, "fp_bi_affine_choice");
+  return XVCGPU_OK;
+}
+
+xvcgpu_status xvcgpu_cu_info_from_bi_affine_choice(xvcgpu_ctx *ctx,
+                                                   const xvcgpu_frame_pass_bi_refs_args *b,
+                                                   const xvcgpu_frame_pass_bi_affine_args *f) {
+  if (!ctx || !b || !f || b->p.n_cus < 0) return XVCGPU_INVALID_ARGUMENT;
+  const xvcgpu_frame_pass_args *a = &b->p;
+  const int n = a->n_cus;
+  if (n && (!b->d_me[0][0] || !f->d_choice || !a->d_nnz || !a->d_cus_own))
+    return XVCGPU_INVALID_ARGUMENT;
+  if (n == 0) return XVCGPU_OK;
+  FpBiRefsPocs pocs;
+  memcpy(pocs.poc, b->ref_poc, sizeof(pocs.poc));
+  hipLaunchKernelGGL(cu_info_from_bi_affine_choice_kernel, dim3((n + 255) / 256), dim3(256), 0,
+                     ctx->stream, b->d_me[0][0], f->d_choice, a->d_nnz, a->d_luma_tx_index, n,
+                     a->qp_y, a->qp_c, pocs, a->d_cus_own);
+  CHECK_LAUNCH(ctx, "cu_info_from_bi_affine_choice");
+  return XVCGPU_OK;
+}
+
+// Launches 5-9 of the pass, behind the plain run's choice
+static xvcgpu_status fp_bi_affine_run(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_bi_refs_args *b,
+                                      const xvcgpu_frame_pass_bi_affine_args *f, int rmax) {
+  const int n = b->p.n_cus;
+  xvcgpu_status st = xvcgpu_fp_bi_affine_boot(ctx, b, f);
+  if (st == XVCGPU_OK)
+    st = xvcgpu_affine_me_listed_refs(ctx, b->p.orig, b->refs, b->n_refs, f->d_uni,
+                                      f->d_uni_slots, n, 2 * rmax, f->d_order, f->n_class,
+                                      f->d_uni_results);
+  if (st == XVCGPU_OK) st = xvcgpu_fp_bi_affine_uni_fold(ctx, b, f);
+  if (st == XVCGPU_OK)
+    st = xvcgpu_affine_me_listed_refs(ctx, b->p.orig, b->refs, b->n_refs, f->d_bi, f->d_bi_slots,
+                                      n, rmax, f->d_order, f->n_class, f->d_bi_results);
+  if (st == XVCGPU_OK) st = xvcgpu_fp_bi_affine_choice(ctx, b, f);
+  return st;
+}
+
 // q: null = one QP (xvcgpu_frame_pass_bi_refs), else xvcgpu_frame_pass_bi_refs_aqp.
 // entry: the name in front of a refusal.  back: xvcgpu_frame_pass_bi_back - the folds of
 // k_fp_bi_back.h, with the predictor-cost launch into d_l1_mvp_cost in front of them.
@@ -3398,7 +3554,8 @@ static xvcgpu_status frame_pass_bi_refs_impl(xvcgpu_ctx *ctx,
                                              int phases, const xvcgpu_aqp_args *q,
                                              const char *entry = "frame_pass_bi_refs",
                                              bool back = false,
-                                             uint32_t *d_l1_mvp_cost = nullptr) {
+                                             uint32_t *d_l1_mvp_cost = nullptr,
+                                             const xvcgpu_frame_pass_bi_affine_args *f = nullptr) {
   if (!ctx || !b || !b->p.rec) return XVCGPU_INVALID_ARGUMENT;
   // the P pass's block with list 0's first picture in the fields the shared helpers read
   xvcgpu_frame_pass_args pa = b->p;
@@ -3427,6 +3584,10 @@ static xvcgpu_status frame_pass_bi_refs_impl(xvcgpu_ctx *ctx,
       return fail(ctx, XVCGPU_INVALID_ARGUMENT, msg);
     }
     FPB_NEED(!back || d_l1_mvp_cost, "d_l1_mvp_cost");
+    if (f) {
+      const char *bad = fp_bi_affine_check(f, n);
+      FPB_NEED(!bad, bad);
+    }
     FPB_NEED(a->orig, "orig");
     for (int k = 0; k < b->n_refs; k++)
       FPB_NEED(b->refs[k] && b->refs[k]->w == a->orig->w && b->refs[k]->h == a->orig->h &&
@@ -3493,11 +3654,14 @@ static xvcgpu_status frame_pass_bi_refs_impl(xvcgpu_ctx *ctx,
                                      b->d_bi_slots, n * t.rmax, b->d_bi_results, cls);
     if (st == XVCGPU_OK)
       st = back ? xvcgpu_fp_bi_back_choice(ctx, b) : xvcgpu_fp_bi_refs_choice(ctx, b);
+    if (st == XVCGPU_OK && f && n > 0) st = fp_bi_affine_run(ctx, b, f, t.rmax);
     // (the prediction reads its `rec` for LIC jobs only: there are none)
     if (st == XVCGPU_OK)
       st = xvcgpu_inter_pred_batch(ctx, b->refs, b->n_refs, a->rec, a->pred, b->d_inter, 3 * n);
     if (st == XVCGPU_OK) st = fp_residual(ctx, a, rec, r.form);
-    if (st == XVCGPU_OK) st = xvcgpu_cu_info_from_choice_refs(ctx, b);
+    if (st == XVCGPU_OK)
+      st = f ? xvcgpu_cu_info_from_bi_affine_choice(ctx, b, f)
+             : xvcgpu_cu_info_from_choice_refs(ctx, b);
     if (st == XVCGPU_OK && q) st = xvcgpu_cu_info_set_qp(ctx, a->d_cus_own, q->d_cu_qp, n);
   }
   if (st == XVCGPU_OK) st = fp_tail(ctx, a, phases, r.fused_tail, 1);
@@ -3508,6 +3672,18 @@ xvcgpu_status xvcgpu_frame_pass_bi_refs(xvcgpu_ctx *ctx, const xvcgpu_frame_pass
                                         const xvcgpu_me_plan *const plans[2][XVC_CS_MAX_REFS],
                                         int phases) {
   return frame_pass_bi_refs_impl(ctx, b, plans, phases, nullptr);
+}
+
+xvcgpu_status xvcgpu_frame_pass_bi_refs_affine(
+    xvcgpu_ctx *ctx, const xvcgpu_frame_pass_bi_refs_args *b,
+    const xvcgpu_frame_pass_bi_affine_args *f,
+    const xvcgpu_me_plan *const plans[2][XVC_CS_MAX_REFS], int phases) {
+  if (!ctx || !f) return XVCGPU_INVALID_ARGUMENT;
+  if (!(phases & XVC_FP_ENCODE))
+    return fail(ctx, XVCGPU_INVALID_ARGUMENT,
+                "frame_pass_bi_refs_affine: phases: the second run belongs to XVC_FP_ENCODE");
+  return frame_pass_bi_refs_impl(ctx, b, plans, phases, nullptr, "frame_pass_bi_refs_affine",
+                                 false, nullptr, f);
 }
 
 xvcgpu_status xvcgpu_frame_pass_bi_refs_aqp(

@@ -567,12 +567,90 @@ class FramePassBiRefs {
       ctx_.Check(xvcgpu_frame_pass_bi_refs_aqp(ctx_.get(), &b, aqp_->args(), plans, phases));
       return;
     }
+    if (affine_entry_) {   // (named by SetAffine alone: a program without it links without it)
+      ctx_.Check(affine_entry_(ctx_.get(), &b, &affine_args_, plans, phases));
+      return;
+    }
     ctx_.Check(xvcgpu_frame_pass_bi_refs(ctx_.get(), &b, plans, phases));
+  }
+
+  // What a B pass with affine motion takes beside the plain pass's jobs, on the host
+  // (pipeline.bi_affine_jobs: the same bytes): E = 2 * Rmax jobs per CU, job [i * E + l * Rmax
+  // + r] with the CU's rectangle, lambda16 and the predictor (mvp_x, mvp_y) at every corner for
+  // r < num_ref[l], zero beyond; two slot bytes per job {slot[l][r], 255}, the first
+  // XVC_FP_BI_NO_JOB beyond the list and for a re-used list-1 picture; the indices of the
+  // capable CUs grouped by CU height 16, 32, 64 (FramePass::AffineJobs' list); the args block
+  // with the counts (its pointers null).
+  static xvcgpu_frame_pass_bi_affine_args AffineJobs(
+      const std::vector<CuRect> &rects, uint32_t lambda16, int mvp_x, int mvp_y,
+      const int num_ref[2], const int *same_poc_in_l0, const int slot[2][XVC_CS_MAX_REFS],
+      std::vector<xvcgpu_affine_me_block> *jobs, std::vector<uint8_t> *slots,
+      std::vector<int32_t> *order) {
+    xvcgpu_frame_pass_bi_affine_args f = xvcgpu_frame_pass_bi_affine_args();
+    const int rmax = num_ref[0] > num_ref[1] ? num_ref[0] : num_ref[1];
+    jobs->assign(rects.size() * 2 * rmax, xvcgpu_affine_me_block());
+    slots->assign(rects.size() * 4 * rmax, XVC_FP_BI_NO_JOB);
+    std::vector<xvcgpu_affine_me_block> one;
+    const xvcgpu_frame_pass_affine_args p =
+        FramePass::AffineJobs(rects, lambda16, mvp_x, mvp_y, 0, &one, order);
+    for (int k = 0; k < 3; k++) f.n_class[k] = p.n_class[k];
+    for (size_t i = 0; i < rects.size(); i++)
+      for (int l = 0; l < 2; l++)
+        for (int r = 0; r < num_ref[l]; r++) {
+          const size_t at = i * 2 * rmax + l * rmax + r;
+          (*jobs)[at] = one[i];
+          if (l == 0 || same_poc_in_l0[r] < 0) (*slots)[2 * at] = static_cast<uint8_t>(slot[l][r]);
+        }
+    return f;
+  }
+
+  // From now on every Run searches the CUs with both sides above 8 a second time with the
+  // three-corner affine model into every picture of both lists, refines the list that lost as
+  // SearchBiIterative does and keeps the cheaper state, the plain one on a tie
+  // (InterSearch::CompressInter, inter_search.cc:74-99; xvcgpu_frame_pass_bi_refs_affine).
+  // lambda16: the jobs' (0: the pass's QP's, as the plain jobs carry it until SetJobs); the
+  // corner predictors are zero, as the plain jobs' are.  Not together with low_delay or
+  // SetAdaptiveQp.
+  void SetAffine(uint32_t lambda16 = 0) {
+    if (low_delay_)
+      throw Error(XVCGPU_INVALID_ARGUMENT,
+                  "SetAffine: not together with low_delay (force_l1_mvd_zero)");
+    if (aqp_) throw Error(XVCGPU_INVALID_ARGUMENT, "SetAffine: not together with SetAdaptiveQp");
+    std::vector<xvcgpu_affine_me_block> jobs;
+    std::vector<uint8_t> slots;
+    std::vector<int32_t> order;
+    affine_args_ = AffineJobs(rects_, lambda16 ? lambda16 : Lambda16(qp_), 0, 0, num_ref_, same_,
+                              slot_, &jobs, &slots, &order);
+    if (order.empty()) order.push_back(0);   // (no empty device array; the counts say none)
+    const size_t n = rects_.size();
+    d_affine_uni_.reset(new DeviceArray<xvcgpu_affine_me_block>(ctx_, jobs));
+    d_affine_uni_slots_.reset(new DeviceArray<uint8_t>(ctx_, slots));
+    d_affine_order_.reset(new DeviceArray<int32_t>(ctx_, order));
+    d_affine_uni_res_.reset(new DeviceArray<xvcgpu_affine_me_result>(ctx_, jobs.size()));
+    d_affine_bi_.reset(new DeviceArray<xvcgpu_affine_me_block>(ctx_, n * rmax_));
+    d_affine_bi_res_.reset(new DeviceArray<xvcgpu_affine_me_result>(ctx_, n * rmax_));
+    d_affine_bi_slots_.reset(new DeviceArray<uint8_t>(ctx_, 2 * n * rmax_));
+    d_affine_choice_.reset(new DeviceArray<xvcgpu_fp_bi_affine_result>(ctx_, n));
+    affine_args_.d_uni = d_affine_uni_->data();
+    affine_args_.d_uni_results = d_affine_uni_res_->data();
+    affine_args_.d_uni_slots = d_affine_uni_slots_->data();
+    affine_args_.d_bi = d_affine_bi_->data();
+    affine_args_.d_bi_results = d_affine_bi_res_->data();
+    affine_args_.d_bi_slots = d_affine_bi_slots_->data();
+    affine_args_.d_order = d_affine_order_->data();
+    affine_args_.d_choice = d_affine_choice_->data();
+    affine_entry_ = &xvcgpu_frame_pass_bi_refs_affine;
+  }
+  // with SetAffine: what both runs ended with per CU
+  std::vector<xvcgpu_fp_bi_affine_result> AffineChoices() const {
+    return d_affine_choice_->ToHost();
   }
 
   // From now on every Run codes with adaptive QP (FramePass::SetAdaptiveQp; the form is
   // RESIDUAL already): xvcgpu_frame_pass_bi_refs_aqp, or xvcgpu_frame_pass_bi_back with q.
   void SetAdaptiveQp(int aqp_strength) {
+    if (affine_entry_)
+      throw Error(XVCGPU_INVALID_ARGUMENT, "SetAdaptiveQp: not together with SetAffine");
     aqp_.reset(new AdaptiveQpArrays(ctx_, w_, h_, bd_, qp_, aqp_strength, n_cus_));
   }
   std::vector<int8_t> CtuDeltaQp() const { return aqp_->CtuDeltaQp(); }
@@ -648,6 +726,7 @@ class FramePassBiRefs {
     map_stride_ = (width + 3) / 4;
     max_cu_ = max_cu;
     n_cus_ = static_cast<int>(parts.size());
+    rects_ = parts;
     std::vector<int32_t> map(static_cast<size_t>(map_stride_) * ((height + 3) / 4), -1);
     std::vector<xvcgpu_me_block> me;
     std::vector<xvcgpu_tx_block> tx;
@@ -736,6 +815,17 @@ class FramePassBiRefs {
   std::unique_ptr<DeviceArray<xvcgpu_cu_info>> d_cus_;
   std::unique_ptr<DeviceArray<uint64_t>> d_ssd_;
   std::unique_ptr<Picture> pred_;
+  // SetAffine
+  std::vector<CuRect> rects_;
+  xvcgpu_frame_pass_bi_affine_args affine_args_;
+  xvcgpu_status (*affine_entry_)(xvcgpu_ctx *, const xvcgpu_frame_pass_bi_refs_args *,
+                                 const xvcgpu_frame_pass_bi_affine_args *,
+                                 const xvcgpu_me_plan *const[2][XVC_CS_MAX_REFS], int) = nullptr;
+  std::unique_ptr<DeviceArray<xvcgpu_affine_me_block>> d_affine_uni_, d_affine_bi_;
+  std::unique_ptr<DeviceArray<xvcgpu_affine_me_result>> d_affine_uni_res_, d_affine_bi_res_;
+  std::unique_ptr<DeviceArray<uint8_t>> d_affine_uni_slots_, d_affine_bi_slots_;
+  std::unique_ptr<DeviceArray<int32_t>> d_affine_order_;
+  std::unique_ptr<DeviceArray<xvcgpu_fp_bi_affine_result>> d_affine_choice_;
 };
 
 }  // namespace xvc_gpu

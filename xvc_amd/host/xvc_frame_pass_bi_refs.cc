@@ -16,7 +16,8 @@ int RunBiRefs(xvcgpu_ctx *ctx, int width, int height, int bitdepth, int qp, int 
               bool low_delay, int aqp_strength, const int32_t *num_ref, const int32_t *pocs,
               xvcgpu_picture *orig, xvcgpu_picture *const *ref_pics, xvcgpu_picture *rec,
               const xvcgpu_me_block *blocks, int n, xvcgpu_fp_bi_refs_result *out_choice,
-              xvcgpu_cu_info *out_cus, uint64_t *out_ssd, uint32_t *out_l1_mvp_cost) {
+              xvcgpu_cu_info *out_cus, uint64_t *out_ssd, uint32_t *out_l1_mvp_cost,
+              xvcgpu_fp_bi_affine_result *out_affine = nullptr) {
   if (!ctx || !num_ref || !pocs || !orig || !ref_pics || !rec || !out_choice || !out_cus ||
       !out_ssd)
     return XVCGPU_INVALID_ARGUMENT;
@@ -32,6 +33,8 @@ int RunBiRefs(xvcgpu_ctx *ctx, int width, int height, int bitdepth, int qp, int 
     xvc_gpu::FramePassBiRefs pass(c, width, height, bitdepth, qp, lists);
     if (pass.num_cus() != n) return XVCGPU_INVALID_ARGUMENT;
     if (aqp_strength >= 0) pass.SetAdaptiveQp(aqp_strength);
+    // (affine jobs carry the plain jobs' lambda)
+    if (out_affine) pass.SetAffine(blocks && n ? blocks[0].lambda16 : 0);
     xvc_gpu::Picture o(c, orig), r(c, rec);
     // one view per handle: the lists name a re-used picture by the same object
     std::vector<std::unique_ptr<xvc_gpu::Picture>> views;
@@ -59,6 +62,10 @@ int RunBiRefs(xvcgpu_ctx *ctx, int width, int height, int bitdepth, int qp, int 
     const std::vector<xvcgpu_cu_info> cus = pass.CuInfo();
     std::memcpy(out_choice, choice.data(), choice.size() * sizeof(choice[0]));
     std::memcpy(out_cus, cus.data(), cus.size() * sizeof(cus[0]));
+    if (out_affine) {
+      const std::vector<xvcgpu_fp_bi_affine_result> both = pass.AffineChoices();
+      std::memcpy(out_affine, both.data(), both.size() * sizeof(both[0]));
+    }
     if (out_l1_mvp_cost && low_delay) {
       const std::vector<uint32_t> cost = pass.L1MvpCost();
       std::memcpy(out_l1_mvp_cost, cost.data(), cost.size() * sizeof(cost[0]));
@@ -84,6 +91,20 @@ int xvc_host_frame_pass_bi_refs(xvcgpu_ctx *ctx, int width, int height, int bitd
                                 uint64_t *out_ssd) {
   return RunBiRefs(ctx, width, height, bitdepth, qp, cur_poc, false, -1, num_ref, pocs, orig,
                    ref_pics, rec, blocks, n, out_choice, out_cus, out_ssd, nullptr);
+}
+
+// The same with SetAffine (the jobs' lambda16 is blocks[0]'s); out_affine[n].
+int xvc_host_frame_pass_bi_refs_affine(xvcgpu_ctx *ctx, int width, int height, int bitdepth,
+                                       int qp, int cur_poc, const int32_t *num_ref,
+                                       const int32_t *pocs, xvcgpu_picture *orig,
+                                       xvcgpu_picture *const *ref_pics, xvcgpu_picture *rec,
+                                       const xvcgpu_me_block *blocks, int n,
+                                       xvcgpu_fp_bi_refs_result *out_choice,
+                                       xvcgpu_cu_info *out_cus, uint64_t *out_ssd,
+                                       xvcgpu_fp_bi_affine_result *out_affine) {
+  if (!out_affine) return XVCGPU_INVALID_ARGUMENT;
+  return RunBiRefs(ctx, width, height, bitdepth, qp, cur_poc, false, -1, num_ref, pocs, orig,
+                   ref_pics, rec, blocks, n, out_choice, out_cus, out_ssd, nullptr, out_affine);
 }
 
 // The same with RefLists::low_delay = true (lists that lie wholly before cur_poc), with

@@ -230,6 +230,70 @@ def affine_order(me):
             [len(g) for g in groups])
 
 
+def bi_affine_jobs(me, same, slot, mvp=None):
+    """What a B pass with affine motion (xvcgpu_frame_pass_bi_refs_affine) takes beside the
+    plain pass's jobs me[l][r] (api.ME_DTYPE): (the uni-directional jobs [n, E]
+    api.AFFINE_ME_DTYPE, E = 2 * Rmax, job [i, l * Rmax + r] = CU i into picture r of list l -
+    x, y, w, h and lambda16 of the plain job, mvp[l][r] [n, 3, 2] or, None, the plain job's
+    mvp at every corner, flags 0 -, their slot bytes [n, E, 2] {slot[l][r], 255} with
+    FP_BI_NO_JOB first for r >= num_ref[l] and for a re-used list-1 picture, d_order,
+    n_class: affine_order(me[0][0])).  The same bytes as xvc_gpu::FramePassBiRefs::SetAffine
+    makes."""
+    num_ref = [len(me[0]), len(me[1])]
+    rmax, n = max(num_ref), len(me[0][0])
+    jobs = np.zeros((n, 2 * rmax), api.AFFINE_ME_DTYPE)
+    slots = np.full((n, 2 * rmax, 2), api.FP_BI_NO_JOB, np.uint8)
+    for l in range(2):
+        for r in range(num_ref[l]):
+            j, m = jobs[:, l * rmax + r], me[l][r]
+            for k in ("x", "y", "w", "h", "lambda16"):
+                j[k] = m[k]
+            if mvp is None:
+                j["mvp"][:, :, 0] = m["mvp_x"][:, None]
+                j["mvp"][:, :, 1] = m["mvp_y"][:, None]
+            else:
+                j["mvp"] = np.asarray(mvp[l][r], np.int32).reshape(n, 3, 2)
+            if l == 0 or same[r] < 0:
+                slots[:, l * rmax + r, 0] = slot[l][r]
+    order, n_class = affine_order(me[0][0])
+    return jobs, slots, order, n_class
+
+
+class _BiAffineArrays:
+    """What a B pass with affine motion holds beside the plain pass's state: the arrays of
+    xvcgpu_frame_pass_bi_affine_args (allocated once; every run writes the work arrays)."""
+
+    def __init__(self, ctx, n_cus, me, same, slot, mvp=None):
+        self.ctx, self.n_cus = ctx, n_cus
+        self.rmax = max(len(me[0]), len(me[1]))
+        self.jobs, self.slots, self.order, self.n_class = bi_affine_jobs(me, same, slot, mvp)
+        n, e = max(1, n_cus), 2 * self.rmax
+        self.d_uni = ctx.buffer(self.jobs) if n_cus else ctx.alloc(api.AFFINE_ME_DTYPE.itemsize)
+        self.d_uni_res = ctx.buffer(np.zeros(n * e, api.AFFINE_ME_RESULT_DTYPE))
+        self.d_uni_slots = ctx.buffer(self.slots) if n_cus else ctx.alloc(2)
+        self.d_bi = ctx.buffer(np.zeros(n * self.rmax, api.AFFINE_ME_DTYPE))
+        self.d_bi_res = ctx.buffer(np.zeros(n * self.rmax, api.AFFINE_ME_RESULT_DTYPE))
+        self.d_bi_slots = ctx.buffer(np.full(2 * n * self.rmax, api.FP_BI_NO_JOB, np.uint8))
+        self.d_order = ctx.buffer(self.order) if len(self.order) else None
+        self.d_choice = ctx.buffer(np.zeros(n, api.FP_BI_AFFINE_RESULT_DTYPE))
+
+    def args(self):
+        f = api.FramePassBiAffineArgs()
+        f.d_uni, f.d_uni_results, f.d_uni_slots = \
+            self.d_uni.ptr, self.d_uni_res.ptr, self.d_uni_slots.ptr
+        f.d_bi, f.d_bi_results, f.d_bi_slots = self.d_bi.ptr, self.d_bi_res.ptr, self.d_bi_slots.ptr
+        f.d_order = self.d_order.ptr if self.d_order is not None else None
+        f.n_class[:] = self.n_class
+        f.d_choice = self.d_choice.ptr
+        return f
+
+    def free(self):
+        for b in (self.d_uni, self.d_uni_res, self.d_uni_slots, self.d_bi, self.d_bi_res,
+                  self.d_bi_slots, self.d_order, self.d_choice):
+            if b is not None:
+                b.free()
+
+
 def cu_partition(width, height, cu=16, xcd_tiles=False):
     """List of (x, y, w, h): cu x cu CUs, smaller at right/bottom edge - in raster
     order, or (xcd_tiles) region by region of a 4 x 2 tiling of the picture, raster
@@ -847,14 +911,28 @@ class BiRefsFramePass:
     (xvcgpu_frame_pass_bi_back; every inter picture of a low-delay encode) - list 1's
     candidate per picture is the job's predictor itself, priced on the device into
     d_l1_mvp_cost (l1_mvp_cost()), list 0 is refined against it, a bi-directional CU codes
-    list 1 without a vector difference.  It accepts only such lists."""
+    list 1 without a vector difference.  It accepts only such lists.
+
+    affine=True: the pass with affine motion (xvcgpu_frame_pass_bi_refs_affine): behind the
+    plain run every CU with both sides in 16, 32, 64 is searched with the three-corner model
+    into every picture of both lists and refined as SearchBiIterative does, and keeps the
+    cheaper state (the plain one on a tie).  Not together with low_delay or aqp_strength.
+    affine_mvp: the jobs' corner predictors [l][r] -> [n_cus, 3, 2]; None: the plain job's
+    mvp at every corner.  affine_choice(), affine_uni_results(), affine_bi_results(),
+    affine_jobs(), affine_bi_jobs(): the last run's records."""
 
     def __init__(self, ctx, width, height, bitdepth=10, qp=32, cu=16, rdoq=False,
                  rdoq_packed=None, keep_levels=False, partition=None, cur_poc=8,
                  ref_pocs=((4,), (12,)), search_range=96, side_bits=(3, 3, 5),
-                 aqp_strength=None, low_delay=False):
+                 aqp_strength=None, low_delay=False, affine=False, affine_mvp=None):
         self.ctx = ctx
         self.aqp = None
+        self.affine = None
+        if affine and low_delay:
+            raise ValueError("affine: not together with low_delay (force_l1_mvd_zero): pricing "
+                             "list 1's affine predictor is a pass of its own")
+        if affine and aqp_strength is not None:
+            raise ValueError("affine: not together with aqp_strength (out of scope)")
         self.low_delay = bool(low_delay)
         self.d_l1_mvp_cost = None
         if aqp_strength is not None:    # (a refused strength: before anything is allocated)
@@ -903,6 +981,9 @@ class BiRefsFramePass:
                 for r in range(self.num_ref[l]):
                     if self.searched[l][r]:
                         self.plans[l][r] = ctx.me_plan(self.d_me[l][r].ptr, d.n_cus, d.cu_size)
+        self.affine_mvp = affine_mvp
+        if affine:
+            self.affine = _BiAffineArrays(ctx, d.n_cus, self.me, self.same, self.slot, affine_mvp)
 
     def set_jobs(self, me):
         """New search jobs me[l][r] (predictors, flags, lambda, range; the shapes stay);
@@ -914,6 +995,14 @@ class BiRefsFramePass:
                     assert all(np.array_equal(new[k], old[k]) for k in ("x", "y", "w", "h"))
                     old[...] = new
                     self.ctx.h2d(self.d_me[l][r].ptr, old)
+        if self.affine is not None and self.desc.n_cus:    # (lambda and the default mvp follow)
+            f = self.affine
+            f.jobs, f.slots, f.order, f.n_class = bi_affine_jobs(self.me, self.same, self.slot,
+                                                                 self.affine_mvp)
+            self.ctx.h2d(f.d_uni.ptr, f.jobs)
+            if f.d_order is not None:
+                f.d_order.free()
+            f.d_order = self.ctx.buffer(f.order) if len(f.order) else None
 
     def _distinct_pictures(self, refs):
         pics = [None] * len(self.distinct)
@@ -975,6 +1064,11 @@ class BiRefsFramePass:
             self.ctx._check(self.ctx.lib.xvcgpu_frame_pass_bi_refs_aqp(
                 self.ctx.h, C.byref(a), C.byref(q), self.plan_handles(planned), phases))
             return
+        if self.affine is not None:
+            f = self.affine.args()
+            self.ctx._check(self.ctx.lib.xvcgpu_frame_pass_bi_refs_affine(
+                self.ctx.h, C.byref(a), C.byref(f), self.plan_handles(planned), phases))
+            return
         self.ctx._check(self.ctx.lib.xvcgpu_frame_pass_bi_refs(
             self.ctx.h, C.byref(a), self.plan_handles(planned), phases))
 
@@ -1025,15 +1119,37 @@ class BiRefsFramePass:
             steps += [("bipred_c%d" % cls, refine(cls)) for cls in (16, 32, 64)
                       if cls <= d.cu_size]
         choice = lib.xvcgpu_fp_bi_back_choice if self.low_delay else lib.xvcgpu_fp_bi_refs_choice
+        steps.append(("choice", lambda: chk(choice(ctx.h, C.byref(a)))))
+        if self.affine is not None:
+            f, fa = self.affine, self.affine.args()
+            order = f.d_order.ptr if f.d_order is not None else None
+            n_class = (C.c_int32 * 3)(*f.n_class)
+
+            def listed(jobs, slots, per_cu, res):
+                return lambda: chk(lib.xvcgpu_affine_me_listed_refs(
+                    ctx.h, orig.h_pic, handles, len(pics), jobs.ptr, slots.ptr, n, per_cu, order,
+                    n_class, res.ptr))
+            steps += [
+                ("affine_boot", lambda: chk(lib.xvcgpu_fp_bi_affine_boot(ctx.h, C.byref(a),
+                                                                         C.byref(fa)))),
+                ("affine_uni", listed(f.d_uni, f.d_uni_slots, 2 * self.rmax, f.d_uni_res)),
+                ("affine_uni_fold", lambda: chk(lib.xvcgpu_fp_bi_affine_uni_fold(
+                    ctx.h, C.byref(a), C.byref(fa)))),
+                ("affine_bi", listed(f.d_bi, f.d_bi_slots, self.rmax, f.d_bi_res)),
+                ("affine_choice", lambda: chk(lib.xvcgpu_fp_bi_affine_choice(
+                    ctx.h, C.byref(a), C.byref(fa))))]
         steps += [
-            ("choice", lambda: chk(choice(ctx.h, C.byref(a)))),
             ("inter_pred", lambda: chk(lib.xvcgpu_inter_pred_batch(
                 ctx.h, handles, len(pics), rec.h_pic, p.pred.h_pic, self.d_inter.ptr, 3 * n)))]
         # the form's residual pipeline: the P pass's launches between its prediction and
         # its CU records
         steps += p._launches(orig, pics[0], rec, 0, fused_tail)[0][2:-1]
-        steps.append(("cu_info", lambda: chk(lib.xvcgpu_cu_info_from_choice_refs(
-            ctx.h, C.byref(a)))))
+        if self.affine is not None:
+            steps.append(("cu_info", lambda: chk(lib.xvcgpu_cu_info_from_bi_affine_choice(
+                ctx.h, C.byref(a), C.byref(fa)))))
+        else:
+            steps.append(("cu_info", lambda: chk(lib.xvcgpu_cu_info_from_choice_refs(
+                ctx.h, C.byref(a)))))
         all_cus, stride = p.d_cus.ptr, d.cu_map.shape[1]
         if fused_tail:
             return steps + [("deblock_pad_ssd", lambda: ctx.deblock_pad_ssd_dev(
@@ -1057,6 +1173,37 @@ class BiRefsFramePass:
                 self.d_bi_res.to_array(api.MERES_DTYPE, d.n_cus * self.rmax).reshape(-1, self.rmax),
                 self.d_bi_slots.to_array(np.uint8, 2 * d.n_cus * self.rmax).reshape(-1, self.rmax, 2))
 
+    def affine_choice(self):
+        """affine=True: the last run's api.FP_BI_AFFINE_RESULT_DTYPE record per CU."""
+        return self.affine.d_choice.to_array(api.FP_BI_AFFINE_RESULT_DTYPE, self.desc.n_cus)
+
+    def affine_uni_results(self):
+        """affine=True: the uni-directional affine results [n_cus, 2 * Rmax]."""
+        e = 2 * self.rmax
+        return self.affine.d_uni_res.to_array(api.AFFINE_ME_RESULT_DTYPE,
+                                              self.desc.n_cus * e).reshape(-1, e)
+
+    def affine_bi_results(self):
+        """affine=True: the refinement's affine results [n_cus, Rmax]."""
+        return self.affine.d_bi_res.to_array(api.AFFINE_ME_RESULT_DTYPE,
+                                             self.desc.n_cus * self.rmax).reshape(-1, self.rmax)
+
+    def affine_jobs(self):
+        """affine=True: the uni-directional jobs after a run [n_cus, 2 * Rmax] (flags and
+        bootstrap are the device's)."""
+        e = 2 * self.rmax
+        return self.affine.d_uni.to_array(api.AFFINE_ME_DTYPE, self.desc.n_cus * e).reshape(-1, e)
+
+    def affine_bi_jobs(self):
+        """affine=True: (the refinement jobs [n_cus, Rmax], their slot bytes [n_cus, Rmax, 2])."""
+        k = self.desc.n_cus * self.rmax
+        return (self.affine.d_bi.to_array(api.AFFINE_ME_DTYPE, k).reshape(-1, self.rmax),
+                self.affine.d_bi_slots.to_array(np.uint8, 2 * k).reshape(-1, self.rmax, 2))
+
+    def inter_jobs(self):
+        """The last run's prediction jobs [3 * n_cus]."""
+        return self.d_inter.to_array(api.INTER_DTYPE, 3 * self.desc.n_cus)
+
     def l1_mvp_cost(self):
         """low_delay: the last run's predictor cost per (CU, list-1 picture), [n_cus,
         CS_MAX_REFS] uint32 (UINT32_MAX beyond list 1's pictures)."""
@@ -1075,6 +1222,9 @@ class BiRefsFramePass:
         if self.aqp is not None:
             self.aqp.free()
             self.aqp = None
+        if self.affine is not None:
+            self.affine.free()
+            self.affine = None
         bufs = [self.d_bi_jobs, self.d_bi_res, self.d_bi_slots, self.d_choice, self.d_inter]
         if self.d_l1_mvp_cost is not None:
             bufs.append(self.d_l1_mvp_cost)
