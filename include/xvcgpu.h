@@ -623,8 +623,8 @@ xvcgpu_status xvcgpu_quant_rdo_set_prove_zero(xvcgpu_ctx *ctx, int mode);
 /* How the quantiser builds its class lists from the per-block classes (k_rdoq.h).
  * Two launches of 1024-thread workgroups: rdoq_count_kernel counts the classes of each
  * chunk of 4096 blocks, rdoq_scatter_kernel sums the chunks in front of its own and
- * writes the indices.  One launch of 256-thread workgroups: rdoq_lists_kernel, where
- * every workgroup of 1024 blocks counts the classes in front of it itself - a read
+ * writes the indices.  One launch of 128-thread workgroups: rdoq_lists_kernel, where
+ * every workgroup of 512 blocks counts the classes in front of it itself - a read
  * that grows with the square of the batch.  The lists are the same either way.
  * mode: 0 two launches, 1 one launch, -1 (default) one launch for batches of up to
  * XVCGPU_RDOQ_ONE_LAUNCH_LISTS_MAX_BLOCKS blocks: twice a 1920x1080 picture's

@@ -112,4 +112,27 @@ __device__ __forceinline__ int xcd_job_index(int block, int n) {
   return ((block >> 3) < chunk && job < n) ? job : -1;
 }
 
+// The same for kernels whose jobs come in pairs that belong together (job 2 * cu the
+// luma wave of a CU, job 2 * cu + 1 its chroma wave) and whose workgroups are W waves
+// (1, 2 or 4), one job per wave.  What xcd_job_index spreads over the XCDs is the unit
+// of max(W, 2) jobs, so a pair never straddles two XCDs: with W = 1 a unit is two
+// workgroups, 8 apart in the grid (both on XCD block % 8).  W = 4 is xcd_job_index
+// over workgroups.  Returns the first job of workgroup `block` (its wave v takes that
+// + v), -1 for a padding workgroup; n jobs in all.
+template <int W>
+struct XcdPairJobs {
+  static_assert(W == 1 || W == 2 || W == 4, "waves per workgroup");
+  static constexpr int UNIT = W > 2 ? W : 2;   // jobs per unit
+  static constexpr int WGS = UNIT / W;         // workgroups per unit
+  // workgroups to launch for n jobs (a multiple of 8)
+  __host__ __device__ static constexpr int grid(int n) {
+    return ((n + UNIT - 1) / UNIT + 7) / 8 * 8 * WGS;
+  }
+  __device__ __forceinline__ static int first_job(int block, int n) {
+    const int slot = block >> 3;
+    const int unit = xcd_job_index(((slot / WGS) << 3) | (block & 7), (n + UNIT - 1) / UNIT);
+    return unit < 0 ? -1 : unit * UNIT + (slot % WGS) * W;
+  }
+};
+
 #endif  // XVCGPU_DEV_COMMON_H_

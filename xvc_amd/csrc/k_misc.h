@@ -264,16 +264,24 @@ picture_ssd_kernel(PlaneView a, PlaneView b, int shift, int y_begin, int y_end,
   }
 }
 
-// grid: 1; block: 256.  out[0] = sum of block SSDs, out[1] = samples visited.
+// grid: 1; block: WAVES waves (1, 2 or 4).  out[0] = sum of block SSDs, out[1] = samples
+// visited.  (A 1080p picture has 510 pairs: four waves fold them in one batch of loads;
+// one or two waves place sooner but hold the chain's last link longer - the pass loses
+// 1.6 % and 1.2 %, DESIGN.md 6, "Waves per workgroup".)
+#ifndef SSD_SUM_WAVES
+#define SSD_SUM_WAVES 4
+#endif
+template <int WAVES = SSD_SUM_WAVES>
 __device__ __forceinline__ void picture_ssd_sum_kernel_body(const unsigned long long *part_in, int items, unsigned long long *out) {
-  __shared__ unsigned long long red[2][4];
+  constexpr int T = 64 * WAVES;
+  __shared__ unsigned long long red[2][WAVES];
   unsigned long long s0 = 0, s1 = 0;
   // batches of four independent loads per thread (one round trip per batch)
-  for (int base = threadIdx.x; base < items; base += 4 * 256) {
+  for (int base = threadIdx.x; base < items; base += 4 * T) {
     ulonglong2 v[4];
 #pragma unroll
     for (int u = 0; u < 4; u++) {
-      const int i = base + 256 * u;
+      const int i = base + T * u;
       v[u] = i < items ? reinterpret_cast<const ulonglong2 *>(part_in)[i]
                        : make_ulonglong2(0ull, 0ull);
     }
@@ -291,12 +299,18 @@ __device__ __forceinline__ void picture_ssd_sum_kernel_body(const unsigned long 
   }
   __syncthreads();
   if (threadIdx.x == 0) {
-    out[0] = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-    out[1] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+    unsigned long long t0 = 0, t1 = 0;
+#pragma unroll
+    for (int w = 0; w < WAVES; w++) {
+      t0 += red[0][w];
+      t1 += red[1][w];
+    }
+    out[0] = t0;
+    out[1] = t1;
   }
 }
 
-__global__ void __launch_bounds__(256)
+__global__ void __launch_bounds__(64 * SSD_SUM_WAVES)
 picture_ssd_sum_kernel(const unsigned long long *part_in, int items, unsigned long long *out) {
   picture_ssd_sum_kernel_body(part_in, items, out);
 }

@@ -20,7 +20,8 @@
 #include "k_tx2.h"
 
 // recon_from_me_kernel<false, FWD>: FWD = prediction + forward transform
-// (coefficients out), else the whole QuantFast reconstruction
+// (coefficients out), else the whole QuantFast reconstruction; workgroups of four
+// waves whatever RECON_WAVES is
 struct ReconMultiArgs {
   PicView orig, ref, rec;
   const xvcgpu_me_block *blocks;
@@ -36,10 +37,10 @@ __global__ void __launch_bounds__(256)
 recon_from_me_multi_kernel(MultiArgs<ReconMultiArgs> m, const int16_t *tx_tables,
                            const int16_t *tx_tables_t, TxTableLayout lay) {
   const ReconMultiArgs &a = m.a[blockIdx.y];
-  recon_from_me_kernel_body<false, FWD>(a.orig, a.ref, a.rec, a.blocks, a.results, a.n_cus,
-                                        a.qp_y, a.qp_c, 0, a.ref_poc, a.nnz_out, a.cus, tx_tables,
-                                        tx_tables_t, lay, nullptr, nullptr, a.coeffs, a.coeff_off,
-                                        FwdClassify());
+  recon_from_me_kernel_body<false, FWD, 4>(a.orig, a.ref, a.rec, a.blocks, a.results, a.n_cus,
+                                           a.qp_y, a.qp_c, 0, a.ref_poc, a.nnz_out, a.cus,
+                                           tx_tables, tx_tables_t, lay, nullptr, nullptr, a.coeffs,
+                                           a.coeff_off, FwdClassify());
 }
 
 // the three kernels of xvcgpu_quant_rdo_batch
@@ -133,7 +134,7 @@ deblock_tail_multi_kernel(MultiArgs<TailMultiArgs> m) {
 __global__ void __launch_bounds__(256)
 picture_ssd_sum_multi_kernel(MultiArgs<TailMultiArgs> m) {
   const TailMultiArgs &a = m.a[blockIdx.y];
-  picture_ssd_sum_kernel_body(a.part, a.tiles, a.out);
+  picture_ssd_sum_kernel_body<4>(a.part, a.tiles, a.out);
 }
 
 #endif  // XVCGPU_K_MULTI_H_

@@ -1545,14 +1545,21 @@ rdoq_scatter_kernel(int n, RdoqLists l) {
 
 // The same lists in ONE launch, for batches small enough that a redundant read of
 // the classes costs less than a second launch and the hand-over through l.part: a
-// workgroup of 256 threads owns RDOQ_LISTS_CHUNK blocks (four per thread, the
-// per-thread shape of the two kernels above) and counts the classes of all the chunks
-// in front of it itself - 1024 bytes per chunk, sixteen at a time, resident in L2
-// (1080p: 24 workgroups, the last one reads 23 KB).  That read grows with the
-// square of n: the caller keeps the two launches above for large batches.  Four
-// waves place beside other streams' kernels where sixteen have to wait for a CU
-// with four free slots on every SIMD.  grid: ceil(n / RDOQ_LISTS_CHUNK); block: 256.
-#define RDOQ_LISTS_CHUNK 1024
+// workgroup owns RDOQ_LISTS_CHUNK blocks (four per thread, the per-thread shape of the
+// two kernels above) and counts the classes of all the chunks in front of it itself - a
+// byte per block, sixteen at a time, resident in L2.  That read grows with the square of
+// n: the caller keeps the two launches above for large batches.  Small workgroups place
+// beside other streams' kernels where sixteen waves have to wait for a CU with four free
+// slots on every SIMD.  RDOQ_LISTS_WAVES (1, 2 or 4) sets the workgroup.  Measured with
+// three picture chains in flight ("Waves per workgroup"): two waves (chunks
+// of 512 blocks; 1080p: 48 workgroups, the last one reads 24 KB, 0.6 MB in all) gain
+// 1.8 % of the pass over four; one wave (96 workgroups, 1.2 MB, the last one's read 24
+// trips long) gains nothing.  grid: ceil(n / RDOQ_LISTS_CHUNK); block: RDOQ_LISTS_THREADS.
+#ifndef RDOQ_LISTS_WAVES
+#define RDOQ_LISTS_WAVES 2
+#endif
+#define RDOQ_LISTS_THREADS (64 * RDOQ_LISTS_WAVES)
+#define RDOQ_LISTS_CHUNK (4 * RDOQ_LISTS_THREADS)
 
 // the bytes of v that equal c (0..127), exactly: no carry crosses a byte
 __device__ __forceinline__ int rq_bytes_equal(uint32_t v, uint32_t c) {
@@ -1560,10 +1567,11 @@ __device__ __forceinline__ int rq_bytes_equal(uint32_t v, uint32_t c) {
   return __popc(~(((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x | 0x7f7f7f7fu));
 }
 
-__global__ void __launch_bounds__(256)
+__global__ void __launch_bounds__(RDOQ_LISTS_THREADS)
 rdoq_lists_kernel(int n, RdoqLists l) {
-  __shared__ int wsum[3][4];    // the prefix read's wave sums
-  __shared__ int wtot[3][4];    // the chunk's own wave totals
+  constexpr int WAVES = RDOQ_LISTS_WAVES;
+  __shared__ int wsum[3][WAVES];    // the prefix read's wave sums
+  __shared__ int wtot[3][WAVES];    // the chunk's own wave totals
   const int t = threadIdx.x, b = blockIdx.x, wv = t >> 6;
   const uint32_t *cw = reinterpret_cast<const uint32_t *>(l.cls);
   // the chunks in front of this one: 64 * b 16-byte words of classes, all of them
@@ -1573,7 +1581,7 @@ rdoq_lists_kernel(int n, RdoqLists l) {
   {
     const uint4 *q = reinterpret_cast<const uint4 *>(cw);
     const int quads = (RDOQ_LISTS_CHUNK / 16) * b;
-    for (int j = t; j < quads; j += 256) {
+    for (int j = t; j < quads; j += RDOQ_LISTS_THREADS) {
       const uint4 u = q[j];
       const uint32_t a[4] = {u.x, u.y, u.z, u.w};
 #pragma unroll
@@ -1604,14 +1612,15 @@ rdoq_lists_kernel(int n, RdoqLists l) {
   int pos[3];
 #pragma unroll
   for (int k = 0; k < 3; k++) {
-    const int base = wsum[k][0] + wsum[k][1] + wsum[k][2] + wsum[k][3];
-    int before = 0;
+    int base = 0, before = 0;
 #pragma unroll
-    for (int w = 0; w < 3; w++) before += w < wv ? wtot[k][w] : 0;
+    for (int w = 0; w < WAVES; w++) base += wsum[k][w];
+#pragma unroll
+    for (int w = 0; w < WAVES - 1; w++) before += w < wv ? wtot[k][w] : 0;
     pos[k] = base + before + inc[k] - cnt[k];
   }
   if (i < n) rq_scatter_word(mine, i, n, l, pos);
-  if (b == (int)gridDim.x - 1 && t == 255)
+  if (b == (int)gridDim.x - 1 && t == RDOQ_LISTS_THREADS - 1)
     for (int k = 0; k < 3; k++) l.count[k] = pos[k];   // base + the chunk's total
 }
 

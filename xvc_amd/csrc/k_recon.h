@@ -122,7 +122,19 @@ __device__ __forceinline__ void wave_interp_block_lds(int bd, int w_in, int h_in
   }
 }
 
-// grid: XCD-swizzled workgroups of 4 waves; two waves per CU: one for the luma
+// Waves per workgroup of recon_from_me_kernel (all three instances): 1, 2 or 4.  The
+// waves of a workgroup share nothing - a job is one wave's - so the figure only decides
+// how the jobs are handed to the CUs: a workgroup starts when one CU has a free slot for
+// each of its waves and its whole LDS at once, and gives that LDS back when its slowest
+// wave ends.  Measured with three picture chains in flight ("Waves per
+// workgroup"): at 1 the forward launch is in flight 54 us instead of 66, but the walk and
+// the tail beside it wait that much longer and the pass as a whole loses 3.6 %; at 2 it
+// loses 1.3 %.
+#ifndef RECON_WAVES
+#define RECON_WAVES 4
+#endif
+
+// grid: XCD-swizzled workgroups of WAVES waves (XcdPairJobs); two waves per CU: one for the luma
 // block, one for the U and V blocks side by side (32 lanes each: a chroma
 // block of a CU up to 16x16 has at most 64 samples, which would leave three
 // quarters of a wave of its own idle through the whole pipeline).
@@ -131,32 +143,31 @@ __device__ __forceinline__ void wave_interp_block_lds(int bd, int w_in, int h_in
 // which then plays TransformEncoder's prediction buffer) and forward transform,
 // coefficients to coeffs + coeff_off[3 * cu + comp]: what precedes a quantiser
 // that runs as its own kernel (xvcgpu_quant_rdo_batch).
-template <bool RDOQ, bool FWD>
+template <bool RDOQ, bool FWD, int WAVES = RECON_WAVES>
 __device__ __forceinline__ void recon_from_me_kernel_body(PicView orig, PicView ref, PicView rec, const xvcgpu_me_block *blocks, const xvcgpu_me_result *results, int n_cus, int qp_y, int qp_c, int intra_pic, int ref_poc, int32_t *nnz_out, xvcgpu_cu_info *cus, const int16_t *tx_tables, const int16_t *tx_tables_t, TxTableLayout lay, const xvcgpu_rdoq_contexts *rq_ctx, const xvcgpu_rdoq_params *rq_prm, int16_t *coeffs, const uint32_t *coeff_off, FwdClassify fc) {
   constexpr int TXM = FWD ? TX_MODE_FWD : TX_MODE_FULL;
-  __shared__ ReconShared s_all[4];
+  __shared__ ReconShared s_all[WAVES];
   // one scratch per wave; a chroma wave splits it between its two halves
   // per wave: one 16x16 luma block, or two 8x8 chroma blocks side by side
   union RqWave {
     RdoqShared<256> one;
     RdoqShared<64> two[2];
   };
-  __shared__ RqWave rq_all[RDOQ ? 4 : 1];
+  __shared__ RqWave rq_all[RDOQ ? WAVES : 1];
   RdoqShared<256> *rq_wave = &rq_all[RDOQ ? (threadIdx.x >> 6) : 0].one;
   ReconShared &s = s_all[threadIdx.x >> 6];
   // the forward half's classification can prove blocks all zero on the spot: a
   // scratch per wave for it
   FwdClassify fcl = fc;
   if constexpr (FWD) {
-    __shared__ RqProveLds pv_all[4];
+    __shared__ RqProveLds pv_all[WAVES];
     fcl.pv = (fc.cls && fc.rq_ctx && fc.rq_prm) ? &pv_all[threadIdx.x >> 6] : nullptr;
     if (fcl.pv && (threadIdx.x & 63) == 0) fcl.pv->staged_ctx = -1;
   }
   const int n = n_cus * 2;
-  const int n_wg = (n + 3) / 4;
-  const int wg = xcd_job_index(blockIdx.x, n_wg);
-  if (wg < 0) return;
-  const int job = __builtin_amdgcn_readfirstlane(wg * 4 + (int)(threadIdx.x >> 6));  // wave-uniform
+  const int job0 = XcdPairJobs<WAVES>::first_job(blockIdx.x, n);
+  if (job0 < 0) return;
+  const int job = __builtin_amdgcn_readfirstlane(job0 + (int)(threadIdx.x >> 6));  // wave-uniform
   if (job >= n) return;
   const int ci = job >> 1;
   const bool chroma = (job & 1) != 0;
@@ -309,8 +320,8 @@ __device__ __forceinline__ void recon_from_me_kernel_body(PicView orig, PicView 
   else ljob(std::false_type());
 }
 
-// Waves per SIMD the forward-only instance is compiled for (LDS allows 7: 22 KB per workgroup
-// of four waves).  At 7 (72 registers) the build spills 5 dwords, all inside the any-size chroma
+// Waves per SIMD the forward-only instance is compiled for (LDS allows 7: 5.4 KB per wave, 22 KB
+// per workgroup of four).  At 7 (72 registers) the build spills 5 dwords, all inside the any-size chroma
 // path; the 16x16 CU's luma and chroma instances touch no scratch.  Before the shape was
 // settled once at the top of the job (one exact and one any-size instance of everything behind
 // it) the figures were - registers / spilled dwords - 5: 93 / 0, 6: 80 / 68, 7: 72 / 104, the
@@ -322,7 +333,7 @@ __device__ __forceinline__ void recon_from_me_kernel_body(PicView orig, PicView 
 #define RECON_FWD_MIN_WAVES 7
 #endif
 template <bool RDOQ = false, bool FWD = false>
-__global__ void __launch_bounds__(256, FWD && !RDOQ ? RECON_FWD_MIN_WAVES : 1)
+__global__ void __launch_bounds__(64 * RECON_WAVES, FWD && !RDOQ ? RECON_FWD_MIN_WAVES : 1)
 recon_from_me_kernel(PicView orig, PicView ref, PicView rec, const xvcgpu_me_block *blocks, const xvcgpu_me_result *results, int n_cus, int qp_y, int qp_c, int intra_pic, int ref_poc, int32_t *nnz_out, xvcgpu_cu_info *cus, const int16_t *tx_tables, const int16_t *tx_tables_t, TxTableLayout lay, const xvcgpu_rdoq_contexts *rq_ctx = nullptr, const xvcgpu_rdoq_params *rq_prm = nullptr, int16_t *coeffs = nullptr, const uint32_t *coeff_off = nullptr, FwdClassify fc = FwdClassify()) {
   recon_from_me_kernel_body<RDOQ, FWD>(orig, ref, rec, blocks, results, n_cus, qp_y, qp_c, intra_pic, ref_poc, nnz_out, cus, tx_tables, tx_tables_t, lay, rq_ctx, rq_prm, coeffs, coeff_off, fc);
 }

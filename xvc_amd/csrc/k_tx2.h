@@ -474,16 +474,20 @@ __device__ __forceinline__ void residual_wave_kernel_body(PicView orig, PicView 
 // block is 24 480 waves for a 1080p picture, two thirds of them for 8x8 blocks
 // that leave three quarters of their wave idle; a wave whose blocks carry no
 // level retires after a look at their counts.  grid: XCD-swizzled workgroups of
-// TX2_WAVES waves over 2 * n_cus jobs.
-__global__ void __launch_bounds__(64 * TX2_WAVES)
+// INV_PAIRS_WAVES waves (1, 2 or 4) over 2 * n_cus jobs (XcdPairJobs); the waves of a
+// workgroup share nothing (RECON_WAVES, k_recon.h: measured the same way - at 1 the pass
+// loses 0.8 %, at 2 nothing moves).
+#ifndef INV_PAIRS_WAVES
+#define INV_PAIRS_WAVES 4
+#endif
+__global__ void __launch_bounds__(64 * INV_PAIRS_WAVES)
 inv_cu_pairs_kernel(PicView rec, const xvcgpu_tx_block *blocks, int n_cus, int16_t *levels,
                     const uint32_t *level_off, int32_t *nnz_out, const int16_t *tx_tables,
                     const int16_t *tx_tables_t, TxTableLayout lay) {
   const int n = 2 * n_cus;
-  const int n_wg = (n + TX2_WAVES - 1) / TX2_WAVES;
-  const int wg = xcd_job_index(blockIdx.x, n_wg);
-  if (wg < 0) return;
-  const int job = __builtin_amdgcn_readfirstlane(wg * TX2_WAVES + (int)(threadIdx.x >> 6));
+  const int job0 = XcdPairJobs<INV_PAIRS_WAVES>::first_job(blockIdx.x, n);
+  if (job0 < 0) return;
+  const int job = __builtin_amdgcn_readfirstlane(job0 + (int)(threadIdx.x >> 6));
   if (job >= n) return;
   const int ci = job >> 1;
   // the counts before anything else: in place, a block without a level is already what it
@@ -493,7 +497,7 @@ inv_cu_pairs_kernel(PicView rec, const xvcgpu_tx_block *blocks, int n_cus, int16
   } else {
     if (nnz_out[3 * ci + 1] == 0 && nnz_out[3 * ci + 2] == 0) return;
   }
-  __shared__ Tx2Shared s_all[TX2_WAVES];
+  __shared__ Tx2Shared s_all[INV_PAIRS_WAVES];
   Tx2Shared &s = s_all[threadIdx.x >> 6];
   if (!(job & 1)) {
     const int bi = 3 * ci;

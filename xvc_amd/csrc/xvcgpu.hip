@@ -1362,8 +1362,8 @@ xvcgpu_status xvcgpu_recon_from_me(xvcgpu_ctx *ctx, const xvcgpu_picture *orig,
   if (orig->w != ref->w || orig->h != ref->h || rec->w != ref->w || rec->h != ref->h)
     return fail(ctx, XVCGPU_INVALID_ARGUMENT, "picture mismatch");
   if (n == 0) return XVCGPU_OK;
-  const int n_wg = (2 * n + 3) / 4;
-  hipLaunchKernelGGL(recon_from_me_kernel<false>, dim3((n_wg + 7) / 8 * 8), dim3(256), 0,
+  hipLaunchKernelGGL(recon_from_me_kernel<false>, dim3(XcdPairJobs<RECON_WAVES>::grid(2 * n)),
+                     dim3(64 * RECON_WAVES), 0,
                      ctx->stream, orig->v, ref->v, rec->v, d_blocks, d_results, n, qp_y,
                      qp_c, intra_pic, ref_poc, d_nnz, d_cus, ctx->d_tx_tables,
                      ctx->d_tx_tables_t, xvcgpu_tx_layout(), nullptr, nullptr);
@@ -1382,8 +1382,8 @@ xvcgpu_status xvcgpu_fwd_from_me(xvcgpu_ctx *ctx, const xvcgpu_picture *orig,
   if (orig->w != ref->w || orig->h != ref->h || pred->w != ref->w || pred->h != ref->h)
     return fail(ctx, XVCGPU_INVALID_ARGUMENT, "picture mismatch");
   if (n == 0) return XVCGPU_OK;
-  const int n_wg = (2 * n + 3) / 4;
-  hipLaunchKernelGGL((recon_from_me_kernel<false, true>), dim3((n_wg + 7) / 8 * 8), dim3(256), 0,
+  hipLaunchKernelGGL((recon_from_me_kernel<false, true>), dim3(XcdPairJobs<RECON_WAVES>::grid(2 * n)),
+                     dim3(64 * RECON_WAVES), 0,
                      ctx->stream, orig->v, ref->v, pred->v, d_blocks, d_results, n, 0, 0, 0, 0,
                      nullptr, nullptr, ctx->d_tx_tables, ctx->d_tx_tables_t, xvcgpu_tx_layout(),
                      nullptr, nullptr, d_coeffs, d_coeff_offsets);
@@ -1405,8 +1405,8 @@ xvcgpu_status xvcgpu_recon_from_me_rdoq(xvcgpu_ctx *ctx, const xvcgpu_picture *o
   if (orig->w != ref->w || orig->h != ref->h || rec->w != ref->w || rec->h != ref->h)
     return fail(ctx, XVCGPU_INVALID_ARGUMENT, "picture mismatch");
   if (n == 0) return XVCGPU_OK;
-  const int n_wg = (2 * n + 3) / 4;
-  hipLaunchKernelGGL(recon_from_me_kernel<true>, dim3((n_wg + 7) / 8 * 8), dim3(256), 0,
+  hipLaunchKernelGGL(recon_from_me_kernel<true>, dim3(XcdPairJobs<RECON_WAVES>::grid(2 * n)),
+                     dim3(64 * RECON_WAVES), 0,
                      ctx->stream, orig->v, ref->v, rec->v, d_blocks, d_results, n, qp_y,
                      qp_c, tx_flags | XVC_TXF_RDOQ, ref_poc, d_nnz, d_cus, ctx->d_tx_tables,
                      ctx->d_tx_tables_t, xvcgpu_tx_layout(), d_contexts, d_params);
@@ -1581,7 +1581,7 @@ static xvcgpu_status quant_rdo_launch(xvcgpu_ctx *ctx, int bitdepth,
   if (ctx->rdoq_list_form > 0 ||
       (ctx->rdoq_list_form < 0 && n <= XVCGPU_RDOQ_ONE_LAUNCH_LISTS_MAX_BLOCKS)) {
     hipLaunchKernelGGL(rdoq_lists_kernel, dim3((n + RDOQ_LISTS_CHUNK - 1) / RDOQ_LISTS_CHUNK),
-                       dim3(256), 0, ctx->stream, n, l);
+                       dim3(RDOQ_LISTS_THREADS), 0, ctx->stream, n, l);
   } else {
     const int chunks = (n + RDOQ_CHUNK - 1) / RDOQ_CHUNK;
     hipLaunchKernelGGL(rdoq_count_kernel, dim3(chunks), dim3(1024), 0, ctx->stream, n, l);
@@ -1668,8 +1668,8 @@ xvcgpu_status xvcgpu_fwd_from_me_classify_prove(
   fc.rq_prm = prove ? d_params : nullptr;
   fc.pv = nullptr;
   ctx->rdoq_classified_proved = prove;
-  const int n_wg = (2 * n + 3) / 4;
-  hipLaunchKernelGGL((recon_from_me_kernel<false, true>), dim3((n_wg + 7) / 8 * 8), dim3(256), 0,
+  hipLaunchKernelGGL((recon_from_me_kernel<false, true>), dim3(XcdPairJobs<RECON_WAVES>::grid(2 * n)),
+                     dim3(64 * RECON_WAVES), 0,
                      ctx->stream, orig->v, ref->v, pred->v, d_blocks, d_results, n, qp_y, qp_c, 0,
                      ref_poc, nullptr, d_cus, ctx->d_tx_tables, ctx->d_tx_tables_t,
                      xvcgpu_tx_layout(), nullptr, nullptr, d_coeffs, d_coeff_offsets, fc);
@@ -1720,11 +1720,11 @@ xvcgpu_status xvcgpu_inv_transform_cu_order(xvcgpu_ctx *ctx, xvcgpu_picture *rec
       (n_cus && (!d_blocks || !d_levels || !d_level_offsets || !d_nnz)))
     return XVCGPU_INVALID_ARGUMENT;
   if (n_cus == 0) return XVCGPU_OK;
-  const int n_wg = (2 * n_cus + TX2_WAVES - 1) / TX2_WAVES;
-  hipLaunchKernelGGL(inv_cu_pairs_kernel, dim3((n_wg + 7) / 8 * 8), dim3(64 * TX2_WAVES), 0,
-                     ctx->stream, rec->v, d_blocks, n_cus, const_cast<int16_t *>(d_levels),
-                     d_level_offsets, const_cast<int32_t *>(d_nnz), ctx->d_tx_tables,
-                     ctx->d_tx_tables_t, xvcgpu_tx_layout());
+  hipLaunchKernelGGL(inv_cu_pairs_kernel, dim3(XcdPairJobs<INV_PAIRS_WAVES>::grid(2 * n_cus)),
+                     dim3(64 * INV_PAIRS_WAVES), 0, ctx->stream, rec->v, d_blocks, n_cus,
+                     const_cast<int16_t *>(d_levels), d_level_offsets,
+                     const_cast<int32_t *>(d_nnz), ctx->d_tx_tables, ctx->d_tx_tables_t,
+                     xvcgpu_tx_layout());
   CHECK_LAUNCH(ctx, "inv_transform_cu_order");
   return XVCGPU_OK;
 }
@@ -1881,7 +1881,7 @@ xvcgpu_status xvcgpu_picture_ssd_rows(xvcgpu_ctx *ctx, const xvcgpu_picture *a,
   if (items > 0)
     hipLaunchKernelGGL(picture_ssd_kernel, dim3(items), dim3(256), 0, ctx->stream, pa,
                        pb, 2 * (shift_bitdepth - 8), y_begin, y_end, ctx->d_ssd_part);
-  hipLaunchKernelGGL(picture_ssd_sum_kernel, dim3(1), dim3(256), 0, ctx->stream,
+  hipLaunchKernelGGL(picture_ssd_sum_kernel, dim3(1), dim3(64 * SSD_SUM_WAVES), 0, ctx->stream,
                      ctx->d_ssd_part, items,
                      reinterpret_cast<unsigned long long *>(d_out));
   CHECK_LAUNCH(ctx, "picture_ssd");
@@ -1933,8 +1933,8 @@ xvcgpu_status xvcgpu_deblock_pad_ssd(xvcgpu_ctx *ctx, const xvcgpu_picture *src,
   if (orig) {
     hipLaunchKernelGGL(deblock_tail_kernel<true>, dim3((tiles + 7) / 8 * 8), dim3(256), 0, ctx->stream, d,
                        src->v, dst->v, orig->v.c[0], 2 * (shift_bitdepth - 8), part);
-    hipLaunchKernelGGL(picture_ssd_sum_kernel, dim3(1), dim3(256), 0, ctx->stream, part, tiles,
-                       reinterpret_cast<unsigned long long *>(d_ssd));
+    hipLaunchKernelGGL(picture_ssd_sum_kernel, dim3(1), dim3(64 * SSD_SUM_WAVES), 0, ctx->stream,
+                       part, tiles, reinterpret_cast<unsigned long long *>(d_ssd));
   } else {
     hipLaunchKernelGGL(deblock_tail_kernel<false>, dim3((tiles + 7) / 8 * 8), dim3(256), 0, ctx->stream, d,
                        src->v, dst->v, dst->v.c[0], 0, part);
