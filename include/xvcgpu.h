@@ -1489,6 +1489,76 @@ xvcgpu_status xvcgpu_frame_pass_affine(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_
                                        const xvcgpu_frame_pass_affine_args *f,
                                        const xvcgpu_me_plan *plan, int phases);
 
+/* ---- the P frame pass with merge mode --------------------------------------------- *
+ * CuEncoder::CompressInterPic runs CompressMerge before CompressInter (cu_encoder.cc:
+ * 469-481): the CU takes one of five candidate motions and codes no vector difference; a
+ * merge CU that keeps no level is a skip CU.  The pass puts a merge stage between the search
+ * and the rest of the flat pass: launches that exist and three small ones (k_fp_merge.h);
+ * nothing is read back.  xvcgpu_types.h: xvcgpu_fp_merge_cand, xvcgpu_fp_merge_ranking,
+ * xvcgpu_fp_merge_result, xvcgpu_frame_pass_merge_args.  One list, one reference picture.
+ *
+ * Inputs per CU: XVC_FP_MERGE_CANDS = 5 candidates (constants::kNumInterMergeCandidates) in
+ * merge-index order, m->d_cands[5 i + m]; vectors in 1/16 pel, unclipped; an input, as a
+ * job's mvp is (no GetMergeCandidates derivation).  A candidate is valid only with ref_idx =
+ * {0, -1}.
+ *
+ * xvcgpu_fp_merge_rank: InterSearch::SearchMergeCandidates (inter_search.cc:165-197).  One
+ * wave per listed CU (m->d_order[0 .. n_listed), strictly ascending; NULL: the CUs 0 ..
+ * n_listed - 1), two waves a workgroup; the CU's geometry is its plain job's.  dist[m] is the
+ * SATD (XVC_METRIC_SATD) of the original luma block against the luma prediction at
+ * ClipMv(mv[m]).  cost[m] = (double)dist[m] + (double)bits(m) * lambda_sqrt, bits(m) = m + 1 -
+ * (m == 4), without contraction (-ffp-contract=off).  std::stable_sort is an insertion sort
+ * that moves only on strictly smaller.  num = 4, lowered to k for every k = 4 .. 0 with
+ * cost[k] > cost[0] * 1.25.  An invalid candidate, or a CU shape outside w, h in {4, 8, 16,
+ * 32, 64}, gets dist = UINT32_MAX and ranks behind every real one.  Writes m->d_rank[i] of
+ * the listed CUs: dist[5] by merge index, cost[5] sorted, order[5], num; records outside the
+ * list are not touched.
+ * xvcgpu_fp_merge_choice: one thread per CU.  The pass's own rule in the closed-form bits
+ * every frame pass here uses - NOT the reference's RD comparison, which needs the entropy
+ * coder.  m0 = order[0]; cost_merge = dist[m0] + (((merge_side_bits + bits(m0)) * lambda16)
+ * >> 16); cost_plain = subpel_dist + (((side_bits + 1 + GetMvdBits(mvp, mv, fullpel ? 2 : 0))
+ * * lambda16) >> 16) as xvcgpu_fp_affine_choice forms it; both with the plain job's lambda16,
+ * a 64-bit product, kept in 32 bits.  Merge where cost_merge <= cost_plain: the reference
+ * evaluates merge first and a later mode replaces it only on strict < (save_if_best_cost,
+ * cu_encoder.cc:449-481).  use_merge = 0, cost_merge = UINT32_MAX, merge_idx = -1 where
+ * dist[m0] == UINT32_MAX, where the plain job carries XVC_ME_USE_LIC and where the list does
+ * not name the CU.  Writes m->d_choice[i] (skip = 0) and m->d_chosen[i]: a copy of
+ * d_results[i], and where merge won mv_x, mv_y the candidate's unclipped vector and
+ * subpel_dist = dist[m0].  A plain search answered with XVCGPU_ME_UNSUPPORTED: the record all
+ * ones, the chosen result the unsupported record unchanged.
+ * xvcgpu_fp_merge_skip: one thread per CU.  d_choice[i].skip = use_merge && no transform block
+ * of the CU has a level (SetSkipFlag(!GetHasAnyCbf()), cu_encoder.cc:639): d_nnz[t], [t + 1],
+ * [t + 2] (Y, U, V) with t = d_luma_tx_index[i], NULL: t = 3 i.  The layouts: the forms with a
+ * prediction picture (FWD_TRANSFORM, RESIDUAL, RESIDUAL_RDOQ) keep a CU's counts at
+ * d_luma_tx_index[i] + 0, 1, 2 (FrameDescriptors); RECON_FROM_ME and FWD_FROM_ME at 3 i + comp
+ * (their kernels index the blocks 3 * cu + comp).  An all-ones record is left alone; nothing
+ * but `skip` is written.  The forced-skip evaluation (CompressSkipOnly as an RD alternative)
+ * is not part of the pass.
+ *
+ * xvcgpu_frame_pass_merge: the search (plan NULL: sized; else planned) -> rank -> choice ->
+ * the launches of a->form behind the search exactly as xvcgpu_frame_pass runs them, on a copy
+ * of the block whose d_results is m->d_chosen (everything behind the search reads d_me and
+ * the results' mv_x / mv_y only; the prediction clips the vector, the CU records keep it
+ * unclipped) -> skip -> the tail exactly as xvcgpu_frame_pass runs it, fused or separate.
+ * All five forms.  a->d_results keeps the search's answer.  Every check - the flat pass's
+ * included - happens before the first launch (XVCGPU_INVALID_ARGUMENT, the message names the
+ * field): a missing array, n_listed outside [0, n_cus], part of a picture, phases without
+ * XVC_FP_ENCODE, lambda_sqrt not finite or below 0.  After them the call only enqueues: no
+ * synchronisation, no allocation.  With n_listed = 0 the pass gives xvcgpu_frame_pass's
+ * bytes. */
+xvcgpu_status xvcgpu_fp_merge_rank(xvcgpu_ctx *ctx, const xvcgpu_picture *orig,
+                                   const xvcgpu_picture *ref, const xvcgpu_me_block *d_me,
+                                   int n_cus, const xvcgpu_frame_pass_merge_args *m);
+xvcgpu_status xvcgpu_fp_merge_choice(xvcgpu_ctx *ctx, const xvcgpu_me_block *d_me,
+                                     const xvcgpu_me_result *d_results, int n_cus,
+                                     const xvcgpu_frame_pass_merge_args *m);
+xvcgpu_status xvcgpu_fp_merge_skip(xvcgpu_ctx *ctx, const int32_t *d_nnz,
+                                   const int32_t *d_luma_tx_index, int n_cus,
+                                   xvcgpu_fp_merge_result *d_choice);
+xvcgpu_status xvcgpu_frame_pass_merge(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_args *a,
+                                      const xvcgpu_frame_pass_merge_args *m,
+                                      const xvcgpu_me_plan *plan, int phases);
+
 /* ---- the B frame pass with affine motion ---------------------------------------- *
  * CompressInter's second SearchMotion run (three-corner model, both lists, the
  * SearchBiIterative step on affine vectors) behind the plain run of

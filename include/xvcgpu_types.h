@@ -780,6 +780,72 @@ typedef struct xvcgpu_frame_pass_affine_args {
   xvcgpu_inter_block *d_inter;               /* 3 * n_cus: the prediction jobs Y, U, V   */
 } xvcgpu_frame_pass_affine_args;
 
+/* ---- the P frame pass with merge mode (xvcgpu_frame_pass_merge) -------------------- *
+ * CuEncoder::CompressInterPic tries CompressMerge before CompressInter (cu_encoder.cc:
+ * 469-481): the CU takes one of XVC_FP_MERGE_CANDS candidate motions and codes no vector
+ * difference; a merge CU that keeps no level is a skip CU (SetSkipFlag(!GetHasAnyCbf()),
+ * :639).
+ * One candidate, in merge-index order five per CU.  Vectors in 1/16 pel, unclipped.  The
+ * candidates are an input, as a job's mvp is: there is no GetMergeCandidates derivation.
+ * Laid out for two lists; the P pass takes a candidate as valid only with ref_idx =
+ * {0, -1} and reads mv[0]. */
+#define XVC_FP_MERGE_CANDS 5   /* constants::kNumInterMergeCandidates */
+typedef struct xvcgpu_fp_merge_cand {
+  int8_t ref_idx[2];   /* per list; -1: list unused                                       */
+  uint8_t reserved[2];
+  int32_t mv[2][2];    /* [list][x, y]                                                    */
+} xvcgpu_fp_merge_cand;
+
+/* InterSearch::SearchMergeCandidates (inter_search.cc:165-197) for one CU.  dist[m]: the
+ * SATD of the original luma block against the luma prediction at ClipMv(mv[m]); UINT32_MAX
+ * for a candidate that is not valid and for a CU shape outside w, h in {4, 8, 16, 32, 64}.
+ * cost: (double)dist[m] + (double)bits(m) * lambda_sqrt, bits(m) = m + 1 - (m == 4), sorted
+ * by std::stable_sort (equal costs keep their merge-index order); order[k]: the merge index
+ * behind cost[k]; num: 4, lowered to k for every k = 4 .. 0 with cost[k] > cost[0] * 1.25. */
+typedef struct xvcgpu_fp_merge_ranking {
+  uint32_t dist[XVC_FP_MERGE_CANDS];   /* by merge index                                  */
+  int32_t order[XVC_FP_MERGE_CANDS];
+  int32_t num;
+  uint32_t reserved;
+  double cost[XVC_FP_MERGE_CANDS];     /* sorted                                          */
+} xvcgpu_fp_merge_ranking;
+
+/* What the pass ends with for one CU, and what shows why.  A CU that does not merge -
+ * dist[order[0]] == UINT32_MAX, a plain job with XVC_ME_USE_LIC, a CU the list does not
+ * name -: use_merge 0, merge_idx -1, cost_merge UINT32_MAX, num 0, the plain vector.  A CU
+ * whose plain search has no kernel instance (XVCGPU_ME_UNSUPPORTED): every byte 0xff. */
+typedef struct xvcgpu_fp_merge_result {
+  int32_t use_merge;
+  int32_t merge_idx;    /* order[0] of the ranking where merge won; else -1               */
+  int32_t skip;         /* use_merge and no transform block of the CU has a level
+                         * (xvcgpu_fp_merge_skip; the choice writes 0)                    */
+  int32_t num;          /* the ranking's num; 0 where the CU was not ranked               */
+  int32_t mv[2];        /* the chosen state's vector, 1/16 pel, unclipped                 */
+  uint32_t cost_plain;  /* subpel_dist + ((bits * lambda16) >> 16) of the searched state  */
+  uint32_t cost_merge;  /* dist[order[0]] + ((bits * lambda16) >> 16); UINT32_MAX: none   */
+  uint32_t cost;        /* the chosen state's                                             */
+} xvcgpu_fp_merge_result;
+
+/* What xvcgpu_frame_pass_merge takes beside the flat pass's block; every array is the
+ * caller's, allocated once.  d_order: the CUs that try merge, strictly ascending indices
+ * into the pass's CUs; NULL: the CUs 0 .. n_listed - 1 (n_listed = n_cus: every CU).
+ * lambda_sqrt: sqrt(lambda) of the picture, the double SearchMergeCandidates ranks with.
+ * side_bits: as xvcgpu_frame_pass_affine_args (1 for a picture with one list);
+ * merge_side_bits: the closed-form side bits of a merge CU in front of its index (the merge
+ * flag: 1). */
+typedef struct xvcgpu_frame_pass_merge_args {
+  const xvcgpu_fp_merge_cand *d_cands;   /* XVC_FP_MERGE_CANDS * n_cus                    */
+  const int32_t *d_order;                /* n_listed, or NULL                             */
+  int32_t n_listed;
+  uint32_t side_bits;
+  uint32_t merge_side_bits;
+  uint32_t reserved;
+  double lambda_sqrt;
+  xvcgpu_fp_merge_ranking *d_rank;          /* n_cus; written for the listed CUs only        */
+  xvcgpu_fp_merge_result *d_choice;      /* n_cus                                         */
+  xvcgpu_me_result *d_chosen;            /* n_cus: what the pass behind the search reads  */
+} xvcgpu_frame_pass_merge_args;
+
 /* ---- the B frame pass with affine motion (xvcgpu_frame_pass_bi_refs_affine) -------- *
  * CompressInter's second SearchMotion run over both lists (inter_search.cc:74-99 with
  * SearchRefIdx<true> :484-572 and SearchBiIterative on affine vectors :394-435), behind

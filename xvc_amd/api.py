@@ -208,6 +208,30 @@ class FramePassAffineArgs(C.Structure):
 
 assert C.sizeof(FramePassAffineArgs) == 56
 
+# the P frame pass with merge mode (xvcgpu_frame_pass_merge; include/xvcgpu_types.h)
+FP_MERGE_CANDS = 5      # XVC_FP_MERGE_CANDS
+FP_MERGE_CAND_DTYPE = np.dtype([("ref_idx", "i1", (2,)), ("reserved", "u1", (2,)),
+                                ("mv", "<i4", (2, 2))])
+FP_MERGE_RANK_DTYPE = np.dtype([
+    ("dist", "<u4", (FP_MERGE_CANDS,)), ("order", "<i4", (FP_MERGE_CANDS,)), ("num", "<i4"),
+    ("reserved", "<u4"), ("cost", "<f8", (FP_MERGE_CANDS,))])
+FP_MERGE_RESULT_DTYPE = np.dtype([
+    ("use_merge", "<i4"), ("merge_idx", "<i4"), ("skip", "<i4"), ("num", "<i4"),
+    ("mv", "<i4", (2,)), ("cost_plain", "<u4"), ("cost_merge", "<u4"), ("cost", "<u4")])
+assert (FP_MERGE_CAND_DTYPE.itemsize, FP_MERGE_RANK_DTYPE.itemsize,
+        FP_MERGE_RESULT_DTYPE.itemsize) == (20, 88, 36)
+
+
+class FramePassMergeArgs(C.Structure):
+    """xvcgpu_frame_pass_merge_args (include/xvcgpu_types.h)"""
+    _fields_ = [("d_cands", C.c_void_p), ("d_order", C.c_void_p), ("n_listed", C.c_int32),
+                ("side_bits", C.c_uint32), ("merge_side_bits", C.c_uint32),
+                ("reserved", C.c_uint32), ("lambda_sqrt", C.c_double), ("d_rank", C.c_void_p),
+                ("d_choice", C.c_void_p), ("d_chosen", C.c_void_p)]
+
+
+assert C.sizeof(FramePassMergeArgs) == 64
+
 # xvcgpu_fp_bi_affine_result: CompressInter's two SearchMotion runs for one CU of a B picture
 FP_BI_AFFINE_RESULT_DTYPE = np.dtype([
     ("use_affine", "<i4"), ("inter_dir", "<i4"), ("ref_idx", "<i4", (2,)),
@@ -302,6 +326,8 @@ SYMBOLS = [
     "xvcgpu_fp_bi_affine_boot", "xvcgpu_affine_me_listed_refs", "xvcgpu_fp_bi_affine_uni_fold",
     "xvcgpu_fp_bi_affine_choice", "xvcgpu_cu_info_from_bi_affine_choice",
     "xvcgpu_frame_pass_bi_refs_affine",
+    "xvcgpu_fp_merge_rank", "xvcgpu_fp_merge_choice", "xvcgpu_fp_merge_skip",
+    "xvcgpu_frame_pass_merge",
 ]
 
 _vp = C.c_void_p
@@ -531,6 +557,11 @@ def load_library(allow_missing=()):
                                               C.c_int, _vp],
         "xvcgpu_frame_pass_affine": [_vp, C.POINTER(FramePassArgs), C.POINTER(FramePassAffineArgs),
                                      _vp, C.c_int],
+        "xvcgpu_fp_merge_rank": [_vp, _vp, _vp, _vp, C.c_int, C.POINTER(FramePassMergeArgs)],
+        "xvcgpu_fp_merge_choice": [_vp, _vp, _vp, C.c_int, C.POINTER(FramePassMergeArgs)],
+        "xvcgpu_fp_merge_skip": [_vp, _vp, _vp, C.c_int, _vp],
+        "xvcgpu_frame_pass_merge": [_vp, C.POINTER(FramePassArgs), C.POINTER(FramePassMergeArgs),
+                                    _vp, C.c_int],
         "xvcgpu_fp_bi_affine_boot": [_vp, C.POINTER(FramePassBiRefsArgs),
                                      C.POINTER(FramePassBiAffineArgs)],
         "xvcgpu_affine_me_listed_refs": [_vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp,

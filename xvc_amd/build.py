@@ -39,7 +39,7 @@ HOST_OUT = os.path.join(HERE, "libxvchost.so")
 HOST_SOURCES = ["xvc_picture_decoder.cc", "xvc_picture_schedule.cc", "xvc_inter_search.cc",
                 "xvc_shard_filter.cc", "xvc_cu_state.cc", "xvc_cu_state_builder.cc", "xvc_shard_engine.cc", "xvc_picture_engine.cc",
                 "xvc_frame_pass_bi_refs.cc", "xvc_frame_pass_aqp.cc",
-                "xvc_frame_pass_affine.cc"]
+                "xvc_frame_pass_affine.cc", "xvc_frame_pass_merge.cc"]
 
 
 def build_host(force=False, verbose=False):

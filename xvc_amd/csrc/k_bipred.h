@@ -434,4 +434,38 @@ mc_metric_refs_kernel(PlaneView orig, RefTable refs, const uint8_t *slots, int b
   mc_metric_body(orig, orig, bd, strength, cands, n, out, &refs, slots);
 }
 
+// The merge ranking's fold: SearchMergeCandidates' arithmetic (inter_search.cc:176-196)
+// behind the per-candidate distortions above.
+// Five costs in double (dist + bits * lambda_sqrt as the reference forms it - no
+// contraction, -ffp-contract=off), std::stable_sort = an insertion sort that only moves on
+// strictly smaller, the 1.25 x cut from the back.  dist: by merge index; cost: sorted;
+// order[k]: the merge index behind cost[k].  Returns num.  Its callers: the CU-state walk's
+// fold (k_cu_state.h) and the frame pass's rank kernel (k_fp_merge.h).
+template <class Dist>
+__device__ __forceinline__ int merge_rank_fold(const Dist *dist, double lambda_sqrt,
+                                               double cost[XVC_CS_MERGE_CANDS],
+                                               int order[XVC_CS_MERGE_CANDS]) {
+  for (int k = 0; k < XVC_CS_MERGE_CANDS; k++) {
+    const int bits = k + 1 - (k < XVC_CS_MERGE_CANDS - 1 ? 0 : 1);
+    cost[k] = (double)dist[k] + (double)bits * lambda_sqrt;
+    order[k] = k;
+  }
+  for (int a = 1; a < XVC_CS_MERGE_CANDS; a++) {   // stable: equal costs keep their order
+    const double c = cost[a];
+    const int o = order[a];
+    int b = a - 1;
+    while (b >= 0 && c < cost[b]) {
+      cost[b + 1] = cost[b];
+      order[b + 1] = order[b];
+      b--;
+    }
+    cost[b + 1] = c;
+    order[b + 1] = o;
+  }
+  int num = XVC_CS_MERGE_SLOTS;
+  for (int k = XVC_CS_MERGE_SLOTS; k >= 0; k--)
+    if (cost[k] > cost[0] * 1.25) num = k;
+  return num;
+}
+
 #endif  // XVCGPU_K_BIPRED_H_

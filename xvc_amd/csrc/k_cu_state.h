@@ -25,6 +25,7 @@
 #define XVCGPU_K_CU_STATE_H_
 
 #include "dev_common.h"
+#include "k_bipred.h"
 #include "xvcgpu_internal.h"
 
 #define XVC_BITS_FN __device__ __forceinline__
@@ -511,10 +512,8 @@ cs_bi_fold_kernel(const xvcgpu_cs_pass *passes, int first, int n,
   cs_bi_fold_body(passes, first, n, bi_res, aff_res, results, ev_inter);
 }
 
-// ---- the merge ranking's fold: SearchMergeCandidates' arithmetic (:176-196) ---------
-// One thread per ranking: five costs in double (dist + bits * lambda_sqrt as the
-// reference forms it - no contraction, -ffp-contract=off), std::stable_sort = an
-// insertion sort that only moves on strictly smaller, the 1.25 x cut from the back.
+// ---- the merge ranking's fold: merge_rank_fold (k_bipred.h) per CU state ------------
+// One thread per ranking.
 __device__ __forceinline__ void cs_merge_fold_body(const xvcgpu_cs_merge *merges, int first, int n,
                                      const uint64_t *dist, const xvcgpu_inter_block *cands,
                                      xvcgpu_cs_merge_result *results,
@@ -524,26 +523,7 @@ __device__ __forceinline__ void cs_merge_fold_body(const xvcgpu_cs_merge *merges
   const xvcgpu_cs_merge m = merges[first + i];
   double cost[XVC_CS_MERGE_CANDS];
   int order[XVC_CS_MERGE_CANDS];
-  for (int k = 0; k < XVC_CS_MERGE_CANDS; k++) {
-    const int bits = k + 1 - (k < XVC_CS_MERGE_CANDS - 1 ? 0 : 1);
-    cost[k] = (double)dist[m.dist + k] + (double)bits * m.lambda_sqrt;
-    order[k] = k;
-  }
-  for (int a = 1; a < XVC_CS_MERGE_CANDS; a++) {   // stable: equal costs keep their order
-    const double c = cost[a];
-    const int o = order[a];
-    int b = a - 1;
-    while (b >= 0 && c < cost[b]) {
-      cost[b + 1] = cost[b];
-      order[b + 1] = order[b];
-      b--;
-    }
-    cost[b + 1] = c;
-    order[b + 1] = o;
-  }
-  int num = XVC_CS_MERGE_SLOTS;
-  for (int k = XVC_CS_MERGE_SLOTS; k >= 0; k--)
-    if (cost[k] > cost[0] * 1.25) num = k;
+  const int num = merge_rank_fold(dist + m.dist, m.lambda_sqrt, cost, order);
   xvcgpu_cs_merge_result r;
   for (int k = 0; k < XVC_CS_MERGE_CANDS; k++) {
     r.cost[k] = cost[k];

@@ -45,6 +45,14 @@ __device__ __forceinline__ uint32_t fp_affine_mvd_bits(const int32_t mvp[3][2],
          d_mvd_bits(mvp[1][0], mvp[1][1], mv[1][0], mv[1][1], 0);
 }
 
+// The searched (translational) state's price: subpel_dist + (((side_bits + 1 + GetMvdBits(mvp,
+// mv, fullpel ? 2 : 0)) * lambda16) >> 16).  Its callers: the choice below and the merge
+// pass's (k_fp_merge.h).
+__device__ __forceinline__ uint32_t fp_plain_cost(const xvcgpu_me_block &b,
+                                                  const xvcgpu_me_result &q, uint32_t side_bits) {
+  return fp_bi_cost(q.subpel_dist, side_bits + 1 + fp_bi_mvd_bits(b, q.mv_x, q.mv_y), b.lambda16);
+}
+
 // grid: ceil(n_listed / 256); block: 256.  n_cus bounds the indices of `order`.
 __global__ void __launch_bounds__(256)
 fp_affine_boot_kernel(const xvcgpu_me_result *res, const int32_t *order, int n_listed,
@@ -107,8 +115,7 @@ fp_affine_choice_kernel(const xvcgpu_me_block *me, const xvcgpu_me_result *res, 
     memset(&c, 0xff, sizeof(c));
   } else {
     memset(&c, 0, sizeof(c));
-    c.cost_plain = fp_bi_cost(q.subpel_dist, side_bits + 1 + fp_bi_mvd_bits(b, q.mv_x, q.mv_y),
-                              b.lambda16);
+    c.cost_plain = fp_plain_cost(b, q, side_bits);
     c.cost_affine = 0xffffffffu;
     const xvcgpu_affine_me_block j = jobs[i];
     if (fp_affine_capable(b) && (j.flags & XVC_AFFINE_ME_HAS_BOOTSTRAP)) {

@@ -35,6 +35,7 @@
 #include "k_fp_bi_back.h"
 #include "k_aqp.h"
 #include "k_fp_affine.h"
+#include "k_fp_merge.h"
 #include "k_fp_bi_affine.h"
 #include "xvcgpu_internal.h"
 
@@ -2929,6 +2930,121 @@ xvcgpu_status xvcgpu_frame_pass_affine(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_
                                              a->d_cus_own);
   }
   if (st == XVCGPU_OK) st = fp_tail(ctx, a, phases, r.fused_tail, 0);
+  return st;
+}
+
+/* ---- the P frame pass with merge mode (k_fp_merge.h) ---- */
+static bool fp_merge_args_ok(const xvcgpu_frame_pass_merge_args *m, int n_cus) {
+  return m->n_listed >= 0 && m->n_listed <= n_cus;
+}
+
+xvcgpu_status xvcgpu_fp_merge_rank(xvcgpu_ctx *ctx, const xvcgpu_picture *orig,
+                                   const xvcgpu_picture *ref, const xvcgpu_me_block *d_me,
+                                   int n_cus, const xvcgpu_frame_pass_merge_args *m) {
+  if (!ctx || !orig || !ref || !m || n_cus < 0) return XVCGPU_INVALID_ARGUMENT;
+  if (orig->v.bd != ref->v.bd || orig->v.c[0].w != ref->v.c[0].w ||
+      orig->v.c[0].h != ref->v.c[0].h)
+    return fail(ctx, XVCGPU_INVALID_ARGUMENT, "fp_merge_rank: ref must be a picture of orig's size and depth");
+  if (!fp_merge_args_ok(m, n_cus))
+    return fail(ctx, XVCGPU_INVALID_ARGUMENT, "fp_merge_rank: n_listed outside [0, n_cus]");
+  if (!(m->lambda_sqrt >= 0) || !std::isfinite(m->lambda_sqrt))
+    return fail(ctx, XVCGPU_INVALID_ARGUMENT, "fp_merge_rank: lambda_sqrt");
+  if (m->n_listed && (!d_me || !m->d_cands || !m->d_rank))
+    return fail(ctx, XVCGPU_INVALID_ARGUMENT, "fp_merge_rank: d_me, d_cands and d_rank");
+  if (m->n_listed == 0) return XVCGPU_OK;
+  hipLaunchKernelGGL(fp_merge_rank_kernel, dim3((m->n_listed + 1) / 2), dim3(128), 0, ctx->stream,
+                     orig->v.c[0], ref->v.c[0], ref->v.bd, d_me, m->d_cands, m->d_order,
+                     m->n_listed, n_cus, m->lambda_sqrt, m->d_rank);
+  CHECK_LAUNCH(ctx, "fp_merge_rank");
+  return XVCGPU_OK;
+}
+
+xvcgpu_status xvcgpu_fp_merge_choice(xvcgpu_ctx *ctx, const xvcgpu_me_block *d_me,
+                                     const xvcgpu_me_result *d_results, int n_cus,
+                                     const xvcgpu_frame_pass_merge_args *m) {
+  if (!ctx || !m || n_cus < 0) return XVCGPU_INVALID_ARGUMENT;
+  if (n_cus && (!d_me || !d_results)) return XVCGPU_INVALID_ARGUMENT;
+  if (!fp_merge_args_ok(m, n_cus))
+    return fail(ctx, XVCGPU_INVALID_ARGUMENT, "fp_merge_choice: n_listed outside [0, n_cus]");
+  if (n_cus && (!m->d_choice || !m->d_chosen || (m->n_listed && (!m->d_cands || !m->d_rank))))
+    return fail(ctx, XVCGPU_INVALID_ARGUMENT,
+                "fp_merge_choice: d_cands, d_rank, d_choice and d_chosen");
+  if (n_cus == 0) return XVCGPU_OK;
+  hipLaunchKernelGGL(fp_merge_choice_kernel, dim3((n_cus + 255) / 256), dim3(256), 0,
+                     ctx->stream, d_me, d_results, n_cus, m->d_cands, m->d_order, m->n_listed,
+                     m->d_rank, m->side_bits, m->merge_side_bits, m->d_choice, m->d_chosen);
+  CHECK_LAUNCH(ctx, "fp_merge_choice");
+  return XVCGPU_OK;
+}
+
+xvcgpu_status xvcgpu_fp_merge_skip(xvcgpu_ctx *ctx, const int32_t *d_nnz,
+                                   const int32_t *d_luma_tx_index, int n_cus,
+                                   xvcgpu_fp_merge_result *d_choice) {
+  if (!ctx || n_cus < 0 || (n_cus && (!d_nnz || !d_choice))) return XVCGPU_INVALID_ARGUMENT;
+  if (n_cus == 0) return XVCGPU_OK;
+  hipLaunchKernelGGL(fp_merge_skip_kernel, dim3((n_cus + 255) / 256), dim3(256), 0, ctx->stream,
+                     d_nnz, d_luma_tx_index, n_cus, d_choice);
+  CHECK_LAUNCH(ctx, "fp_merge_skip");
+  return XVCGPU_OK;
+}
+
+xvcgpu_status xvcgpu_frame_pass_merge(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_args *a,
+                                      const xvcgpu_frame_pass_merge_args *m,
+                                      const xvcgpu_me_plan *plan, int phases) {
+  if (!m) return XVCGPU_INVALID_ARGUMENT;
+  xvcgpu_status st = plan ? fp_plan_check(ctx, a, plan) : XVCGPU_OK;
+  FramePassForm r;
+  if (st == XVCGPU_OK) st = frame_pass_resolve(ctx, a, phases, plan, &r);
+  if (st != XVCGPU_OK) return st;
+  const int n = a->n_cus;
+#define FPM_NEED(cond, what) \
+  if (!(cond)) return fail(ctx, XVCGPU_INVALID_ARGUMENT, "frame_pass_merge: " what)
+  FPM_NEED(phases & XVC_FP_ENCODE, "phases: the merge stage belongs to XVC_FP_ENCODE");
+  FPM_NEED(n == a->n_cus_total && a->db_y_begin == 0 && a->db_y_end >= a->rec->h &&
+               a->dbh_y_end >= a->rec->h && a->ssd_y_begin == 0 && a->ssd_y_end >= a->rec->h,
+           "whole pictures only (no row shard)");
+  FPM_NEED(m->lambda_sqrt >= 0 && std::isfinite(m->lambda_sqrt),
+           "lambda_sqrt must be finite and not below 0");
+  if (n > 0) {
+    FPM_NEED(m->n_listed >= 0 && m->n_listed <= n, "n_listed outside [0, n_cus]");
+    FPM_NEED(m->d_cands && m->d_rank && m->d_choice && m->d_chosen,
+             "d_cands, d_rank, d_choice and d_chosen");
+    FPM_NEED(a->d_nnz, "d_nnz: the skip flag is read from it");
+    FPM_NEED(a->rec->w == a->orig->w && a->rec->h == a->orig->h && a->rec->bd == a->orig->bd &&
+                 a->ref->w == a->orig->w && a->ref->h == a->orig->h && a->ref->bd == a->orig->bd,
+             "ref and rec must be pictures of orig's size and depth");
+  }
+#undef FPM_NEED
+  xvcgpu_picture *const rec = r.fused_tail ? a->scratch_rec : a->rec;
+  hipStream_t main_stream = nullptr;   // set while the pass runs on ctx->hi_stream
+  if (r.form) {
+    st = fp_search(ctx, a, a->ref, a->d_me, a->d_results, plan);
+    if (st != XVCGPU_OK) return st;   // (nothing behind a search that was refused)
+    st = xvcgpu_fp_merge_rank(ctx, a->orig, a->ref, a->d_me, n, m);
+    if (st == XVCGPU_OK) st = xvcgpu_fp_merge_choice(ctx, a->d_me, a->d_results, n, m);
+    if (st != XVCGPU_OK) return st;
+    // everything behind the search reads d_me and d_results[i].mv_x / mv_y only: the chosen
+    // results stand in for the search's
+    xvcgpu_frame_pass_args c = *a;
+    c.d_results = m->d_chosen;
+    switch (r.form) {
+      case XVC_FP_FORM_RECON_FROM_ME: st = fp_recon_from_me(ctx, &c, rec); break;
+      case XVC_FP_FORM_FWD_FROM_ME:
+        st = fp_fwd_from_me(ctx, &c, rec, r.tail_on_hi, &main_stream);
+        break;
+      default: st = fp_from_pred(ctx, &c, rec, r.form); break;
+    }
+    const bool from_me = r.form == XVC_FP_FORM_RECON_FROM_ME || r.form == XVC_FP_FORM_FWD_FROM_ME;
+    if (st == XVCGPU_OK)
+      st = xvcgpu_fp_merge_skip(ctx, a->d_nnz, from_me ? nullptr : a->d_luma_tx_index, n,
+                                m->d_choice);
+  }
+  if (st == XVCGPU_OK) st = fp_tail(ctx, a, phases, r.fused_tail, 0);
+  if (main_stream) {   // every way out: the chain continues on its own stream, after the tail
+    hipEventRecord(ctx->ev_hi_out, ctx->hi_stream);
+    ctx->stream = main_stream;
+    hipStreamWaitEvent(ctx->stream, ctx->ev_hi_out, 0);
+  }
   return st;
 }
 

@@ -219,6 +219,7 @@ class FramePass {
   // transform blocks are made here where the grid's fused form had none.
   void SetAdaptiveQp(int aqp_strength) {
     if (affine_) throw Error(XVCGPU_INVALID_ARGUMENT, "SetAdaptiveQp: not together with SetAffine");
+    if (merge_) throw Error(XVCGPU_INVALID_ARGUMENT, "SetAdaptiveQp: not together with SetMerge");
     aqp_.reset(new AdaptiveQpArrays(ctx_, w_, h_, bd_, qp_, aqp_strength, n_cus_));
     if (!d_tx_) {
       std::vector<xvcgpu_tx_block> tx;
@@ -280,6 +281,7 @@ class FramePass {
   // Not together with SetAdaptiveQp.
   void SetAffine(uint32_t side_bits = 1) {
     if (aqp_) throw Error(XVCGPU_INVALID_ARGUMENT, "SetAffine: not together with SetAdaptiveQp");
+    if (merge_) throw Error(XVCGPU_INVALID_ARGUMENT, "SetAffine: not together with SetMerge");
     std::vector<xvcgpu_affine_me_block> jobs;
     std::vector<int32_t> order;
     affine_args_ = AffineJobs(rects_, Lambda16(qp_), 0, 0, side_bits, &jobs, &order);
@@ -310,6 +312,65 @@ class FramePass {
   }
   // the last Run's record per CU (synchronises)
   std::vector<xvcgpu_fp_affine_result> AffineChoice() const { return d_choice_->ToHost(); }
+
+  // What a pass with merge mode takes beside the flat pass's jobs, on the host
+  // (pipeline.merge_cand_array / merge_args / lambda_sqrt_for_qp: the same bytes): the
+  // candidates from list 0's vectors mv[n_cus][5][2] (1/16 pel, unclipped, merge-index
+  // order; every candidate names picture 0 of list 0: ref_idx {0, -1}), the args block from
+  // its numbers (pointers null), and sqrt(lambda) of a QP - the expression Lambda16 floors.
+  static std::vector<xvcgpu_fp_merge_cand> MergeCands(const int32_t *mv, int n_cus) {
+    std::vector<xvcgpu_fp_merge_cand> c(static_cast<size_t>(n_cus) * XVC_FP_MERGE_CANDS,
+                                        xvcgpu_fp_merge_cand());
+    for (size_t k = 0; k < c.size(); k++) {
+      c[k].ref_idx[0] = 0;
+      c[k].ref_idx[1] = -1;
+      c[k].mv[0][0] = mv[2 * k];
+      c[k].mv[0][1] = mv[2 * k + 1];
+    }
+    return c;
+  }
+  static xvcgpu_frame_pass_merge_args MergeArgs(int n_listed, uint32_t side_bits,
+                                                uint32_t merge_side_bits, double lambda_sqrt) {
+    xvcgpu_frame_pass_merge_args m = xvcgpu_frame_pass_merge_args();
+    m.n_listed = n_listed;
+    m.side_bits = side_bits;
+    m.merge_side_bits = merge_side_bits;
+    m.lambda_sqrt = lambda_sqrt;
+    return m;
+  }
+  static double LambdaSqrtForQp(int qp) {
+    return std::sqrt(0.57 * std::pow(2.0, (qp - 12) / 3.0));
+  }
+
+  // From now on every Run tries merge mode for every CU behind the search
+  // (xvcgpu_frame_pass_merge): the five candidates mv[n_cus][5][2] are ranked as
+  // InterSearch::SearchMergeCandidates ranks them and the best is taken where its
+  // closed-form price is not above the searched state's; a merge CU without levels is a
+  // skip CU.  Every form the pass has.  lambda_sqrt < 0: LambdaSqrtForQp(qp).  Not together
+  // with SetAdaptiveQp or SetAffine.
+  void SetMerge(const int32_t *mv, uint32_t side_bits = 1, uint32_t merge_side_bits = 1,
+                double lambda_sqrt = -1.0) {
+    if (aqp_ || affine_)
+      throw Error(XVCGPU_INVALID_ARGUMENT, "SetMerge: not together with SetAdaptiveQp or SetAffine");
+    const size_t n = static_cast<size_t>(n_cus_ > 0 ? n_cus_ : 1);
+    std::vector<xvcgpu_fp_merge_cand> cands = MergeCands(mv, n_cus_);
+    if (cands.empty()) cands.push_back(xvcgpu_fp_merge_cand());   // (no empty device array)
+    merge_args_ = MergeArgs(n_cus_, side_bits, merge_side_bits,
+                            lambda_sqrt < 0 ? LambdaSqrtForQp(qp_) : lambda_sqrt);
+    d_cands_.reset(new DeviceArray<xvcgpu_fp_merge_cand>(ctx_, cands));
+    d_rank_.reset(new DeviceArray<xvcgpu_fp_merge_ranking>(ctx_, n));
+    d_merge_choice_.reset(new DeviceArray<xvcgpu_fp_merge_result>(ctx_, n));
+    d_chosen_.reset(new DeviceArray<xvcgpu_me_result>(ctx_, n));
+    merge_args_.d_cands = d_cands_->data();
+    merge_args_.d_rank = d_rank_->data();
+    merge_args_.d_choice = d_merge_choice_->data();
+    merge_args_.d_chosen = d_chosen_->data();
+    merge_ = true;
+  }
+  // the last Run's records per CU (synchronise)
+  std::vector<xvcgpu_fp_merge_ranking> MergeRank() const { return d_rank_->ToHost(); }
+  std::vector<xvcgpu_fp_merge_result> MergeChoice() const { return d_merge_choice_->ToHost(); }
+  std::vector<xvcgpu_me_result> ChosenResults() const { return d_chosen_->ToHost(); }
 
   // the last Run's delta per CTU (raster order) and {qp_y, qp_c} per CU (synchronise)
   std::vector<int8_t> CtuDeltaQp() const { return aqp_->CtuDeltaQp(); }
@@ -355,6 +416,10 @@ class FramePass {
     }
     if (affine_) {
       ctx_.Check(xvcgpu_frame_pass_affine(ctx_.get(), &a, &affine_args_, plan_, phases));
+      return;
+    }
+    if (merge_) {
+      ctx_.Check(xvcgpu_frame_pass_merge(ctx_.get(), &a, &merge_args_, plan_, phases));
       return;
     }
     if (aqp_) {
@@ -418,6 +483,12 @@ class FramePass {
   std::unique_ptr<DeviceArray<xvcgpu_affine_me_result>> d_affine_res_;
   std::unique_ptr<DeviceArray<xvcgpu_fp_affine_result>> d_choice_;
   std::unique_ptr<DeviceArray<xvcgpu_inter_block>> d_inter_;
+  bool merge_ = false;
+  xvcgpu_frame_pass_merge_args merge_args_;
+  std::unique_ptr<DeviceArray<xvcgpu_fp_merge_cand>> d_cands_;
+  std::unique_ptr<DeviceArray<xvcgpu_fp_merge_ranking>> d_rank_;
+  std::unique_ptr<DeviceArray<xvcgpu_fp_merge_result>> d_merge_choice_;
+  std::unique_ptr<DeviceArray<xvcgpu_me_result>> d_chosen_;
   std::unique_ptr<DeviceArray<xvcgpu_tx_block>> d_tx_;
   std::unique_ptr<DeviceArray<int32_t>> d_luma_;
   std::unique_ptr<Picture> pred_;

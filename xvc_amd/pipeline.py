@@ -44,6 +44,12 @@ def lambda16_for_qp(qp):
     return int(math.floor(65536.0 * math.sqrt(lam)))
 
 
+def lambda_sqrt_for_qp(qp):
+    """sqrt(lambda) in double, lambda = 0.57*2^((qp-12)/3): the expression lambda16_for_qp
+    floors, what SearchMergeCandidates ranks with (qp.GetLambdaSqrt())."""
+    return math.sqrt(0.57 * math.pow(2.0, (qp - 12) / 3.0))
+
+
 _INV_QUANT_SCALES = (40, 45, 51, 57, 64, 72)       # quantize.cc:44-46
 _DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data")
 _init_ctx_table = None
@@ -208,6 +214,76 @@ class _AffineArrays:
         for b in (self.d_affine, self.d_affine_res, self.d_order, self.d_choice, self.d_inter):
             if b is not None:
                 b.free()
+
+
+def merge_cand_array(cands, n_cus):
+    """A pass's merge candidates as api.FP_MERGE_CAND_DTYPE [n_cus, 5]: from such an array as
+    it is, or from list 0's vectors [n_cus, 5, 2] int32 (1/16 pel, unclipped) - every candidate
+    then names picture 0 of list 0 and leaves list 1 unused (ref_idx = {0, -1}).  The same
+    bytes as xvc_gpu::FramePass::MergeCands makes."""
+    c = np.asarray(cands)
+    if c.dtype == api.FP_MERGE_CAND_DTYPE:
+        if c.shape != (n_cus, api.FP_MERGE_CANDS):
+            raise ValueError("merge_cands: expected %d x %d candidates, got shape %r"
+                             % (n_cus, api.FP_MERGE_CANDS, c.shape))
+        return np.ascontiguousarray(c)
+    if c.shape != (n_cus, api.FP_MERGE_CANDS, 2) or not np.issubdtype(c.dtype, np.integer):
+        raise ValueError("merge_cands: expected an integer array [%d, %d, 2] (x, y per "
+                         "candidate), got shape %r, dtype %s"
+                         % (n_cus, api.FP_MERGE_CANDS, c.shape, c.dtype))
+    out = np.zeros((n_cus, api.FP_MERGE_CANDS), api.FP_MERGE_CAND_DTYPE)
+    out["ref_idx"] = (0, -1)
+    out["mv"][:, :, 0, :] = c
+    return out
+
+
+def merge_order_array(order, n_cus):
+    """(d_order or None, n_listed) of xvcgpu_frame_pass_merge_args: None lists every CU (a
+    NULL list of n_cus); else the strictly ascending CU indices that try merge."""
+    if order is None:
+        return None, n_cus
+    o = np.asarray(order, np.int64).reshape(-1)
+    if len(o) and (o[0] < 0 or o[-1] >= n_cus or (np.diff(o) <= 0).any()):
+        raise ValueError("merge_order: strictly ascending indices in [0, %d) expected" % n_cus)
+    return o.astype(np.int32), len(o)
+
+
+class _MergeArrays:
+    """What a pass with merge mode holds beside the flat pass's state: the arrays of
+    xvcgpu_frame_pass_merge_args (allocated once; every run writes the work arrays)."""
+
+    def __init__(self, ctx, desc, cands, order, side_bits, merge_side_bits, lambda_sqrt):
+        self.ctx, self.n_cus = ctx, desc.n_cus
+        self.side_bits, self.merge_side_bits = side_bits, merge_side_bits
+        self.lambda_sqrt = float(lambda_sqrt)
+        self.cands = cands                      # merge_cand_array's
+        self.order, self.n_listed = order       # merge_order_array's
+        n = max(1, desc.n_cus)
+        self.d_cands = ctx.buffer(self.cands) if desc.n_cus else ctx.alloc(api.FP_MERGE_CAND_DTYPE.itemsize)
+        self.d_order = ctx.buffer(self.order) if self.order is not None and len(self.order) else None
+        self.d_rank = ctx.buffer(np.zeros(n, api.FP_MERGE_RANK_DTYPE))
+        self.d_choice = ctx.buffer(np.zeros(n, api.FP_MERGE_RESULT_DTYPE))
+        self.d_chosen = ctx.buffer(np.zeros(n, api.MERES_DTYPE))
+
+    def args(self):
+        return merge_args(self.n_listed, self.side_bits, self.merge_side_bits, self.lambda_sqrt,
+                          self.d_cands.ptr, self.d_order.ptr if self.d_order is not None else None,
+                          self.d_rank.ptr, self.d_choice.ptr, self.d_chosen.ptr)
+
+    def free(self):
+        for b in (self.d_cands, self.d_order, self.d_rank, self.d_choice, self.d_chosen):
+            if b is not None:
+                b.free()
+
+
+def merge_args(n_listed, side_bits, merge_side_bits, lambda_sqrt, d_cands=None, d_order=None,
+               d_rank=None, d_choice=None, d_chosen=None):
+    """xvcgpu_frame_pass_merge_args from its parts (pointers: integers or None)."""
+    m = api.FramePassMergeArgs()
+    m.d_cands, m.d_order, m.n_listed = d_cands, d_order, n_listed
+    m.side_bits, m.merge_side_bits, m.lambda_sqrt = side_bits, merge_side_bits, lambda_sqrt
+    m.d_rank, m.d_choice, m.d_chosen = d_rank, d_choice, d_chosen
+    return m
 
 
 _AQP_FORMS = ("fwd_transform", "residual", "residual_rdoq")
@@ -475,6 +551,9 @@ def run_multi(passes, origs, refs, recs, ref_pocs=None):
     n = len(passes)
     if any(getattr(p, "affine", None) is not None for p in passes):
         raise ValueError("run_multi: a pass with affine motion has no multi-picture form")
+    if any(getattr(p, "merge", None) is not None for p in passes):
+        raise ValueError("merge_cands and run_multi: a pass with merge mode has no "
+                         "multi-picture form")
     if any(p.plan is not None for p in passes):
         for i, p in enumerate(passes):
             p.run(origs[i], refs[i], recs[i], ref_pocs[i] if ref_pocs is not None else 0)
@@ -524,16 +603,42 @@ class FramePass:
     `residual_rdoq`; else ValueError), not together with aqp_strength and not through
     run_multi.  affine_mvp: the jobs' corner predictors [n_cus, 3, 2]; None: the plain
     job's mvp at every corner.  side_bits: 1, a picture with one list.  affine_choice()
-    reads the last run's records back."""
+    reads the last run's records back.
+
+    merge_cands=: the pass with merge mode (xvcgpu_frame_pass_merge): five candidate motions
+    per CU - list 0's vectors [n_cus, 5, 2] int32 in 1/16 pel, unclipped, in merge-index
+    order, or api.FP_MERGE_CAND_DTYPE [n_cus, 5] -, an input as a job's mvp is.  Behind the
+    search every listed CU ranks them (SearchMergeCandidates) and takes the best where its
+    closed-form price is not above the searched state's; a merge CU without levels is a skip
+    CU.  Every form, grid or partition, whole pictures; not together with affine, aqp_strength,
+    run_multi or a row_range (ValueError).  merge_order: None, every CU, or the ascending
+    indices of the CUs that try merge.  merge_side_bits: the merge flag's bit.
+    merge_lambda_sqrt: None, sqrt(0.57 * 2^((qp - 12) / 3)) in double, or the picture's.
+    merge_rank(), merge_choice() and chosen_results() read the last run's records back;
+    results() keeps the search's answer."""
 
     def __init__(self, ctx, width, height, bitdepth=10, qp=32, cu=16,
                  search_range=96, row_range=None, fused=True, keep_levels=False,
                  rdoq=False, rdoq_packed=None, xcd_tiles=False, partition=None, form=None,
-                 aqp_strength=None, affine=False, affine_mvp=None, side_bits=1):
+                 aqp_strength=None, affine=False, affine_mvp=None, side_bits=1,
+                 merge_cands=None, merge_side_bits=1, merge_lambda_sqrt=None, merge_order=None):
         self.ctx = ctx
         self.plan = None
         self.aqp = None
         self.affine = None
+        self.merge = None
+        if merge_cands is not None:     # (refusals before anything is allocated)
+            if affine:
+                raise ValueError("merge_cands and affine: not together (out of scope)")
+            if aqp_strength is not None:
+                raise ValueError("merge_cands and aqp_strength: not together (out of scope)")
+            if not (row_range is None or (max(0, row_range[0]), min(height, row_range[1])) ==
+                    (0, height)):
+                raise ValueError("merge_cands and row_range: whole pictures only")
+            if merge_lambda_sqrt is None:
+                merge_lambda_sqrt = lambda_sqrt_for_qp(qp)
+            if not (math.isfinite(merge_lambda_sqrt) and merge_lambda_sqrt >= 0):
+                raise ValueError("merge_lambda_sqrt: a finite value not below 0 expected")
         self.rdoq = rdoq
         # RDOQ keeps only a few lanes of a wave busy per block, so its own kernel
         # packs several blocks into a wave (xvcgpu_quant_rdo_batch) between the
@@ -584,6 +689,9 @@ class FramePass:
                                  "form=\"fwd_transform\")" % (self.form, ", ".join(_AQP_FORMS)))
             if d.row_range != (0, d.h):
                 raise ValueError("affine: whole pictures only (no row_range)")
+        if merge_cands is not None:     # (a refused array: before anything is allocated)
+            merge_cands = merge_cand_array(merge_cands, d.n_cus)
+            merge_order = merge_order_array(merge_order, d.n_cus)
         self.d_rdoq_ctx = ctx.buffer(d.rdoq_contexts) if rdoq else None
         self.d_rdoq_prm = ctx.buffer(d.rdoq_params) if rdoq else None
         self.d_me = ctx.buffer(d.me)
@@ -643,6 +751,9 @@ class FramePass:
             self.aqp = _AqpArrays(ctx, d, bitdepth, aqp_strength)
         if affine:
             self.affine = _AffineArrays(ctx, d, affine_mvp, side_bits)
+        if merge_cands is not None:
+            self.merge = _MergeArrays(ctx, d, merge_cands, merge_order, side_bits,
+                                      merge_side_bits, merge_lambda_sqrt)
 
     @property
     def d_cus_own(self):
@@ -711,6 +822,12 @@ class FramePass:
                 self.ctx.h, C.byref(a), C.byref(f), self.plan.h if self.plan is not None else None,
                 phases))
             return
+        if self.merge is not None:
+            m = self.merge.args()
+            self.ctx._check(self.ctx.lib.xvcgpu_frame_pass_merge(
+                self.ctx.h, C.byref(a), C.byref(m), self.plan.h if self.plan is not None else None,
+                phases))
+            return
         if self.plan is not None:
             self.ctx._check(self.ctx.lib.xvcgpu_frame_pass_planned(self.ctx.h, C.byref(a),
                                                                    self.plan.h, phases))
@@ -731,6 +848,8 @@ class FramePass:
         xvcgpu_quant_rdo_set_list_form) -> quant_rdo_packed4_kernel [-> quant_rdo_packed_kernel]."""
         if self.affine is not None:     # (these are the flat pass's launches)
             raise ValueError("a pass with affine motion runs through run() / run_phases() only")
+        if self.merge is not None:
+            raise ValueError("a pass with merge mode runs through run() / run_phases() only")
         ctx, d, lib = self.ctx, self.desc, self.ctx.lib
         n, T, bd, form = d.n_cus, len(d.tx), self.bd, self.form
         out = self.scratch if fused_tail else rec
@@ -850,10 +969,26 @@ class FramePass:
         """Affine motion: the last run's api.FP_AFFINE_RESULT_DTYPE record per CU."""
         return self.affine.choice()
 
+    def merge_rank(self):
+        """Merge mode: the last run's api.FP_MERGE_RANK_DTYPE record per CU (the CUs outside
+        the list: as allocated, zero)."""
+        return self.merge.d_rank.to_array(api.FP_MERGE_RANK_DTYPE, self.desc.n_cus)
+
+    def merge_choice(self):
+        """Merge mode: the last run's api.FP_MERGE_RESULT_DTYPE record per CU."""
+        return self.merge.d_choice.to_array(api.FP_MERGE_RESULT_DTYPE, self.desc.n_cus)
+
+    def chosen_results(self):
+        """Merge mode: the results the pass behind the search ran on (api.MERES_DTYPE)."""
+        return self.merge.d_chosen.to_array(api.MERES_DTYPE, self.desc.n_cus)
+
     def destroy(self):
         if self.aqp is not None:
             self.aqp.free()
             self.aqp = None
+        if self.merge is not None:
+            self.merge.free()
+            self.merge = None
         if self.affine is not None:
             self.affine.free()
             self.affine = None
