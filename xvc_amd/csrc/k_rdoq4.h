@@ -28,6 +28,11 @@
 //     and a lane whose budget CLASS differs once the levels in front of it are
 //     counted decides again (the class changes at most twice per sub-block, so
 //     this second trip is rare; lanes are final in scan order, four trips at most);
+//     of a sub-block's seven anti-diagonals only those are visited on which a
+//     coefficient of the diagonal's sub-blocks has a choice; a trip whose candidates
+//     all quantise to 1 prices the one against zero directly; with one unit per lane
+//     the quad exchanges a level as three counts in one register (!= 0, >= 1, >= 2),
+//     summed by DPP, with four units the levels themselves;
 //   * one block per wave (G = 64): the no-choice coefficients of an anti-diagonal of
 //     sub-blocks (4 x 16, or 8 x 16 in a 32x32 corner) are one or two rounds, and no
 //     other block's trip counts are paid for;
@@ -111,6 +116,22 @@ __device__ __forceinline__ int rq4_sum(int v) {
     v = __builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16) +
         __builtin_amdgcn_readlane(v, 32) + __builtin_amdgcn_readlane(v, 48);
   return v;
+}
+// OR of a set of at most eight bits over the lanes that walk, wave-uniform: with 64 lanes
+// per block the whole wave walks - DPP inside the rows, the four rows through v_readlane;
+// of the groups of sixteen some may be outside the call, so a ballot per bit.
+template <int G>
+__device__ __forceinline__ unsigned rq4_wave_or8(unsigned v, int bits) {
+  if (G == 64) {
+    int o = rq4_quad_or((int)v);
+    o |= rq4_row_half_mirror(o);
+    o |= rq4_row_mirror(o);
+    return (unsigned)(__builtin_amdgcn_readlane(o, 0) | __builtin_amdgcn_readlane(o, 16) |
+                      __builtin_amdgcn_readlane(o, 32) | __builtin_amdgcn_readlane(o, 48));
+  }
+  unsigned r = 0;
+  for (int b = 0; b < bits; b++) r |= (__ballot((v >> b) & 1u) ? 1u : 0u) << b;
+  return r;
 }
 __device__ __forceinline__ long long rq4_readlane_i64(long long v, int l) {
   const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, l);
@@ -264,6 +285,9 @@ __device__ __forceinline__ int wave_rdoq4(S &s, int lane, const BlockQuant &bq, 
   // ---- the units: magnitudes, plain quantised values, signs (two 16-bit halves a
   // register); per sub-block the zero distortion and the q != 0 set; the last position
   unsigned pa[NR][2], pq[NR][2], negs = 0, valid = 0;
+  // one unit per lane: the anti-diagonals x + j of its sub-block on which this row has a
+  // choice (four units: taken from the unit's values per diagonal - a register less to hold)
+  unsigned sdm = 0;
   int scan_u[NR];
   long long zd_u[NR];          // (the sub-block's, equal on its four lanes)
   int last = -1;
@@ -289,7 +313,10 @@ __device__ __forceinline__ int wave_rdoq4(S &s, int lane, const BlockQuant &bq, 
       q[i] = bq.fwd(a[i]);
       negs |= (unsigned)(c[i] < 0) << (4 * r + i);
       sum_sq += (unsigned)(a[i] * a[i]);
-      if (q[i]) qm |= 1u << kof(i);
+      if (q[i]) {
+        qm |= 1u << kof(i);
+        if (NR == 1) sdm |= 1u << i;
+      }
     }
     pa[r][0] = (unsigned)(a[0] & 0xffff) | ((unsigned)a[1] << 16);
     pa[r][1] = (unsigned)(a[2] & 0xffff) | ((unsigned)a[3] << 16);
@@ -301,6 +328,7 @@ __device__ __forceinline__ int wave_rdoq4(S &s, int lane, const BlockQuant &bq, 
     const int l = mine && qmask ? (scan_u[r] << 4) + 31 - __clz((int)qmask) : -1;
     last = l > last ? l : last;
   }
+  sdm <<= j;
   const int last_pos_index = rq4_max<G>(last);
   RQ_TRACE(4);
   if (last_pos_index < 0) {  // nothing quantises to a level
@@ -434,13 +462,20 @@ __device__ __forceinline__ int wave_rdoq4(S &s, int lane, const BlockQuant &bq, 
     // on its four lanes)
     int c1 = 0, c2 = 0, nz = 0;
     long long code_cost = 0;
-    for (int sd = 6; sd >= 0; sd--) {
+    // only the anti-diagonals on which a sub-block of this diagonal has a choice, from
+    // the highest down (most of the seven are empty: no trip, no ballot for them)
+    if (NR > 1)
+      sdm = ((unsigned)((uq[0] & 0xffffu) != 0) | ((unsigned)((uq[0] >> 16) != 0) << 1) |
+             ((unsigned)((uq[1] & 0xffffu) != 0) << 2) | ((unsigned)((uq[1] >> 16) != 0) << 3)) << j;
+    unsigned sds = rq4_wave_or8<G>(act ? sdm : 0u, 7);
+    while (sds) {
+      const int sd = 31 - __clz((int)sds);
+      sds &= ~(1u << sd);
       const int x = sd - j;
       const bool on = act && (unsigned)x < 4u;
       const int xi = on ? x : 0;
       const int qv = half(uq, xi);
       const bool has = on && qv != 0;
-      if (!__ballot(has)) continue;
       const int abs_coeff = half(ua, xi);
       const int k = kof(xi);
       const int p = row_p + xi;
@@ -486,42 +521,76 @@ __device__ __forceinline__ int wave_rdoq4(S &s, int lane, const BlockQuant &bq, 
       bool need = has;
       int best_level = 0;
       long long best_cost = 0;
-      int v0, v1, v2, v3;
-      for (;;) {
-        if (need) {
-          RdoqCoeffState st = {c1a, c2a, gr};
-          best_cost = 0x7fffffffffffffffll;
-          best_level = qv;   // (a magnitude of 32768 wraps to q < 0: no candidate but zero)
-          if (qv > 0) {
-            if (qv > 1) {
-              best_cost = dist_q1 + rq_bit_cost(sig1 + rq_abs_level_bits(fb, qv - 1, st), lambda);
-              best_level = qv - 1;
-            }
-            const long long cost =
-                dist_q + rq_bit_cost(sig1 + rq_abs_level_bits(fb, qv, st), lambda);
-            if (cost <= best_cost) {
-              best_cost = cost;
-              best_level = qv;
-            }
+      // any level
+      auto decide_any = [&]() {
+        RdoqCoeffState st = {c1a, c2a, gr};
+        best_cost = 0x7fffffffffffffffll;
+        best_level = qv;   // (a magnitude of 32768 wraps to q < 0: no candidate but zero)
+        if (qv > 0) {
+          if (qv > 1) {
+            best_cost = dist_q1 + rq_bit_cost(sig1 + rq_abs_level_bits(fb, qv - 1, st), lambda);
+            best_level = qv - 1;
           }
-          if (zero_ok && zero_alt <= best_cost) {
-            best_cost = zero_alt;
-            best_level = 0;
+          const long long cost = dist_q + rq_bit_cost(sig1 + rq_abs_level_bits(fb, qv, st), lambda);
+          if (cost <= best_cost) {
+            best_cost = cost;
+            best_level = qv;
           }
         }
-        const int mylv = has ? best_level : 0;
-        v0 = rq4_quad_bcast<0>(mylv);
-        v1 = rq4_quad_bcast<1>(mylv);
-        v2 = rq4_quad_bcast<2>(mylv);
-        v3 = rq4_quad_bcast<3>(mylv);
-        // reverse scan visits an anti-diagonal from its top-right end: rows ascending
-        const int c1t = c1 + (j > 0 && v0 >= 1) + (j > 1 && v1 >= 1) + (j > 2 && v2 >= 1);
-        const int c2t = c2 + (j > 0 && v0 >= 2) + (j > 1 && v1 >= 2) + (j > 2 && v2 >= 2);
-        need = has && ((c1t < 8) != (c1a < 8) || (c2t < 1) != (c2a < 1));
-        c1a = c1t;
-        c2a = c2t;
-        if (!__ballot(need)) break;
-      }
+        if (zero_ok && zero_alt <= best_cost) {
+          best_cost = zero_alt;
+          best_level = 0;
+        }
+      };
+      // q == 1, one against zero: GetAbsLevelBits of level 1 is the greater-1 flag's zero
+      // bin while the budget lasts (1 < base_level) and the Golomb-Rice code of 0 after it
+      // (base_level = 1, no flag) - neither reads c2
+      auto decide_one = [&]() {
+        const unsigned bits1 = c1a < 8 ? RQ_BYPASS + fb.c1_0 : (2u + gr) * RQ_BYPASS;
+        best_cost = dist_q + rq_bit_cost(sig1 + bits1, lambda);
+        best_level = 1;
+        if (zero_ok && zero_alt <= best_cost) {
+          best_cost = zero_alt;
+          best_level = 0;
+        }
+      };
+      // The quad's levels as three counts a byte each (!= 0, >= 1, >= 2), summed over the
+      // rows in front of this one: the reverse scan visits an anti-diagonal from its
+      // top-right end, rows ascending.  Decide, exchange, and again where the budget class
+      // a lane assumed was another.  (Four units per lane: the levels themselves are
+      // exchanged and compared - the kernels that hold that walk stand at 256 vector
+      // registers, and the packed form costs them a wave per SIMD.)
+      unsigned flags = 0;
+      int v0 = 0, v1 = 0, v2 = 0, v3 = 0;   // (four units per lane)
+      auto settle = [&](auto decide, const bool c2_read) {
+        for (;;) {
+          if (need) decide();
+          const int mylv = has ? best_level : 0;
+          int c1t, c2t;
+          if (NR == 1) {
+            flags = (unsigned)(mylv != 0) | ((unsigned)(mylv >= 1) << 8) | ((unsigned)(mylv >= 2) << 16);
+            const unsigned f0 = (unsigned)rq4_quad_bcast<0>((int)flags),
+                           f1 = (unsigned)rq4_quad_bcast<1>((int)flags),
+                           f2 = (unsigned)rq4_quad_bcast<2>((int)flags);
+            const unsigned front = (j > 0 ? f0 : 0u) + (j > 1 ? f1 : 0u) + (j > 2 ? f2 : 0u);
+            c1t = c1 + (int)((front >> 8) & 0xffu);
+            c2t = c2 + (int)(front >> 16);
+          } else {
+            v0 = rq4_quad_bcast<0>(mylv);
+            v1 = rq4_quad_bcast<1>(mylv);
+            v2 = rq4_quad_bcast<2>(mylv);
+            v3 = rq4_quad_bcast<3>(mylv);
+            c1t = c1 + (j > 0 && v0 >= 1) + (j > 1 && v1 >= 1) + (j > 2 && v2 >= 1);
+            c2t = c2 + (j > 0 && v0 >= 2) + (j > 1 && v1 >= 2) + (j > 2 && v2 >= 2);
+          }
+          need = has && ((c1t < 8) != (c1a < 8) || (c2_read && (c2t < 1) != (c2a < 1)));
+          c1a = c1t;
+          c2a = c2t;
+          if (!__ballot(need)) break;
+        }
+      };
+      if (!__ballot(has && qv != 1)) settle(decide_one, false);   // (wave-uniform)
+      else settle(decide_any, true);
       if (has) {
         wl[p] = (short)best_level;
         s.rate_up[rec_pos((sx << 2) + xi, (sy << 2) + j)] =
@@ -529,9 +598,16 @@ __device__ __forceinline__ int wave_rdoq4(S &s, int lane, const BlockQuant &bq, 
         if (dc_sig_zero) s.sb_dcz[sbi] = 1;
         code_cost += best_cost;
       }
-      c1 += (v0 >= 1) + (v1 >= 1) + (v2 >= 1) + (v3 >= 1);
-      c2 += (v0 >= 2) + (v1 >= 2) + (v2 >= 2) + (v3 >= 2);
-      nz += (v0 != 0) + (v1 != 0) + (v2 != 0) + (v3 != 0);
+      if (NR == 1) {
+        const unsigned quad = (unsigned)dpp_group_sum<4>((int)flags);
+        nz += (int)(quad & 0xffu);
+        c1 += (int)((quad >> 8) & 0xffu);
+        c2 += (int)(quad >> 16);
+      } else {
+        c1 += (v0 >= 1) + (v1 >= 1) + (v2 >= 1) + (v3 >= 1);
+        c2 += (v0 >= 2) + (v1 >= 2) + (v2 >= 2) + (v3 >= 2);
+        nz += (v0 != 0) + (v1 != 0) + (v2 != 0) + (v3 != 0);
+      }
       wave_sync();   // the levels are in place for the next anti-diagonal's templates
     }
     code_cost = rq_group_sum_i64<4>(code_cost);
