@@ -1495,7 +1495,8 @@ xvcgpu_status xvcgpu_frame_pass_affine(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_
  * merge CU that keeps no level is a skip CU.  The pass puts a merge stage between the search
  * and the rest of the flat pass: launches that exist and three small ones (k_fp_merge.h);
  * nothing is read back.  xvcgpu_types.h: xvcgpu_fp_merge_cand, xvcgpu_fp_merge_ranking,
- * xvcgpu_fp_merge_result, xvcgpu_frame_pass_merge_args.  One list, one reference picture.
+ * xvcgpu_fp_merge_result, xvcgpu_frame_pass_merge_args.  One list, one reference picture;
+ * a B picture's lists: xvcgpu_frame_pass_bi_refs_merge, further down.
  *
  * Inputs per CU: XVC_FP_MERGE_CANDS = 5 candidates (constants::kNumInterMergeCandidates) in
  * merge-index order, m->d_cands[5 i + m]; vectors in 1/16 pel, unclipped; an input, as a
@@ -1625,6 +1626,73 @@ xvcgpu_status xvcgpu_cu_info_from_bi_affine_choice(xvcgpu_ctx *ctx,
 xvcgpu_status xvcgpu_frame_pass_bi_refs_affine(
     xvcgpu_ctx *ctx, const xvcgpu_frame_pass_bi_refs_args *a,
     const xvcgpu_frame_pass_bi_affine_args *f,
+    const xvcgpu_me_plan *const plans[2][XVC_CS_MAX_REFS], int phases);
+
+/* ---- the B frame pass with merge mode --------------------------------------------- *
+ * CompressMerge before CompressInter (cu_encoder.cc:469-481) for a B picture: a merge stage
+ * between xvcgpu_fp_bi_refs_choice and the prediction of xvcgpu_frame_pass_bi_refs; launches
+ * that exist and three new ones (k_fp_bi_merge.h); nothing is read back.  xvcgpu_types.h:
+ * xvcgpu_fp_merge_cand, xvcgpu_fp_merge_ranking, xvcgpu_fp_bi_merge_result,
+ * xvcgpu_frame_pass_bi_merge_args.  The small entries take the pass's two blocks and read
+ * the tables of `a` (num_ref, slot, refs, d_me[0][0], d_choice, d_inter).
+ *
+ * Inputs per CU: XVC_FP_MERGE_CANDS = 5 candidates in merge-index order, m->d_cands[5 i + m];
+ * vectors in 1/16 pel, unclipped; an input, as a job's mvp is (no GetMergeCandidates
+ * derivation).  A candidate is valid when each ref_idx[l] is -1 or in 0 .. num_ref[l] - 1 and
+ * at least one list is used.  The picture for list l is refs[slot[l][ref_idx[l]]].
+ *
+ * xvcgpu_fp_bi_merge_rank: InterSearch::SearchMergeCandidates (inter_search.cc:165-197) with
+ * MotionCompensation's two branches (inter_prediction.cc:710-738).  One wave per listed CU
+ * (m->d_order[0 .. n_listed), strictly ascending; NULL: the CUs 0 .. n_listed - 1), two waves a
+ * workgroup; the CU's geometry is that of d_me[0][0][i].  One list used: dist[m] is the SATD
+ * (XVC_METRIC_SATD) of the original luma block against the luma prediction at ClipMv(mv[l])
+ * from that list's picture.  Both lists used: each list's luma prediction is taken at ClipMv
+ * of its own vector in the 14-bit intermediate form (MotionCompRefList with post_filter =
+ * false), AddAvgBi follows (:1545-1547: (p0 + p1 + (1 << (s - 1)) + 2 * 8192) >> s clipped to
+ * the depth, s = max(2, 14 - depth) + 1), and dist[m] is the SATD against that.  No prediction
+ * goes to memory.  cost, the stable sort and num: as xvcgpu_fp_merge_rank.  A candidate that
+ * is invalid, or whose CU shape is outside w, h in {4, 8, 16, 32, 64}, gets dist = UINT32_MAX.
+ * Writes m->d_rank[i] of the listed CUs; records outside the list are not touched.
+ * xvcgpu_fp_bi_merge_choice: one thread per CU.  m0 = order[0]; cost_merge = dist[m0] +
+ * (((merge_side_bits + bits(m0)) * lambda16) >> 16) with the lambda16 of d_me[0][0][i], a
+ * 64-bit product, kept in 32 bits; compared with the plain run's a->d_choice[i].cost.  Merge
+ * where cost_merge <= cost: the reference evaluates merge first and a later mode replaces it
+ * only on strict <.  No merge - use_merge = 0, cost_merge = UINT32_MAX, merge_idx = -1 - where
+ * dist[m0] == UINT32_MAX, where the list does not name the CU and where the plain job
+ * d_me[0][0][i] carries XVC_ME_USE_LIC (and for a candidate m0 that is not valid, whatever
+ * the ranking record says).  Writes m->d_choice[i] (skip = 0) and m->d_chosen[i]: a copy of
+ * a->d_choice[i], and where merge won inter_dir, ref_idx, mv (an unused list gets -1 and zero)
+ * and cost are the candidate's.  For a merge winner the CU's three jobs a->d_inter[3 i + comp]
+ * are rewritten: ref[l] the table slot or -1, the vectors unclipped; other jobs are left
+ * alone.  a->d_choice is not written.  A plain record of all ones stays all ones in both
+ * outputs.
+ * xvcgpu_fp_bi_merge_skip: xvcgpu_fp_merge_skip on xvcgpu_fp_bi_merge_result records:
+ * d_choice[i].skip = use_merge && d_nnz[t], [t + 1], [t + 2] are all zero, t =
+ * d_luma_tx_index[i], NULL: t = 3 i.  An all-ones record is left alone.
+ *
+ * xvcgpu_frame_pass_bi_refs_merge: the launches of xvcgpu_frame_pass_bi_refs up to its choice
+ * unchanged -> rank -> choice -> xvcgpu_inter_pred_batch over a->d_inter -> the residual
+ * pipeline of the form -> xvcgpu_cu_info_from_choice_refs on a copy of the block whose
+ * d_choice is m->d_chosen (ref_poc, ref_idx0 and the vectors are the chosen state's) -> skip
+ * -> the B tail.  Every check of xvcgpu_frame_pass_bi_refs (a set force_l1_mvd_zero, the
+ * _from_me forms, part of a picture, plans with LIC jobs) and of `m` happens before the first
+ * launch (XVCGPU_INVALID_ARGUMENT, the message names the field): a missing array (d_cands,
+ * d_rank, d_choice, d_chosen, p.d_nnz), m->d_chosen or m->d_choice that is a->d_choice or
+ * each other, n_listed outside [0, n_cus], phases without
+ * XVC_FP_ENCODE, lambda_sqrt not finite or below 0.  After them the call only enqueues: no
+ * synchronisation, no allocation.  With n_listed = 0 the pass gives
+ * xvcgpu_frame_pass_bi_refs' bytes.  Not together with affine motion, adaptive QP or
+ * force_l1_mvd_zero. */
+xvcgpu_status xvcgpu_fp_bi_merge_rank(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_bi_refs_args *a,
+                                      const xvcgpu_frame_pass_bi_merge_args *m);
+xvcgpu_status xvcgpu_fp_bi_merge_choice(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_bi_refs_args *a,
+                                        const xvcgpu_frame_pass_bi_merge_args *m);
+xvcgpu_status xvcgpu_fp_bi_merge_skip(xvcgpu_ctx *ctx, const int32_t *d_nnz,
+                                      const int32_t *d_luma_tx_index, int n_cus,
+                                      xvcgpu_fp_bi_merge_result *d_choice);
+xvcgpu_status xvcgpu_frame_pass_bi_refs_merge(
+    xvcgpu_ctx *ctx, const xvcgpu_frame_pass_bi_refs_args *a,
+    const xvcgpu_frame_pass_bi_merge_args *m,
     const xvcgpu_me_plan *const plans[2][XVC_CS_MAX_REFS], int phases);
 
 /* ---- tables (host side, no GPU needed) ---------------------------------- *

@@ -787,8 +787,9 @@ typedef struct xvcgpu_frame_pass_affine_args {
  * :639).
  * One candidate, in merge-index order five per CU.  Vectors in 1/16 pel, unclipped.  The
  * candidates are an input, as a job's mvp is: there is no GetMergeCandidates derivation.
- * Laid out for two lists; the P pass takes a candidate as valid only with ref_idx =
- * {0, -1} and reads mv[0]. */
+ * Laid out for two lists: the P pass takes a candidate as valid only with ref_idx =
+ * {0, -1} and reads mv[0]; the B pass (xvcgpu_frame_pass_bi_refs_merge, below) takes either
+ * list, both, and every index of a list. */
 #define XVC_FP_MERGE_CANDS 5   /* constants::kNumInterMergeCandidates */
 typedef struct xvcgpu_fp_merge_cand {
   int8_t ref_idx[2];   /* per list; -1: list unused                                       */
@@ -893,6 +894,45 @@ typedef struct xvcgpu_frame_pass_bi_affine_args {
   int32_t reserved;
   xvcgpu_fp_bi_affine_result *d_choice;      /* n_cus                                    */
 } xvcgpu_frame_pass_bi_affine_args;
+
+/* ---- the B frame pass with merge mode (xvcgpu_frame_pass_bi_refs_merge) ------------ *
+ * CompressMerge in front of CompressInter for a B picture: the candidates are
+ * xvcgpu_fp_merge_cand with both lists in use - ref_idx[l] = -1 or an index into list l of
+ * the pass's tables, at least one list used; both: a bi-directional candidate.  The ranking
+ * record is xvcgpu_fp_merge_ranking.
+ * What the pass ends with for one CU, and what shows why.  A CU that does not merge -
+ * dist[order[0]] == UINT32_MAX, a plain job with XVC_ME_USE_LIC, a CU the list does not
+ * name -: use_merge 0, merge_idx -1, cost_merge UINT32_MAX, num 0, the plain choice's
+ * direction, pictures and vectors.  A CU whose plain record is all ones: every byte 0xff. */
+typedef struct xvcgpu_fp_bi_merge_result {
+  int32_t use_merge;
+  int32_t merge_idx;    /* order[0] of the ranking where merge won; else -1               */
+  int32_t skip;         /* use_merge and no transform block of the CU has a level
+                         * (xvcgpu_fp_bi_merge_skip; the choice writes 0)                 */
+  int32_t num;          /* the ranking's num; 0 where the CU was not ranked               */
+  int32_t inter_dir;    /* the chosen state's: 0 L0, 1 L1, 2 bi                           */
+  int32_t ref_idx[2];   /* ... picture per list; -1: list unused                          */
+  int32_t mv[2][2];     /* ... vector per list, 1/16 pel, unclipped; the unused list zero */
+  uint32_t cost_plain;  /* xvcgpu_fp_bi_refs_result.cost of the plain run                 */
+  uint32_t cost_merge;  /* dist[order[0]] + ((bits * lambda16) >> 16); UINT32_MAX: none   */
+  uint32_t cost;        /* the chosen state's                                             */
+} xvcgpu_fp_bi_merge_result;
+
+/* What xvcgpu_frame_pass_bi_refs_merge takes beside xvcgpu_frame_pass_bi_refs' block; every
+ * array is the caller's, allocated once.  d_order, lambda_sqrt, merge_side_bits: as
+ * xvcgpu_frame_pass_merge_args (the plain side's bits are the B block's side_bits_*).
+ * d_chosen: the plain records with the winners' motion - what the prediction's jobs, the CU
+ * records and the tail are made from; the B block's d_choice keeps the plain answer. */
+typedef struct xvcgpu_frame_pass_bi_merge_args {
+  const xvcgpu_fp_merge_cand *d_cands;   /* XVC_FP_MERGE_CANDS * n_cus                    */
+  const int32_t *d_order;                /* n_listed, or NULL                             */
+  int32_t n_listed;
+  uint32_t merge_side_bits;
+  double lambda_sqrt;
+  xvcgpu_fp_merge_ranking *d_rank;       /* n_cus; written for the listed CUs only        */
+  xvcgpu_fp_bi_merge_result *d_choice;   /* n_cus                                         */
+  xvcgpu_fp_bi_refs_result *d_chosen;    /* n_cus                                         */
+} xvcgpu_frame_pass_bi_merge_args;
 
 /* ---- C1, decision half: the folds of CompressAndEvalTransform and of
  * CompressAndEvalCbf (transform_encoder.cc:53-201, inter_search.cc:261-365).

@@ -232,6 +232,24 @@ class FramePassMergeArgs(C.Structure):
 
 assert C.sizeof(FramePassMergeArgs) == 64
 
+# the B frame pass with merge mode (xvcgpu_frame_pass_bi_refs_merge; include/xvcgpu_types.h):
+# the candidates and the ranking are the P pass's types
+FP_BI_MERGE_RESULT_DTYPE = np.dtype([
+    ("use_merge", "<i4"), ("merge_idx", "<i4"), ("skip", "<i4"), ("num", "<i4"),
+    ("inter_dir", "<i4"), ("ref_idx", "<i4", (2,)), ("mv", "<i4", (2, 2)),
+    ("cost_plain", "<u4"), ("cost_merge", "<u4"), ("cost", "<u4")])
+assert FP_BI_MERGE_RESULT_DTYPE.itemsize == 56
+
+
+class FramePassBiMergeArgs(C.Structure):
+    """xvcgpu_frame_pass_bi_merge_args (include/xvcgpu_types.h)"""
+    _fields_ = [("d_cands", C.c_void_p), ("d_order", C.c_void_p), ("n_listed", C.c_int32),
+                ("merge_side_bits", C.c_uint32), ("lambda_sqrt", C.c_double),
+                ("d_rank", C.c_void_p), ("d_choice", C.c_void_p), ("d_chosen", C.c_void_p)]
+
+
+assert C.sizeof(FramePassBiMergeArgs) == 56
+
 # xvcgpu_fp_bi_affine_result: CompressInter's two SearchMotion runs for one CU of a B picture
 FP_BI_AFFINE_RESULT_DTYPE = np.dtype([
     ("use_affine", "<i4"), ("inter_dir", "<i4"), ("ref_idx", "<i4", (2,)),
@@ -328,6 +346,8 @@ SYMBOLS = [
     "xvcgpu_frame_pass_bi_refs_affine",
     "xvcgpu_fp_merge_rank", "xvcgpu_fp_merge_choice", "xvcgpu_fp_merge_skip",
     "xvcgpu_frame_pass_merge",
+    "xvcgpu_fp_bi_merge_rank", "xvcgpu_fp_bi_merge_choice", "xvcgpu_fp_bi_merge_skip",
+    "xvcgpu_frame_pass_bi_refs_merge",
 ]
 
 _vp = C.c_void_p
@@ -560,6 +580,11 @@ def load_library(allow_missing=()):
         "xvcgpu_fp_merge_rank": [_vp, _vp, _vp, _vp, C.c_int, C.POINTER(FramePassMergeArgs)],
         "xvcgpu_fp_merge_choice": [_vp, _vp, _vp, C.c_int, C.POINTER(FramePassMergeArgs)],
         "xvcgpu_fp_merge_skip": [_vp, _vp, _vp, C.c_int, _vp],
+        "xvcgpu_fp_bi_merge_rank": [_vp, C.POINTER(FramePassBiRefsArgs),
+                                    C.POINTER(FramePassBiMergeArgs)],
+        "xvcgpu_fp_bi_merge_choice": [_vp, C.POINTER(FramePassBiRefsArgs),
+                                      C.POINTER(FramePassBiMergeArgs)],
+        "xvcgpu_fp_bi_merge_skip": [_vp, _vp, _vp, C.c_int, _vp],
         "xvcgpu_frame_pass_merge": [_vp, C.POINTER(FramePassArgs), C.POINTER(FramePassMergeArgs),
                                     _vp, C.c_int],
         "xvcgpu_fp_bi_affine_boot": [_vp, C.POINTER(FramePassBiRefsArgs),
@@ -574,6 +599,8 @@ def load_library(allow_missing=()):
                                                  C.POINTER(FramePassBiAffineArgs)],
         "xvcgpu_frame_pass_bi_refs_affine": [_vp, C.POINTER(FramePassBiRefsArgs),
                                              C.POINTER(FramePassBiAffineArgs), _vp, C.c_int],
+        "xvcgpu_frame_pass_bi_refs_merge": [_vp, C.POINTER(FramePassBiRefsArgs),
+                                            C.POINTER(FramePassBiMergeArgs), _vp, C.c_int],
     }
     if "xvcgpu_me_plan_destroy" not in allow_missing or hasattr(lib, "xvcgpu_me_plan_destroy"):
         lib.xvcgpu_me_plan_destroy.restype = None

@@ -11,7 +11,9 @@
 // original (wave_compare).  No prediction goes to memory and there is no candidate-job
 // array.  Lane 0 folds the ranking with merge_rank_fold (k_bipred.h), the arithmetic the
 // CU-state walk's fold uses.  Shapes as fp_bi_back_mvp_cost_kernel: every w, h in {4, 8, 16,
-// 32, 64}; any other shape, and a candidate that is not {0, -1}, gets UINT32_MAX.
+// 32, 64}; any other shape, and a candidate that is not {0, -1}, gets UINT32_MAX.  The B
+// pass's kernel (k_fp_bi_merge.h) takes candidates of either list, of both and of ref_idx > 0
+// and shares fp_merge_uni_dist, fp_merge_write_ranking and fp_merge_skip_body with this file.
 //
 // The choice is the pass's own rule in closed-form bits - not the reference's RD comparison,
 // which needs the entropy coder: cost_merge = dist[m0] + (((merge_side_bits + bits(m0)) *
@@ -57,6 +59,39 @@ __device__ __forceinline__ bool fp_merge_listed(const int32_t *order, int n_list
   return lo < n_listed && order[lo] == i;
 }
 
+// One candidate that uses one list, by one wave: the luma block at ClipMv(mx, my) of `ref`
+// into pred, SATD against the original at src.  pred is free again on return.  Shared with
+// the B pass's rank kernel (k_fp_bi_merge.h).
+__device__ __forceinline__ uint32_t fp_merge_uni_dist(int bd, const xvcgpu_me_block &b,
+                                                      const PlaneView &ref, int mx, int my,
+                                                      const uint16_t *src, int src_stride,
+                                                      int16_t *tmp, uint16_t *pred) {
+  bi_mc_luma(bd, b, ref, mx, my, tmp, pred);
+  wave_sync();
+  const uint32_t dist =
+      (uint32_t)wave_compare(XVC_METRIC_SATD, bd, 0, 0, b.w, b.h, src, src_stride, pred, b.w);
+  wave_sync();   // pred is the next candidate's
+  return dist;
+}
+
+// Lane 0's end of a rank kernel: the fold and the record
+__device__ __forceinline__ void fp_merge_write_ranking(const uint32_t (&dist)[XVC_FP_MERGE_CANDS],
+                                                       double lambda_sqrt,
+                                                       xvcgpu_fp_merge_ranking *out) {
+  double cost[XVC_FP_MERGE_CANDS];
+  int rank[XVC_FP_MERGE_CANDS];
+  xvcgpu_fp_merge_ranking r;
+  r.num = merge_rank_fold(dist, lambda_sqrt, cost, rank);
+  r.reserved = 0;
+#pragma unroll
+  for (int k = 0; k < XVC_FP_MERGE_CANDS; k++) {
+    r.dist[k] = dist[k];
+    r.order[k] = rank[k];
+    r.cost[k] = cost[k];
+  }
+  *out = r;
+}
+
 // grid: ceil(n_listed / 2); block: 128.  n_cus bounds the indices of `order`.
 __global__ void __launch_bounds__(128)
 fp_merge_rank_kernel(PlaneView orig, PlaneView ref, int bd, const xvcgpu_me_block *me,
@@ -83,25 +118,11 @@ fp_merge_rank_kernel(PlaneView orig, PlaneView ref, int bd, const xvcgpu_me_bloc
     // (one candidate per wave: the branch is scalar)
     if (!__builtin_amdgcn_readfirstlane((int)(shape && c.ref_idx[0] == 0 && c.ref_idx[1] == -1)))
       continue;
-    bi_mc_luma(bd, b, ref, c.mv[0][0], c.mv[0][1], sh[wave].tmp, sh[wave].pred);
-    wave_sync();
-    dist[m] = (uint32_t)wave_compare(XVC_METRIC_SATD, bd, 0, 0, b.w, b.h, src, orig.stride,
-                                     sh[wave].pred, b.w);
-    wave_sync();   // pred is the next candidate's
+    dist[m] = fp_merge_uni_dist(bd, b, ref, c.mv[0][0], c.mv[0][1], src, orig.stride,
+                                sh[wave].tmp, sh[wave].pred);
   }
   if (lane != 0) return;
-  double cost[XVC_FP_MERGE_CANDS];
-  int rank[XVC_FP_MERGE_CANDS];
-  xvcgpu_fp_merge_ranking r;
-  r.num = merge_rank_fold(dist, lambda_sqrt, cost, rank);
-  r.reserved = 0;
-#pragma unroll
-  for (int k = 0; k < XVC_FP_MERGE_CANDS; k++) {
-    r.dist[k] = dist[k];
-    r.order[k] = rank[k];
-    r.cost[k] = cost[k];
-  }
-  out[i] = r;
+  fp_merge_write_ranking(dist, lambda_sqrt, &out[i]);
 }
 
 // grid: ceil(n / 256); block: 256
@@ -155,16 +176,24 @@ fp_merge_choice_kernel(const xvcgpu_me_block *me, const xvcgpu_me_result *res, i
 
 // skip = use_merge && no transform block of the CU has a level.  A record whose use_merge
 // is neither 0 nor 1 (all ones: no search result) is left alone.  luma_tx_index: null = 3 i.
-// grid: ceil(n / 256); block: 256
-__global__ void __launch_bounds__(256)
-fp_merge_skip_kernel(const int32_t *nnz, const int32_t *luma_tx_index, int n,
-                     xvcgpu_fp_merge_result *choice) {
+// Record: xvcgpu_fp_merge_result, or the B pass's xvcgpu_fp_bi_merge_result (k_fp_bi_merge.h)
+template <class Record>
+__device__ __forceinline__ void fp_merge_skip_body(const int32_t *nnz,
+                                                   const int32_t *luma_tx_index, int n,
+                                                   Record *choice) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const int32_t use = choice[i].use_merge;
   if (use != 0 && use != 1) return;
   const int t = luma_tx_index ? luma_tx_index[i] : 3 * i;
   choice[i].skip = use == 1 && nnz[t] == 0 && nnz[t + 1] == 0 && nnz[t + 2] == 0;
+}
+
+// grid: ceil(n / 256); block: 256
+__global__ void __launch_bounds__(256)
+fp_merge_skip_kernel(const int32_t *nnz, const int32_t *luma_tx_index, int n,
+                     xvcgpu_fp_merge_result *choice) {
+  fp_merge_skip_body(nnz, luma_tx_index, n, choice);
 }
 
 #endif  // XVCGPU_K_FP_MERGE_H_

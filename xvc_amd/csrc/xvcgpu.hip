@@ -37,6 +37,7 @@
 #include "k_fp_affine.h"
 #include "k_fp_merge.h"
 #include "k_fp_bi_affine.h"
+#include "k_fp_bi_merge.h"
 #include "xvcgpu_internal.h"
 
 namespace {
@@ -3661,9 +3662,88 @@ static xvcgpu_status fp_bi_affine_run(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_b
   return st;
 }
 
+/* ---- the B frame pass with merge mode (k_fp_bi_merge.h) ---- */
+// What is wrong with the merge stage's block for n CUs beside the B block's plain choice
+// array, or null
+static const char *fp_bi_merge_check(const xvcgpu_frame_pass_bi_merge_args *m, int n,
+                                     const xvcgpu_fp_bi_refs_result *d_plain) {
+  if (m->n_listed < 0 || m->n_listed > n) return "merge: n_listed outside [0, n_cus]";
+  if (!(m->lambda_sqrt >= 0) || !std::isfinite(m->lambda_sqrt))
+    return "merge: lambda_sqrt must be finite and not below 0";
+  if (n > 0 && (!m->d_cands || !m->d_rank || !m->d_choice || !m->d_chosen))
+    return "merge: d_cands, d_rank, d_choice and d_chosen";
+  // (the stage reads the plain records and leaves them as they are)
+  if (n > 0 && d_plain &&
+      (m->d_chosen == d_plain || static_cast<const void *>(m->d_choice) == d_plain))
+    return "merge: d_chosen and d_choice must not be the plain pass's d_choice";
+  if (n > 0 && static_cast<const void *>(m->d_choice) == m->d_chosen)
+    return "merge: d_choice and d_chosen must be two arrays";
+  return nullptr;
+}
+
+// The tables of both blocks checked, as the stage's kernels read them
+static xvcgpu_status fp_bi_merge_dev(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_bi_refs_args *b,
+                                     const xvcgpu_frame_pass_bi_merge_args *m, const char *entry,
+                                     FpBiRefsDev *t) {
+  if (!ctx || !b || !m || b->p.n_cus < 0) return XVCGPU_INVALID_ARGUMENT;
+  const char *what = nullptr;
+  if (!fp_bi_refs_tables(b, t, &what)) return fail(ctx, XVCGPU_INVALID_ARGUMENT, what);
+  what = fp_bi_merge_check(m, b->p.n_cus, b->d_choice);
+  if (what) {
+    char msg[240];
+    snprintf(msg, sizeof(msg), "%s: %s", entry, what);
+    return fail(ctx, XVCGPU_INVALID_ARGUMENT, msg);
+  }
+  return XVCGPU_OK;
+}
+
+xvcgpu_status xvcgpu_fp_bi_merge_rank(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_bi_refs_args *b,
+                                      const xvcgpu_frame_pass_bi_merge_args *m) {
+  FpBiRefsDev t;
+  xvcgpu_status st = fp_bi_merge_dev(ctx, b, m, "fp_bi_merge_rank", &t);
+  if (st != XVCGPU_OK) return st;
+  if (!b->p.orig) return fail(ctx, XVCGPU_INVALID_ARGUMENT, "fp_bi_merge_rank: p.orig");
+  RefTable refs;
+  st = ref_table_of(ctx, b->p.orig, b->refs, b->n_refs, &refs);
+  if (st != XVCGPU_OK) return st;
+  if (m->n_listed == 0) return XVCGPU_OK;
+  hipLaunchKernelGGL(fp_bi_merge_rank_kernel, dim3((m->n_listed + 1) / 2), dim3(128), 0,
+                     ctx->stream, b->p.orig->v.c[0], refs, t, b->p.orig->bd, m->d_cands,
+                     m->d_order, m->n_listed, b->p.n_cus, m->lambda_sqrt, m->d_rank);
+  CHECK_LAUNCH(ctx, "fp_bi_merge_rank");
+  return XVCGPU_OK;
+}
+
+xvcgpu_status xvcgpu_fp_bi_merge_choice(xvcgpu_ctx *ctx, const xvcgpu_frame_pass_bi_refs_args *b,
+                                        const xvcgpu_frame_pass_bi_merge_args *m) {
+  FpBiRefsDev t;
+  const xvcgpu_status st = fp_bi_merge_dev(ctx, b, m, "fp_bi_merge_choice", &t);
+  if (st != XVCGPU_OK) return st;
+  const int n = b->p.n_cus;
+  if (n == 0) return XVCGPU_OK;
+  hipLaunchKernelGGL(fp_bi_merge_choice_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream,
+                     t, b->n_refs, n, b->d_choice, m->d_cands, m->d_order, m->n_listed, m->d_rank,
+                     m->merge_side_bits, m->d_choice, m->d_chosen, b->d_inter);
+  CHECK_LAUNCH(ctx, "fp_bi_merge_choice");
+  return XVCGPU_OK;
+}
+
+xvcgpu_status xvcgpu_fp_bi_merge_skip(xvcgpu_ctx *ctx, const int32_t *d_nnz,
+                                      const int32_t *d_luma_tx_index, int n_cus,
+                                      xvcgpu_fp_bi_merge_result *d_choice) {
+  if (!ctx || n_cus < 0 || (n_cus && (!d_nnz || !d_choice))) return XVCGPU_INVALID_ARGUMENT;
+  if (n_cus == 0) return XVCGPU_OK;
+  hipLaunchKernelGGL(fp_bi_merge_skip_kernel, dim3((n_cus + 255) / 256), dim3(256), 0,
+                     ctx->stream, d_nnz, d_luma_tx_index, n_cus, d_choice);
+  CHECK_LAUNCH(ctx, "fp_bi_merge_skip");
+  return XVCGPU_OK;
+}
+
 // q: null = one QP (xvcgpu_frame_pass_bi_refs), else xvcgpu_frame_pass_bi_refs_aqp.
 // entry: the name in front of a refusal.  back: xvcgpu_frame_pass_bi_back - the folds of
 // k_fp_bi_back.h, with the predictor-cost launch into d_l1_mvp_cost in front of them.
+// m: xvcgpu_frame_pass_bi_refs_merge - the merge stage behind the choice; what follows reads
+// m->d_chosen.
 static xvcgpu_status frame_pass_bi_refs_impl(xvcgpu_ctx *ctx,
                                              const xvcgpu_frame_pass_bi_refs_args *b,
                                              const xvcgpu_me_plan *const plans[2][XVC_CS_MAX_REFS],
@@ -3671,7 +3751,8 @@ static xvcgpu_status frame_pass_bi_refs_impl(xvcgpu_ctx *ctx,
                                              const char *entry = "frame_pass_bi_refs",
                                              bool back = false,
                                              uint32_t *d_l1_mvp_cost = nullptr,
-                                             const xvcgpu_frame_pass_bi_affine_args *f = nullptr) {
+                                             const xvcgpu_frame_pass_bi_affine_args *f = nullptr,
+                                             const xvcgpu_frame_pass_bi_merge_args *m = nullptr) {
   if (!ctx || !b || !b->p.rec) return XVCGPU_INVALID_ARGUMENT;
   // the P pass's block with list 0's first picture in the fields the shared helpers read
   xvcgpu_frame_pass_args pa = b->p;
@@ -3688,6 +3769,10 @@ static xvcgpu_status frame_pass_bi_refs_impl(xvcgpu_ctx *ctx,
   FPB_NEED(n == a->n_cus_total && a->db_y_begin == 0 && a->db_y_end >= a->rec->h &&
                a->dbh_y_end >= a->rec->h && a->ssd_y_begin == 0 && a->ssd_y_end >= a->rec->h,
            "whole pictures only (no row shard)");
+  if (m) {
+    const char *bad = fp_bi_merge_check(m, n, b->d_choice);
+    FPB_NEED(!bad, bad);
+  }
   if ((phases & XVC_FP_ENCODE) && n > 0) {
     FPB_NEED(a->form == XVC_FP_FORM_FWD_TRANSFORM || a->form == XVC_FP_FORM_RESIDUAL ||
                  a->form == XVC_FP_FORM_RESIDUAL_RDOQ,
@@ -3704,6 +3789,7 @@ static xvcgpu_status frame_pass_bi_refs_impl(xvcgpu_ctx *ctx,
       const char *bad = fp_bi_affine_check(f, n);
       FPB_NEED(!bad, bad);
     }
+    FPB_NEED(!m || a->d_nnz, "d_nnz: the skip flag is read from it");
     FPB_NEED(a->orig, "orig");
     for (int k = 0; k < b->n_refs; k++)
       FPB_NEED(b->refs[k] && b->refs[k]->w == a->orig->w && b->refs[k]->h == a->orig->h &&
@@ -3771,13 +3857,23 @@ static xvcgpu_status frame_pass_bi_refs_impl(xvcgpu_ctx *ctx,
     if (st == XVCGPU_OK)
       st = back ? xvcgpu_fp_bi_back_choice(ctx, b) : xvcgpu_fp_bi_refs_choice(ctx, b);
     if (st == XVCGPU_OK && f && n > 0) st = fp_bi_affine_run(ctx, b, f, t.rmax);
+    // the merge stage; the CU records behind it read the chosen records (the prediction
+    // reads d_inter, which the stage rewrites for its winners)
+    xvcgpu_frame_pass_bi_refs_args chosen = *b;
+    if (m && n > 0) {
+      if (st == XVCGPU_OK) st = xvcgpu_fp_bi_merge_rank(ctx, b, m);
+      if (st == XVCGPU_OK) st = xvcgpu_fp_bi_merge_choice(ctx, b, m);
+      chosen.d_choice = m->d_chosen;
+    }
     // (the prediction reads its `rec` for LIC jobs only: there are none)
     if (st == XVCGPU_OK)
       st = xvcgpu_inter_pred_batch(ctx, b->refs, b->n_refs, a->rec, a->pred, b->d_inter, 3 * n);
     if (st == XVCGPU_OK) st = fp_residual(ctx, a, rec, r.form);
     if (st == XVCGPU_OK)
       st = f ? xvcgpu_cu_info_from_bi_affine_choice(ctx, b, f)
-             : xvcgpu_cu_info_from_choice_refs(ctx, b);
+             : xvcgpu_cu_info_from_choice_refs(ctx, &chosen);
+    if (st == XVCGPU_OK && m && n > 0)
+      st = xvcgpu_fp_bi_merge_skip(ctx, a->d_nnz, a->d_luma_tx_index, n, m->d_choice);
     if (st == XVCGPU_OK && q) st = xvcgpu_cu_info_set_qp(ctx, a->d_cus_own, q->d_cu_qp, n);
   }
   if (st == XVCGPU_OK) st = fp_tail(ctx, a, phases, r.fused_tail, 1);
@@ -3800,6 +3896,18 @@ xvcgpu_status xvcgpu_frame_pass_bi_refs_affine(
                 "frame_pass_bi_refs_affine: phases: the second run belongs to XVC_FP_ENCODE");
   return frame_pass_bi_refs_impl(ctx, b, plans, phases, nullptr, "frame_pass_bi_refs_affine",
                                  false, nullptr, f);
+}
+
+xvcgpu_status xvcgpu_frame_pass_bi_refs_merge(
+    xvcgpu_ctx *ctx, const xvcgpu_frame_pass_bi_refs_args *b,
+    const xvcgpu_frame_pass_bi_merge_args *m,
+    const xvcgpu_me_plan *const plans[2][XVC_CS_MAX_REFS], int phases) {
+  if (!ctx || !m) return XVCGPU_INVALID_ARGUMENT;
+  if (!(phases & XVC_FP_ENCODE))
+    return fail(ctx, XVCGPU_INVALID_ARGUMENT,
+                "frame_pass_bi_refs_merge: phases: the merge stage belongs to XVC_FP_ENCODE");
+  return frame_pass_bi_refs_impl(ctx, b, plans, phases, nullptr, "frame_pass_bi_refs_merge",
+                                 false, nullptr, nullptr, m);
 }
 
 xvcgpu_status xvcgpu_frame_pass_bi_refs_aqp(

@@ -642,8 +642,69 @@ class FramePassBiRefs {
       ctx_.Check(affine_entry_(ctx_.get(), &b, &affine_args_, plans, phases));
       return;
     }
+    if (merge_entry_) {    // (named by SetMerge alone)
+      ctx_.Check(merge_entry_(ctx_.get(), &b, &merge_args_, plans, phases));
+      return;
+    }
     ctx_.Check(xvcgpu_frame_pass_bi_refs(ctx_.get(), &b, plans, phases));
   }
+
+  // What a B pass with merge mode takes beside the plain pass's jobs, on the host
+  // (pipeline.bi_merge_cand_array / bi_merge_args: the same bytes): the candidates from
+  // ref_idx[n_cus][5][2] (per list the picture's index in that list, -1: unused) and
+  // mv[n_cus][5][2][2] (1/16 pel, unclipped; merge-index order), and the args block from its
+  // numbers (pointers null).
+  static std::vector<xvcgpu_fp_merge_cand> MergeCands(const int32_t *ref_idx, const int32_t *mv,
+                                                      int n_cus) {
+    std::vector<xvcgpu_fp_merge_cand> c(static_cast<size_t>(n_cus) * XVC_FP_MERGE_CANDS,
+                                        xvcgpu_fp_merge_cand());
+    for (size_t k = 0; k < c.size(); k++)
+      for (int l = 0; l < 2; l++) {
+        c[k].ref_idx[l] = static_cast<int8_t>(ref_idx[2 * k + l]);
+        c[k].mv[l][0] = mv[4 * k + 2 * l];
+        c[k].mv[l][1] = mv[4 * k + 2 * l + 1];
+      }
+    return c;
+  }
+  static xvcgpu_frame_pass_bi_merge_args MergeArgs(int n_listed, uint32_t merge_side_bits,
+                                                   double lambda_sqrt) {
+    xvcgpu_frame_pass_bi_merge_args m = xvcgpu_frame_pass_bi_merge_args();
+    m.n_listed = n_listed;
+    m.merge_side_bits = merge_side_bits;
+    m.lambda_sqrt = lambda_sqrt;
+    return m;
+  }
+
+  // From now on every Run tries merge mode for every CU behind the plain choice
+  // (xvcgpu_frame_pass_bi_refs_merge): the five candidates per CU - of list 0, of list 1 or
+  // bi-directional - are ranked as InterSearch::SearchMergeCandidates ranks them and the best
+  // is taken where its closed-form price is not above the plain choice's; a merge CU without
+  // levels is a skip CU.  lambda_sqrt < 0: FramePass::LambdaSqrtForQp(qp).  Not together
+  // with low_delay, SetAffine or SetAdaptiveQp.
+  void SetMerge(const int32_t *ref_idx, const int32_t *mv, uint32_t merge_side_bits = 1,
+                double lambda_sqrt = -1.0) {
+    if (low_delay_ || affine_entry_ || aqp_)
+      throw Error(XVCGPU_INVALID_ARGUMENT,
+                  "SetMerge: not together with low_delay, SetAffine or SetAdaptiveQp");
+    const size_t n = static_cast<size_t>(n_cus_ > 0 ? n_cus_ : 1);
+    std::vector<xvcgpu_fp_merge_cand> cands = MergeCands(ref_idx, mv, n_cus_);
+    if (cands.empty()) cands.push_back(xvcgpu_fp_merge_cand());   // (no empty device array)
+    merge_args_ = MergeArgs(n_cus_, merge_side_bits,
+                            lambda_sqrt < 0 ? FramePass::LambdaSqrtForQp(qp_) : lambda_sqrt);
+    d_cands_.reset(new DeviceArray<xvcgpu_fp_merge_cand>(ctx_, cands));
+    d_rank_.reset(new DeviceArray<xvcgpu_fp_merge_ranking>(ctx_, n));
+    d_merge_choice_.reset(new DeviceArray<xvcgpu_fp_bi_merge_result>(ctx_, n));
+    d_chosen_.reset(new DeviceArray<xvcgpu_fp_bi_refs_result>(ctx_, n));
+    merge_args_.d_cands = d_cands_->data();
+    merge_args_.d_rank = d_rank_->data();
+    merge_args_.d_choice = d_merge_choice_->data();
+    merge_args_.d_chosen = d_chosen_->data();
+    merge_entry_ = &xvcgpu_frame_pass_bi_refs_merge;
+  }
+  // the last Run's records per CU (synchronise)
+  std::vector<xvcgpu_fp_merge_ranking> MergeRank() const { return d_rank_->ToHost(); }
+  std::vector<xvcgpu_fp_bi_merge_result> MergeChoice() const { return d_merge_choice_->ToHost(); }
+  std::vector<xvcgpu_fp_bi_refs_result> ChosenResults() const { return d_chosen_->ToHost(); }
 
   // What a B pass with affine motion takes beside the plain pass's jobs, on the host
   // (pipeline.bi_affine_jobs: the same bytes): E = 2 * Rmax jobs per CU, job [i * E + l * Rmax
@@ -687,6 +748,7 @@ class FramePassBiRefs {
       throw Error(XVCGPU_INVALID_ARGUMENT,
                   "SetAffine: not together with low_delay (force_l1_mvd_zero)");
     if (aqp_) throw Error(XVCGPU_INVALID_ARGUMENT, "SetAffine: not together with SetAdaptiveQp");
+    if (merge_entry_) throw Error(XVCGPU_INVALID_ARGUMENT, "SetAffine: not together with SetMerge");
     std::vector<xvcgpu_affine_me_block> jobs;
     std::vector<uint8_t> slots;
     std::vector<int32_t> order;
@@ -722,6 +784,8 @@ class FramePassBiRefs {
   void SetAdaptiveQp(int aqp_strength) {
     if (affine_entry_)
       throw Error(XVCGPU_INVALID_ARGUMENT, "SetAdaptiveQp: not together with SetAffine");
+    if (merge_entry_)
+      throw Error(XVCGPU_INVALID_ARGUMENT, "SetAdaptiveQp: not together with SetMerge");
     aqp_.reset(new AdaptiveQpArrays(ctx_, w_, h_, bd_, qp_, aqp_strength, n_cus_));
   }
   std::vector<int8_t> CtuDeltaQp() const { return aqp_->CtuDeltaQp(); }
@@ -897,6 +961,15 @@ class FramePassBiRefs {
   std::unique_ptr<DeviceArray<uint8_t>> d_affine_uni_slots_, d_affine_bi_slots_;
   std::unique_ptr<DeviceArray<int32_t>> d_affine_order_;
   std::unique_ptr<DeviceArray<xvcgpu_fp_bi_affine_result>> d_affine_choice_;
+  // SetMerge
+  xvcgpu_frame_pass_bi_merge_args merge_args_;
+  xvcgpu_status (*merge_entry_)(xvcgpu_ctx *, const xvcgpu_frame_pass_bi_refs_args *,
+                                const xvcgpu_frame_pass_bi_merge_args *,
+                                const xvcgpu_me_plan *const[2][XVC_CS_MAX_REFS], int) = nullptr;
+  std::unique_ptr<DeviceArray<xvcgpu_fp_merge_cand>> d_cands_;
+  std::unique_ptr<DeviceArray<xvcgpu_fp_merge_ranking>> d_rank_;
+  std::unique_ptr<DeviceArray<xvcgpu_fp_bi_merge_result>> d_merge_choice_;
+  std::unique_ptr<DeviceArray<xvcgpu_fp_bi_refs_result>> d_chosen_;
 };
 
 }  // namespace xvc_gpu

@@ -10,6 +10,15 @@
 
 namespace {
 
+// SetMerge's inputs and where its records go
+struct MergeIo {
+  const int32_t *ref_idx, *mv;   // [n][5][2], [n][5][2][2]
+  double lambda_sqrt;            // < 0: the QP's
+  xvcgpu_fp_merge_ranking *out_rank;
+  xvcgpu_fp_bi_merge_result *out_choice;
+  xvcgpu_fp_bi_refs_result *out_chosen;
+};
+
 // low_delay: RefLists::low_delay; aqp_strength < 0: one QP; out_l1_mvp_cost[n * 3]: NULL or
 // the predictor costs of a low_delay pass
 int RunBiRefs(xvcgpu_ctx *ctx, int width, int height, int bitdepth, int qp, int cur_poc,
@@ -17,7 +26,7 @@ int RunBiRefs(xvcgpu_ctx *ctx, int width, int height, int bitdepth, int qp, int 
               xvcgpu_picture *orig, xvcgpu_picture *const *ref_pics, xvcgpu_picture *rec,
               const xvcgpu_me_block *blocks, int n, xvcgpu_fp_bi_refs_result *out_choice,
               xvcgpu_cu_info *out_cus, uint64_t *out_ssd, uint32_t *out_l1_mvp_cost,
-              xvcgpu_fp_bi_affine_result *out_affine = nullptr) {
+              xvcgpu_fp_bi_affine_result *out_affine = nullptr, const MergeIo *merge = nullptr) {
   if (!ctx || !num_ref || !pocs || !orig || !ref_pics || !rec || !out_choice || !out_cus ||
       !out_ssd)
     return XVCGPU_INVALID_ARGUMENT;
@@ -35,6 +44,7 @@ int RunBiRefs(xvcgpu_ctx *ctx, int width, int height, int bitdepth, int qp, int 
     if (aqp_strength >= 0) pass.SetAdaptiveQp(aqp_strength);
     // (affine jobs carry the plain jobs' lambda)
     if (out_affine) pass.SetAffine(blocks && n ? blocks[0].lambda16 : 0);
+    if (merge) pass.SetMerge(merge->ref_idx, merge->mv, 1, merge->lambda_sqrt);
     xvc_gpu::Picture o(c, orig), r(c, rec);
     // one view per handle: the lists name a re-used picture by the same object
     std::vector<std::unique_ptr<xvc_gpu::Picture>> views;
@@ -65,6 +75,14 @@ int RunBiRefs(xvcgpu_ctx *ctx, int width, int height, int bitdepth, int qp, int 
     if (out_affine) {
       const std::vector<xvcgpu_fp_bi_affine_result> both = pass.AffineChoices();
       std::memcpy(out_affine, both.data(), both.size() * sizeof(both[0]));
+    }
+    if (merge) {
+      const std::vector<xvcgpu_fp_merge_ranking> rank = pass.MergeRank();
+      const std::vector<xvcgpu_fp_bi_merge_result> won = pass.MergeChoice();
+      const std::vector<xvcgpu_fp_bi_refs_result> chosen = pass.ChosenResults();
+      std::memcpy(merge->out_rank, rank.data(), n * sizeof(rank[0]));
+      std::memcpy(merge->out_choice, won.data(), n * sizeof(won[0]));
+      std::memcpy(merge->out_chosen, chosen.data(), n * sizeof(chosen[0]));
     }
     if (out_l1_mvp_cost && low_delay) {
       const std::vector<uint32_t> cost = pass.L1MvpCost();
@@ -105,6 +123,25 @@ int xvc_host_frame_pass_bi_refs_affine(xvcgpu_ctx *ctx, int width, int height, i
   if (!out_affine) return XVCGPU_INVALID_ARGUMENT;
   return RunBiRefs(ctx, width, height, bitdepth, qp, cur_poc, false, -1, num_ref, pocs, orig,
                    ref_pics, rec, blocks, n, out_choice, out_cus, out_ssd, nullptr, out_affine);
+}
+
+// The same with SetMerge: candidates ref_idx[n][5][2] and mv[n][5][2][2], merge_side_bits 1,
+// lambda_sqrt (< 0: the QP's); out_rank[n], out_merge[n], out_chosen[n].
+int xvc_host_frame_pass_bi_refs_merge(xvcgpu_ctx *ctx, int width, int height, int bitdepth,
+                                      int qp, int cur_poc, const int32_t *num_ref,
+                                      const int32_t *pocs, xvcgpu_picture *orig,
+                                      xvcgpu_picture *const *ref_pics, xvcgpu_picture *rec,
+                                      const xvcgpu_me_block *blocks, int n,
+                                      const int32_t *ref_idx, const int32_t *mv,
+                                      double lambda_sqrt, xvcgpu_fp_bi_refs_result *out_choice,
+                                      xvcgpu_cu_info *out_cus, uint64_t *out_ssd,
+                                      xvcgpu_fp_merge_ranking *out_rank,
+                                      xvcgpu_fp_bi_merge_result *out_merge,
+                                      xvcgpu_fp_bi_refs_result *out_chosen) {
+  if (!ref_idx || !mv || !out_rank || !out_merge || !out_chosen) return XVCGPU_INVALID_ARGUMENT;
+  const MergeIo io = {ref_idx, mv, lambda_sqrt, out_rank, out_merge, out_chosen};
+  return RunBiRefs(ctx, width, height, bitdepth, qp, cur_poc, false, -1, num_ref, pocs, orig,
+                   ref_pics, rec, blocks, n, out_choice, out_cus, out_ssd, nullptr, nullptr, &io);
 }
 
 // The same with RefLists::low_delay = true (lists that lie wholly before cur_poc), with

@@ -286,6 +286,72 @@ def merge_args(n_listed, side_bits, merge_side_bits, lambda_sqrt, d_cands=None, 
     return m
 
 
+def bi_merge_cand_array(cands, n_cus):
+    """A B pass's merge candidates as api.FP_MERGE_CAND_DTYPE [n_cus, 5]: from such an array as
+    it is, or from a pair (ref_idx [n_cus, 5, 2], mv [n_cus, 5, 2, 2]) of integer arrays -
+    per list the picture's index in that list (-1: list unused) and its vector (x, y; 1/16
+    pel, unclipped).  The same bytes as xvc_gpu::FramePassBiRefs::MergeCands makes."""
+    if isinstance(cands, np.ndarray) and cands.dtype == api.FP_MERGE_CAND_DTYPE:
+        if cands.shape != (n_cus, api.FP_MERGE_CANDS):
+            raise ValueError("merge_cands: expected %d x %d candidates, got shape %r"
+                             % (n_cus, api.FP_MERGE_CANDS, cands.shape))
+        return np.ascontiguousarray(cands)
+    try:
+        ref_idx, mv = (np.asarray(v) for v in cands)
+    except (TypeError, ValueError):
+        raise ValueError("merge_cands: api.FP_MERGE_CAND_DTYPE [n_cus, 5] or a pair (ref_idx "
+                         "[n_cus, 5, 2], mv [n_cus, 5, 2, 2]) expected")
+    want = (n_cus, api.FP_MERGE_CANDS, 2)
+    if ref_idx.shape != want or mv.shape != want + (2,) or \
+            not np.issubdtype(ref_idx.dtype, np.integer) or not np.issubdtype(mv.dtype, np.integer):
+        raise ValueError("merge_cands: expected integer arrays ref_idx %r and mv %r, got %r %s "
+                         "and %r %s" % (want, want + (2,), ref_idx.shape, ref_idx.dtype, mv.shape,
+                                        mv.dtype))
+    if len(ref_idx) and (ref_idx.min() < -128 or ref_idx.max() > 127):
+        raise ValueError("merge_cands: ref_idx does not fit the candidate's int8")
+    out = np.zeros((n_cus, api.FP_MERGE_CANDS), api.FP_MERGE_CAND_DTYPE)
+    out["ref_idx"] = ref_idx
+    out["mv"] = mv
+    return out
+
+
+class _BiMergeArrays:
+    """What a B pass with merge mode holds beside the plain pass's state: the arrays of
+    xvcgpu_frame_pass_bi_merge_args (allocated once; every run writes the work arrays)."""
+
+    def __init__(self, ctx, desc, cands, order, merge_side_bits, lambda_sqrt):
+        self.ctx, self.n_cus = ctx, desc.n_cus
+        self.merge_side_bits, self.lambda_sqrt = merge_side_bits, float(lambda_sqrt)
+        self.cands = cands                      # bi_merge_cand_array's
+        self.order, self.n_listed = order       # merge_order_array's
+        n = max(1, desc.n_cus)
+        self.d_cands = ctx.buffer(self.cands) if desc.n_cus else ctx.alloc(api.FP_MERGE_CAND_DTYPE.itemsize)
+        self.d_order = ctx.buffer(self.order) if self.order is not None and len(self.order) else None
+        self.d_rank = ctx.buffer(np.zeros(n, api.FP_MERGE_RANK_DTYPE))
+        self.d_choice = ctx.buffer(np.zeros(n, api.FP_BI_MERGE_RESULT_DTYPE))
+        self.d_chosen = ctx.buffer(np.zeros(n, api.FP_BI_REFS_RESULT_DTYPE))
+
+    def args(self):
+        return bi_merge_args(self.n_listed, self.merge_side_bits, self.lambda_sqrt,
+                             self.d_cands.ptr, self.d_order.ptr if self.d_order is not None else None,
+                             self.d_rank.ptr, self.d_choice.ptr, self.d_chosen.ptr)
+
+    def free(self):
+        for b in (self.d_cands, self.d_order, self.d_rank, self.d_choice, self.d_chosen):
+            if b is not None:
+                b.free()
+
+
+def bi_merge_args(n_listed, merge_side_bits, lambda_sqrt, d_cands=None, d_order=None,
+                  d_rank=None, d_choice=None, d_chosen=None):
+    """xvcgpu_frame_pass_bi_merge_args from its parts (pointers: integers or None)."""
+    m = api.FramePassBiMergeArgs()
+    m.d_cands, m.d_order, m.n_listed = d_cands, d_order, n_listed
+    m.merge_side_bits, m.lambda_sqrt = merge_side_bits, lambda_sqrt
+    m.d_rank, m.d_choice, m.d_chosen = d_rank, d_choice, d_chosen
+    return m
+
+
 _AQP_FORMS = ("fwd_transform", "residual", "residual_rdoq")
 
 
@@ -621,7 +687,10 @@ class FramePass:
                  search_range=96, row_range=None, fused=True, keep_levels=False,
                  rdoq=False, rdoq_packed=None, xcd_tiles=False, partition=None, form=None,
                  aqp_strength=None, affine=False, affine_mvp=None, side_bits=1,
-                 merge_cands=None, merge_side_bits=1, merge_lambda_sqrt=None, merge_order=None):
+                 merge_cands=None, merge_side_bits=1, merge_lambda_sqrt=None, merge_order=None,
+                 desc=None):
+        """desc: the FrameDescriptors of exactly these arguments, where the caller has made
+        them already (None: made here)."""
         self.ctx = ctx
         self.plan = None
         self.aqp = None
@@ -652,8 +721,8 @@ class FramePass:
         self.fused = fused and width % 8 == 0 and height % 8 == 0 and not keep_levels \
             and not self.rdoq_packed
         self.w, self.h, self.bd = width, height, bitdepth
-        self.desc = d = FrameDescriptors(width, height, qp, cu, search_range,
-                                         row_range, rdoq, bitdepth, xcd_tiles, partition)
+        self.desc = d = desc if desc is not None else FrameDescriptors(
+            width, height, qp, cu, search_range, row_range, rdoq, bitdepth, xcd_tiles, partition)
         # the kernels that take a CU whole hold CUs of 8 ... 16 samples a side (the grid
         # goes by its nominal side: what the picture edge cuts off a CU does not count)
         max_side, small_side = (d.max_side, d.min_side) if partition is not None else (cu, cu)
@@ -1054,15 +1123,48 @@ class BiRefsFramePass:
     cheaper state (the plain one on a tie).  Not together with low_delay or aqp_strength.
     affine_mvp: the jobs' corner predictors [l][r] -> [n_cus, 3, 2]; None: the plain job's
     mvp at every corner.  affine_choice(), affine_uni_results(), affine_bi_results(),
-    affine_jobs(), affine_bi_jobs(): the last run's records."""
+    affine_jobs(), affine_bi_jobs(): the last run's records.
+
+    merge_cands: the pass with merge mode (xvcgpu_frame_pass_bi_refs_merge): five candidates
+    per CU in merge-index order - a pair (ref_idx [n_cus, 5, 2], mv [n_cus, 5, 2, 2]): per list
+    the picture's index in that list, -1 for an unused list, and its vector in 1/16 pel,
+    unclipped; or api.FP_MERGE_CAND_DTYPE [n_cus, 5] -, an input as a job's mvp is.  Behind the
+    plain choice the listed CUs (merge_order: strictly ascending CU indices; None: every CU)
+    are ranked - a candidate of both lists is bi-predicted in the rank kernel's LDS - and a CU
+    takes its best candidate where that costs no more than its plain choice.  The prediction,
+    the CU records and the tail are the winners'; results()' choice records stay the plain
+    run's.  merge_side_bits: the bits of a merge CU in front of its index; merge_lambda_sqrt:
+    the ranking's double, None: lambda_sqrt_for_qp(qp).  Not together with affine,
+    aqp_strength or low_delay.  merge_rank(), merge_choice(), chosen_results(): the last
+    run's records."""
 
     def __init__(self, ctx, width, height, bitdepth=10, qp=32, cu=16, rdoq=False,
                  rdoq_packed=None, keep_levels=False, partition=None, cur_poc=8,
                  ref_pocs=((4,), (12,)), search_range=96, side_bits=(3, 3, 5),
-                 aqp_strength=None, low_delay=False, affine=False, affine_mvp=None):
+                 aqp_strength=None, low_delay=False, affine=False, affine_mvp=None,
+                 merge_cands=None, merge_side_bits=1, merge_lambda_sqrt=None, merge_order=None):
         self.ctx = ctx
         self.aqp = None
         self.affine = None
+        self.merge = None
+        desc = None
+        if merge_cands is not None:
+            for on, name in ((affine, "affine"), (aqp_strength is not None, "aqp_strength"),
+                             (low_delay, "low_delay")):
+                if on:
+                    raise ValueError("merge_cands: not together with %s (out of scope)" % name)
+            if merge_lambda_sqrt is None:
+                merge_lambda_sqrt = lambda_sqrt_for_qp(qp)
+            if not (np.isfinite(merge_lambda_sqrt) and merge_lambda_sqrt >= 0):
+                raise ValueError("merge_lambda_sqrt must be finite and not below 0")
+            if merge_side_bits < 0:
+                raise ValueError("merge_side_bits must not be below 0")
+            # the pass's descriptors, made here (on the host) so that a refused array is
+            # refused before anything is allocated; the FramePass below takes these
+            desc = FrameDescriptors(width, height, qp, cu, search_range, None, rdoq, bitdepth,
+                                    False, partition)
+            merge_cands = bi_merge_cand_array(merge_cands, desc.n_cus)
+            merge_order = merge_order_array(merge_order, desc.n_cus)
         if affine and low_delay:
             raise ValueError("affine: not together with low_delay (force_l1_mvd_zero): pricing "
                              "list 1's affine predictor is a pass of its own")
@@ -1087,7 +1189,7 @@ class BiRefsFramePass:
                              % (self.ref_pocs, cur_poc))
         self.rmax = max(self.num_ref)
         self.p = p = FramePass(ctx, width, height, bitdepth, qp, cu, search_range, None, True,
-                               keep_levels, rdoq, rdoq_packed, False, partition)
+                               keep_levels, rdoq, rdoq_packed, False, partition, desc=desc)
         self.desc = d = p.desc
         p.form = "fwd_transform" if p.rdoq_packed else ("residual_rdoq" if rdoq else "residual")
         self.form = p.form
@@ -1119,6 +1221,9 @@ class BiRefsFramePass:
         self.affine_mvp = affine_mvp
         if affine:
             self.affine = _BiAffineArrays(ctx, d.n_cus, self.me, self.same, self.slot, affine_mvp)
+        if merge_cands is not None:
+            self.merge = _BiMergeArrays(ctx, d, merge_cands, merge_order, merge_side_bits,
+                                        merge_lambda_sqrt)
 
     def set_jobs(self, me):
         """New search jobs me[l][r] (predictors, flags, lambda, range; the shapes stay);
@@ -1204,6 +1309,11 @@ class BiRefsFramePass:
             self.ctx._check(self.ctx.lib.xvcgpu_frame_pass_bi_refs_affine(
                 self.ctx.h, C.byref(a), C.byref(f), self.plan_handles(planned), phases))
             return
+        if self.merge is not None:
+            m = self.merge.args()
+            self.ctx._check(self.ctx.lib.xvcgpu_frame_pass_bi_refs_merge(
+                self.ctx.h, C.byref(a), C.byref(m), self.plan_handles(planned), phases))
+            return
         self.ctx._check(self.ctx.lib.xvcgpu_frame_pass_bi_refs(
             self.ctx.h, C.byref(a), self.plan_handles(planned), phases))
 
@@ -1273,6 +1383,16 @@ class BiRefsFramePass:
                 ("affine_bi", listed(f.d_bi, f.d_bi_slots, self.rmax, f.d_bi_res)),
                 ("affine_choice", lambda: chk(lib.xvcgpu_fp_bi_affine_choice(
                     ctx.h, C.byref(a), C.byref(fa))))]
+        chosen = a
+        if self.merge is not None:
+            ma = self.merge.args()
+            chosen = self._call_args(orig, refs, rec)
+            chosen.d_choice = self.merge.d_chosen.ptr
+            steps += [
+                ("merge_rank", lambda: chk(lib.xvcgpu_fp_bi_merge_rank(ctx.h, C.byref(a),
+                                                                       C.byref(ma)))),
+                ("merge_choice", lambda: chk(lib.xvcgpu_fp_bi_merge_choice(ctx.h, C.byref(a),
+                                                                           C.byref(ma))))]
         steps += [
             ("inter_pred", lambda: chk(lib.xvcgpu_inter_pred_batch(
                 ctx.h, handles, len(pics), rec.h_pic, p.pred.h_pic, self.d_inter.ptr, 3 * n)))]
@@ -1284,7 +1404,10 @@ class BiRefsFramePass:
                 ctx.h, C.byref(a), C.byref(fa)))))
         else:
             steps.append(("cu_info", lambda: chk(lib.xvcgpu_cu_info_from_choice_refs(
-                ctx.h, C.byref(a)))))
+                ctx.h, C.byref(chosen)))))
+        if self.merge is not None:
+            steps.append(("merge_skip", lambda: chk(lib.xvcgpu_fp_bi_merge_skip(
+                ctx.h, p.d_nnz.ptr, p.d_luma_idx.ptr, n, self.merge.d_choice.ptr))))
         all_cus, stride = p.d_cus.ptr, d.cu_map.shape[1]
         if fused_tail:
             return steps + [("deblock_pad_ssd", lambda: ctx.deblock_pad_ssd_dev(
@@ -1335,6 +1458,20 @@ class BiRefsFramePass:
         return (self.affine.d_bi.to_array(api.AFFINE_ME_DTYPE, k).reshape(-1, self.rmax),
                 self.affine.d_bi_slots.to_array(np.uint8, 2 * k).reshape(-1, self.rmax, 2))
 
+    def merge_rank(self):
+        """Merge mode: the last run's api.FP_MERGE_RANK_DTYPE record per CU (the CUs outside
+        the list keep what the array held)."""
+        return self.merge.d_rank.to_array(api.FP_MERGE_RANK_DTYPE, self.desc.n_cus)
+
+    def merge_choice(self):
+        """Merge mode: the last run's api.FP_BI_MERGE_RESULT_DTYPE record per CU."""
+        return self.merge.d_choice.to_array(api.FP_BI_MERGE_RESULT_DTYPE, self.desc.n_cus)
+
+    def chosen_results(self):
+        """Merge mode: the records the pass behind the choice was made from - the plain
+        choice records with the merge winners' direction, pictures, vectors and cost."""
+        return self.merge.d_chosen.to_array(api.FP_BI_REFS_RESULT_DTYPE, self.desc.n_cus)
+
     def inter_jobs(self):
         """The last run's prediction jobs [3 * n_cus]."""
         return self.d_inter.to_array(api.INTER_DTYPE, 3 * self.desc.n_cus)
@@ -1360,6 +1497,9 @@ class BiRefsFramePass:
         if self.affine is not None:
             self.affine.free()
             self.affine = None
+        if self.merge is not None:
+            self.merge.free()
+            self.merge = None
         bufs = [self.d_bi_jobs, self.d_bi_res, self.d_bi_slots, self.d_choice, self.d_inter]
         if self.d_l1_mvp_cost is not None:
             bufs.append(self.d_l1_mvp_cost)
